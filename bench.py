@@ -7,6 +7,9 @@ data-path collective — weak scaling).
                                                            N>1 WITHOUT a launcher: this process starts N rank processes itself,
                                                            before it has touched the GPU, relays rank 0's line, exits with their rc)
   python bench.py --workload cfg3|cfg4|cfg5 ...           (the other BASELINE configs, same JSON schema)
+  python bench.py --full ...                              (adds the rooflines, the stage split, the CPU baseline and, for the
+                                                           plain default, short runs of the other configs: see below)
+  python bench.py --dump-outputs DIR ...                  (writes what the last timed step computed to DIR/*.npy)
 
 Workloads (BASELINE.json `configs`):
   cfg2 (default)  configs[1]: fib_air 2^20-row trace, blowup 2.  A "step" proves `--batch` independent instances
@@ -17,9 +20,11 @@ Workloads (BASELINE.json `configs`):
   cfg5            configs[4]: the wide trace 2^16 x 2633 (benchmark_input, fib_air.rs:77-86, standing in for the
                   Keccak-f AIR trace): step = one bit-reversed coset LDE (blowup 2) + Poseidon2 MMCS commit of
                   the 2^17-row result.
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects: `roofline` (the
-dominant HBM-bound unit, algorithmic bytes per SURVEY.md §8d, timed with HIP events on the launch stream) and
-`cpu_baseline` (the C oracle timed on the host cores)."""
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the line: what it reports beyond the headline is what the timed steps themselves measured.  Everything
+that takes runs of its own is behind --full: `roofline` (the dominant HBM-bound unit, algorithmic bytes per SURVEY.md §8d,
+timed with HIP events on the launch stream), `valu_roofline` and `stages_ms`, `cpu_baseline` (the C oracle timed on the host
+cores) and `other_workloads`; a plain run reports them as null or leaves them out."""
 import argparse
 import json
 import os
@@ -128,9 +133,9 @@ PG_NOTE = ""
 
 
 def other_workloads(budget_s=240.0, child_timeout_s=120.0):
-    """The default run (what the driver records) also carries SHORT runs of the other single-GPU BASELINE configs and of the
+    """The default run under --full also carries SHORT runs of the other single-GPU BASELINE configs and of the
     reference's own configuration, so that their numbers are in a driver-run record and not only in builder-run profiles:
-    each is this same script in a child process (`--no-cpu-baseline --no-extras`, few steps), its line condensed to a few
+    each is this same script in a child process (`--full --no-cpu-baseline --no-extras`, few steps), its line condensed to a few
     numbers (the entries are the LAST thing in the line, the two BASELINE configs last of all, so that a reader who keeps only
     the tail of the line still sees them).  A child gets at most `child_timeout_s`; once `budget_s` is spent the remaining ones
     are recorded as skipped.  A child that fails leaves its error text; the main line does not depend on them."""
@@ -150,7 +155,7 @@ def other_workloads(budget_s=240.0, child_timeout_s=120.0):
             res.append(entry)
             continue
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-extras"],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-extras"],
                                capture_output=True, text=True, timeout=min(child_timeout_s, left))
             lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode != 0 or not lines:
@@ -175,6 +180,49 @@ def other_workloads(budget_s=240.0, child_timeout_s=120.0):
         entry["wall_s"] = round(time.perf_counter() - t0, 1)
         res.append(entry)
     return res
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # proof_words; the other files of a dump stay far below the rest of the 64 MB limit
+
+
+def dump_outputs(out_dir, step_out, job):
+    """--dump-outputs: what the last timed step handed back, as out_dir/<name>.npy in float64 (every value is an integer below
+    2^32, exact in float64).  The instances are fixed by the arguments, so two builds run with the same arguments compare file by file.
+      proof workloads: proof_slots, proof_lengths (bytes) and proof_sha256 (eight big-endian u32 words) of every proof of the step;
+                       proof_words: whole proofs as little-endian u32 words (rows zero-padded to the longest) of every proof if they
+                       fit DUMP_BUDGET_BYTES, else of a fixed, seeded choice of them, whose slots are proof_words_slots
+      cfg5:            root (the MMCS root, 8 words) and lde_rows: a fixed, seeded sample of the committed LDE's rows, their
+                       indices in lde_row_index"""
+    import hashlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    if isinstance(step_out, np.ndarray):  # cfg5: the root of the step's commit
+        import torch
+        save("root", step_out.astype(np.uint32))
+        rows = np.sort(np.random.default_rng(0).choice(job.lde.shape[0], min(256, job.lde.shape[0]), replace=False))
+        save("lde_row_index", rows)
+        save("lde_rows", job.lde.index_select(0, torch.from_numpy(rows).to(job.lde.device)).cpu().numpy().view(np.uint32))
+        return
+    items = sorted(step_out.items()) if isinstance(step_out, dict) else list(enumerate(step_out))
+    if not items or any(pf is None for _, pf in items):
+        raise RuntimeError("--dump-outputs: the last step handed back no proof for some slot")
+    slots = [i for i, _ in items]
+    proofs = [pf.tobytes() if hasattr(pf, "tobytes") else bytes(pf) for _, pf in items]
+    save("proof_slots", slots)
+    save("proof_lengths", [len(pf) for pf in proofs])
+    save("proof_sha256", [np.frombuffer(hashlib.sha256(pf).digest(), dtype=">u4") for pf in proofs])
+    n_words = max((len(pf) + 3) // 4 for pf in proofs)
+    keep = min(len(proofs), max(1, DUMP_BUDGET_BYTES // (8 * n_words)))
+    pick = np.arange(len(proofs)) if keep == len(proofs) else np.sort(np.random.default_rng(0).choice(len(proofs), keep, replace=False))
+    words = np.zeros((keep, n_words), dtype=np.uint32)
+    for r, j in enumerate(pick):
+        pf = proofs[j] + b"\0" * (-len(proofs[j]) % 4)
+        words[r, : len(pf) // 4] = np.frombuffer(pf, dtype="<u4")
+    save("proof_words_slots", [slots[j] for j in pick])
+    save("proof_words", words)
 
 
 def parse_cpulist(text):
@@ -277,15 +325,22 @@ def main():
     ap.add_argument("--log-blowup", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None, help="independent proofs per rank per step")
     ap.add_argument("--threads", type=int, default=None, help="concurrent provers (host threads/streams) per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of its own after the timed steps: the rooflines, the "
+                         "stage split, the CPU baseline and (default configuration) the short runs of the other configs, `other_workloads`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64): proofs, or the cfg5 root and LDE sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default run only: skip the short runs of the other BASELINE configs that are added to the line as `other_workloads`")
+                    help="with --full, default run only: skip the short runs of the other BASELINE configs that are added to the line as `other_workloads`")
     ap.add_argument("--hash", choices=["poseidon2", "keccak"], default="poseidon2",
                     help="poseidon2 = BASELINE.json's configuration (default); keccak = the hashes the reference itself wires")
     ap.add_argument("--hiding", action="store_true",
                     help="the reference's hiding configuration (MerkleTreeHidingMmcs + HidingFriPcs, fib_air.rs:40-65); with --hash keccak "
                          "this is exactly what the reference runs")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -516,6 +571,8 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
         prev, coll_state["pending"] = coll_state.get("pending"), timed("gather_launch_s", lambda: coll_state["gatherer"].launch(slot))
         return timed("gather_wait_s", lambda: prev.wait(copy=False) if prev is not None else None)
 
+    last = {}  # what the last step handed back (--dump-outputs): its proofs (on rank 0 after a gather), or cfg5's root
+
     def run_steps(first, count):
         # A failed collective is FATAL: an N-GPU line must never be printed without RCCL having moved the batch.
         try:
@@ -527,10 +584,11 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
             for k in range(first + 1, first + count):
                 inflight.append(issue(k))
                 retire(inflight.pop(0))
-            retire(inflight.pop(0))
+            last["step"] = retire(inflight.pop(0))
             pend = coll_state.pop("pending", None)
             if pend is not None:
-                timed("gather_wait_s", lambda: pend.wait(copy=False))  # the last step's proofs must be on rank 0 inside the timed region
+                # the last step's proofs must be on rank 0 inside the timed region
+                last["step"] = timed("gather_wait_s", lambda: pend.wait(copy=False))
         except Exception as e:
             if not use_gather:
                 raise
@@ -555,6 +613,8 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
     elapsed = time.perf_counter() - t0
     timing["on"] = False
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last.get("step"), job)
     cur_dev = -1 if stub else torch.cuda.current_device()
     # one row per rank, so that an N-rank line explains itself: what the rank proved, how long its own steps took, where it waited
     # (a scaling loss shows up as one rank's prove_wall_s, or as gather / scatter waits), and which host cores it ran on
@@ -582,7 +642,7 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
     units = args.batch * args.steps * world
     value = units / elapsed
 
-    roof = job.roofline()
+    roof = job.roofline() if args.full else None
     out = {
         "metric": job.metric_name(),
         "value": value,
@@ -620,7 +680,8 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
         "parity": "proof bytes / digests are compared with the repo's C oracle (a restatement of upstream Plonky3 from "
                   "recall; pinned by reference code only for the DFT): self-consistent, upstream parity UNPINNED",
     }
-    out.update(job.extra_report())
+    if args.full:
+        out.update(job.extra_report())
     vr = out.get("valu_roofline")
     if isinstance(vr, dict) and vr.get("valu_wave_instr_per_proof"):
         # the ruler that binds: what the timed region issued, in VALU wave-instructions per second, against the chip's measured issue peak
@@ -638,9 +699,9 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
                                     "workgroup generations: the hash kernels at their own VALU-bound rate), per GPU")
     if world > 1:
         out["cpu_baseline"] = "omitted for world > 1 (the CPU leg is timed by the N=1 run only)"
-    elif stub or args.no_cpu_baseline:
+    elif stub or args.no_cpu_baseline or not args.full:
         out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not stub:
         if args.workload == "cfg5":
             out["cpu_baseline"] = cpu_baseline_wide(job)
         else:
@@ -648,7 +709,7 @@ def run(args, job, dist, world, rank, local_rank, n_dev, backend, coll_dev, use_
     job.close()
     plain_default = (args.workload == "cfg2" and args.hash == "poseidon2" and not args.hiding and
                      (args.log_height, args.log_blowup) == (defaults["log_height"], defaults["log_blowup"]))
-    if rank == 0 and world == 1 and not stub and plain_default and not args.no_extras:
+    if rank == 0 and world == 1 and not stub and plain_default and args.full and not args.no_extras:
         out["other_workloads"] = other_workloads()
     if rank == 0:
         print(json.dumps(out))

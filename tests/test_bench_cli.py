@@ -106,7 +106,7 @@ def test_a_failing_rank_fails_the_launcher():
 
 
 def test_other_workloads_condenses_child_lines_and_survives_a_failing_child(monkeypatch):
-    """bench.py's default line carries short runs of the other configs (`other_workloads`), each this script in a child process.
+    """bench.py --full's default line carries short runs of the other configs (`other_workloads`), each this script in a child process.
     The condensation and the failure handling are checked here with canned children: a child that fails leaves its error text and
     the remaining ones still run."""
     import importlib.util
@@ -130,6 +130,7 @@ def test_other_workloads_condenses_child_lines_and_survives_a_failing_child(monk
     res = bench.other_workloads()
     assert len(res) == 4 and len(calls) == 4
     assert all("--no-cpu-baseline" in c and "--no-extras" in c for c in calls)  # a child never recurses into extras
+    assert all("--full" in c for c in calls)  # the condensed figures (roofline, VALU) come from the children's --full lines
     assert [e["label"] for e in res][-2:] == ["cfg3", "cfg5"]  # the BASELINE configs last: they must survive a tail of the line
     ok = [e for e in res if "error" not in e]
     bad = [e for e in res if "error" in e]
@@ -165,3 +166,80 @@ def test_pmc_profiles_are_keyed_by_the_build_and_staleness_is_said(tmp_path, mon
     monkeypatch.setattr(p3._lib, "_src_sha", None)
     assert bs._profile_json(("r04_pmc_lde_valu.json",))[2] is None  # no identity recorded: said so, not assumed fresh
     assert "predates" in bs._stale_note(None)
+
+
+def _stub_proof(a):
+    return (b"STUB" + int(a).to_bytes(8, "little")) * 5 + b"\0" * 4
+
+
+def _load_dump(d):
+    import numpy as np
+    out = {}
+    for name in ("proof_slots", "proof_lengths", "proof_sha256", "proof_words", "proof_words_slots"):
+        a = np.load(os.path.join(d, name + ".npy"))
+        assert a.dtype == np.float64, name
+        out[name] = a
+    return out
+
+
+def _dumped_proofs(dump):
+    import numpy as np
+    words = dump["proof_words"].astype(np.uint32)
+    lengths = dict(zip(dump["proof_slots"].astype(int).tolist(), dump["proof_lengths"].astype(int).tolist()))
+    return {s: words[r].astype("<u4").tobytes()[: lengths[s]] for r, s in enumerate(dump["proof_words_slots"].astype(int).tolist())}
+
+
+def test_dump_outputs_writes_the_last_timed_steps_proofs(tmp_path):
+    """--dump-outputs DIR: the proofs of the last timed step as float64 .npy files; the same arguments give the same files."""
+    import hashlib
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        res = _bench(["--steps", "3", "--warmup", "1", "--workload", "cfg4", "--dump-outputs", d],
+                     {"P3HIP_BENCH_STUB": "1", "P3HIP_BENCH_BACKEND": "gloo"})
+        assert res.returncode == 0, res.stderr
+        assert _line(res)["steps"] == 3
+    a, b = _load_dump(dirs[0]), _load_dump(dirs[1])
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert a["proof_slots"].tolist() == list(range(64)) and a["proof_words_slots"].tolist() == list(range(64))
+    proofs = _dumped_proofs(a)
+    assert proofs == {i: _stub_proof(i) for i in range(64)}  # single rank: every step proves instances 0..63
+    assert [bytes(np.asarray(h, dtype=">u4").tobytes()) for h in a["proof_sha256"].astype(np.uint32)] == \
+        [hashlib.sha256(_stub_proof(i)).digest() for i in range(64)]
+
+
+def test_dump_outputs_of_two_ranks_hold_the_gathered_last_step(tmp_path):
+    """Two ranks: rank 0 dumps the step gathered from both ranks, the last timed one (step warmup + steps - 1)."""
+    d = str(tmp_path / "dump")
+    res = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", d], {"P3HIP_BENCH_STUB": "1", "P3HIP_BENCH_BACKEND": "gloo"})
+    assert res.returncode == 0, res.stderr
+    last = 2  # steps 0 (warmup), 1, 2 of 64 instances each
+    assert _dumped_proofs(_load_dump(d)) == {i: _stub_proof(last * 64 + i) for i in range(64)}
+
+
+def test_dump_outputs_samples_proofs_beyond_the_budget(tmp_path, monkeypatch):
+    """Proofs that do not all fit the 64 MB limit: all lengths and hashes, whole words of a fixed, seeded choice of proofs."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 16 * 3)  # three 16-word proofs
+    proofs = [_stub_proof(i) for i in range(10)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), proofs, None)
+    a, b = _load_dump(str(tmp_path / "a")), _load_dump(str(tmp_path / "b"))
+    assert a["proof_lengths"].tolist() == [64] * 10 and a["proof_sha256"].shape == (10, 8)
+    assert a["proof_words"].shape == (3, 16) and a["proof_words_slots"].tolist() == b["proof_words_slots"].tolist()
+    assert all(_stub_proof(s) == pf for s, pf in _dumped_proofs(a).items())
+
+
+def test_plain_run_leaves_the_extra_measurements_to_full():
+    """A plain run times the steps and prints the line; the CPU baseline and the rooflines are --full's."""
+    res = _bench(["--steps", "2", "--warmup", "0"], {"P3HIP_BENCH_STUB": "1", "P3HIP_BENCH_BACKEND": "gloo"})
+    assert res.returncode == 0, res.stderr
+    out = _line(res)
+    assert out["cpu_baseline"] is None and out["roofline"] is None and "other_workloads" not in out
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["steps"] == 2 and out["ranks"][0]["proofs"] == 64

@@ -30,12 +30,12 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o bench
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench_1t -o bench1 -- python3 $ROOT/bench.py --steps 4 --warmup 1 --threads 1 --batch 8 --no-cpu-baseline --no-extras > $OUT/bench_cfg2_1prover_under_rocprof.json 2> $OUT/prof_bench_1t.err
 cd $ROOT
 say "bench lines (un-profiled)"
-python3 bench.py > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-python3 bench.py --workload cfg3 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
-python3 bench.py --workload cfg5 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
-python3 bench.py --workload cfg4 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_1gpu.json 2> $OUT/bench_cfg4.err
-python3 bench.py --hash keccak > $OUT/bench_keccak.json 2> $OUT/bench_keccak.err
-python3 bench.py --hash keccak --hiding > $OUT/bench_keccak_hiding.json 2> $OUT/bench_keccak_hiding.err
+python3 bench.py --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python3 bench.py --full --workload cfg3 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python3 bench.py --full --workload cfg5 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python3 bench.py --full --workload cfg4 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_1gpu.json 2> $OUT/bench_cfg4.err
+python3 bench.py --full --hash keccak > $OUT/bench_keccak.json 2> $OUT/bench_keccak.err
+python3 bench.py --full --hash keccak --hiding > $OUT/bench_keccak_hiding.json 2> $OUT/bench_keccak_hiding.err
 say "2 ranks started by bench.py --gpus 2 over gloo on one GPU (NOT RCCL)"
 P3HIP_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --workload cfg4 --steps 5 --warmup 1 > $OUT/bench_cfg4_2rank_gloo_rehearsal.json 2> $OUT/bench_2rank_gloo.err
 say "hiding prover timing"

@@ -23,12 +23,12 @@ cd $ROOT
 python3 tools/pmc_summarize.py $OUT/pmc_fetch $OUT/pmc_write gpurun_out/r05_pmc_lde.json > $OUT/pmc_lde.txt 2>&1; cat $OUT/pmc_lde.txt
 cp gpurun_out/r05_pmc_lde.json profiles/r05_pmc_lde.json
 say "bench lines (un-profiled)"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python3 bench.py --workload cfg3 --no-extras > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
-python3 bench.py --workload cfg5 --no-extras > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
-python3 bench.py --hash keccak --no-extras > $OUT/bench_keccak.json 2> $OUT/bench_keccak.err
-python3 bench.py --hash keccak --hiding --no-extras > $OUT/bench_keccak_hiding.json 2> $OUT/bench_keccak_hiding.err
-python3 bench.py --workload cfg4 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_1gpu.json 2> $OUT/bench_cfg4.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --workload cfg3 --no-extras > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python3 bench.py --full --workload cfg5 --no-extras > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python3 bench.py --full --hash keccak --no-extras > $OUT/bench_keccak.json 2> $OUT/bench_keccak.err
+python3 bench.py --full --hash keccak --hiding --no-extras > $OUT/bench_keccak_hiding.json 2> $OUT/bench_keccak_hiding.err
+python3 bench.py --full --workload cfg4 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_1gpu.json 2> $OUT/bench_cfg4.err
 say "soak: cfg2 x3, hiding x3"
 for i in 1 2 3; do
   python3 bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 2 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg2 run $i: %.1f proofs/s' % d['value'])"
