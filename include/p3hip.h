@@ -305,6 +305,51 @@ int p3hip_fib_batch_submit(p3hip_fib_batch_t *batch, size_t n, const uint64_t *a
 int p3hip_fib_batch_collect(p3hip_fib_batch_t *batch, uint64_t ticket, const uint8_t **proofs_out, size_t *lens_out);
 void p3hip_fib_batch_destroy(p3hip_fib_batch_t *batch);
 
+/* ---- a CALLER's trace and public values: prove(&config, &FibonacciAir {}, trace, &pis) (native/src/fib_air.rs:61,68-70) ----
+ * The trace is 2^log_n rows x 2 Montgomery words, row-major (what p3hip_fib_trace_dev writes); pis = [left of row 0, right of row 0,
+ * right of the last row] as Montgomery words, each < P (else ERR_BAD_ARG).  The proof commits to THIS trace and its transcript
+ * observes THESE pis, whether or not they agree: as in upstream's release builds, a trace that is no Fibonacci trace, or pis it does
+ * not satisfy, still yields a proof, and the verifiers reject it for those pis.  For a Fibonacci trace with its own pis the bytes are
+ * those of p3hip_fib_prover_prove(a, b).  Every prover and pool of the create functions above takes these entries (the hiding ones
+ * too; the enqueue form, as p3hip_fib_prover_enqueue, the non-hiding prover only).
+ * BUFFER CONTRACT of the _dev entries: d_trace is read in place (no copy).  The caller's writes to it must be complete, or ordered
+ * on the prover's stream, before the call; the buffer must stay unchanged until the prove call returns, or, after an enqueue, until
+ * finish has returned that proof.  A d_trace that hipPointerGetAttributes does not report as device memory of the prover's device,
+ * or whose allocation ends before 2^log_n rows, is refused before anything is launched.
+ * flags: P3HIP_PROVE_CHECK_TRACE runs p3hip_fib_check_trace_dev on the prover's stream first (upstream's debug-build
+ * check_constraints) and returns ERR_BAD_ARG without proving when a row breaks a rule ("constraints had nonzero value on row <i>");
+ * other bits are refused. */
+#define P3HIP_PROVE_CHECK_TRACE 1u
+/* p3hip_trace_check_t.mask bits: the rules of FibonacciAir (fib_air.rs:236-260) a row breaks.  is_transition is false on the
+ * last row and there is no wrap-around; with one row, row 0 is first and last. */
+#define P3HIP_TRACE_BAD_FIRST_LEFT 1u   /* first row: left != pis[0] */
+#define P3HIP_TRACE_BAD_FIRST_RIGHT 2u  /* first row: right != pis[1] */
+#define P3HIP_TRACE_BAD_NEXT_LEFT 4u    /* transition: next.left != right */
+#define P3HIP_TRACE_BAD_NEXT_RIGHT 8u   /* transition: next.right != left + right (mod P, of the words as integers) */
+#define P3HIP_TRACE_BAD_LAST_RIGHT 16u  /* last row: right != pis[2] */
+#define P3HIP_TRACE_BAD_RANGE 32u       /* a word of the row is >= P */
+typedef struct {
+    int64_t first_bad_row;  /* -1: every row holds */
+    uint32_t mask;          /* bits of first_bad_row */
+    uint64_t bad_rows;      /* rows with a nonzero mask */
+} p3hip_trace_check_t;
+/* check_constraints over a device trace of n rows (any n; d_trace 8-byte aligned, device memory of the current device): one
+ * streaming pass on `stream`, which the call synchronises. */
+int p3hip_fib_check_trace_dev(const uint32_t *d_trace, size_t n, const uint32_t pis[3], p3hip_trace_check_t *out, void *stream);
+/* the proof of a device trace; the bytes stay valid until the next prove / finish / destroy */
+int p3hip_fib_prover_prove_trace_dev(p3hip_fib_prover_t *prover, const uint32_t *d_trace, const uint32_t pis[3], unsigned flags,
+                                     const uint8_t **proof_out, size_t *proof_len);
+/* the same from host memory: n must equal 2^log_n; the rows are uploaded into the prover's own trace buffer on its stream */
+int p3hip_fib_prover_prove_trace(p3hip_fib_prover_t *prover, const uint32_t *host_trace, size_t n, const uint32_t pis[3], unsigned flags,
+                                 const uint8_t **proof_out, size_t *proof_len);
+/* p3hip_fib_prover_enqueue for a device trace (non-hiding provers); the proof comes back from p3hip_fib_prover_finish */
+int p3hip_fib_prover_enqueue_trace_dev(p3hip_fib_prover_t *prover, const uint32_t *d_trace, const uint32_t pis[3]);
+/* p3hip_fib_batch_prove for n device traces (device memory of the device the pool was created on, each complete before the call:
+ * the pool's provers run on streams of their own); pis holds 3 words per trace.  Every trace and pis word is checked before any
+ * prover starts. */
+int p3hip_fib_batch_prove_traces_dev(p3hip_fib_batch_t *batch, size_t n, const uint32_t *const *d_traces, const uint32_t *pis,
+                                     unsigned flags, const uint8_t **proofs_out, size_t *lens_out);
+
 /* ---- The reference's report-returning entry points (native/src/lib.rs:37-131 call fib_air::run_fib_air_zk /
  * fib_air::run_dft_benchmark and hand the returned String to Java).  Both write a NUL-terminated text of at most cap - 1 bytes
  * to out and return the length of the WHOLE text (snprintf convention); they never fail by status: a failure is text that

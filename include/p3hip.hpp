@@ -173,6 +173,25 @@ class FibAirProver {  // prove(&config, &FibonacciAir{}, generate_trace_rows(a, 
         check(p3hip_fib_prover_prove(h_, a, b, &p, &n));
         return std::vector<uint8_t>(p, p + n);
     }
+    // prove(&config, &FibonacciAir{}, trace, &pis) for a caller's trace (fib_air.rs:61,68-70): trace = 2^log_n rows x 2 Montgomery
+    // words, pis = canonical public values (reduced mod P).  check = upstream's debug-build check_constraints first: a bad row
+    // throws Error("constraints had nonzero value on row <i> ...") instead of proving.
+    std::vector<uint8_t> prove_trace(const RowMajorMatrix& trace, const uint64_t pis[3], bool check_trace = false) {
+        if (trace.width != 2) throw Error(P3HIP_ERR_BAD_ARG, "prove_trace: FibonacciAir traces have two columns");
+        const uint32_t pm[3] = {to_monty(pis[0]), to_monty(pis[1]), to_monty(pis[2])};
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_fib_prover_prove_trace(h_, trace.values.data(), trace.height(), pm, check_trace ? P3HIP_PROVE_CHECK_TRACE : 0u, &p, &n));
+        return std::vector<uint8_t>(p, p + n);
+    }
+    // the same for a trace in device memory of the prover's device (include/p3hip.h: buffer contract)
+    std::vector<uint8_t> prove_trace_dev(const uint32_t* d_trace, const uint64_t pis[3], bool check_trace = false) {
+        const uint32_t pm[3] = {to_monty(pis[0]), to_monty(pis[1]), to_monty(pis[2])};
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_fib_prover_prove_trace_dev(h_, d_trace, pm, check_trace ? P3HIP_PROVE_CHECK_TRACE : 0u, &p, &n));
+        return std::vector<uint8_t>(p, p + n);
+    }
 
   private:
     p3hip_fib_prover_t* h_ = nullptr;

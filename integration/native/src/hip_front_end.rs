@@ -16,10 +16,67 @@ type Val = BabyBear;
 /// include/p3hip.h `p3hip_cpu_dft_fn`
 type CpuDftFn = unsafe extern "C" fn(*mut c_void, *const u32, *mut u32, usize, usize) -> i32;
 
-// include/p3hip.h, "report-returning entry points"
+/// include/p3hip.h `p3hip_fri_params_t`
+#[repr(C)]
+struct FriParamsC {
+    log_blowup: u32,
+    log_final_poly_len: u32,
+    num_queries: u32,
+    proof_of_work_bits: u32,
+}
+#[repr(C)]
+struct FibProverC {
+    _opaque: [u8; 0],
+}
+const P3HIP_HASH_KECCAK: i32 = 1;
+
+// include/p3hip.h, "report-returning entry points" and "a CALLER's trace"
 extern "C" {
     fn p3hip_run_fib_air_zk(out: *mut c_char, cap: usize) -> i32;
     fn p3hip_run_dft_benchmark(cpu_dft: Option<CpuDftFn>, user: *mut c_void, out: *mut c_char, cap: usize) -> i32;
+    fn p3hip_fib_prover_create_hiding(hash: i32, log_n: u32, params: *const FriParamsC, seed: u64, stream: *mut c_void,
+                                      own_stream: i32, out: *mut *mut FibProverC) -> i32;
+    fn p3hip_fib_prover_prove_trace(prover: *mut FibProverC, host_trace: *const u32, n: usize, pis: *const u32, flags: u32,
+                                    proof_out: *mut *const u8, proof_len: *mut usize) -> i32;
+    fn p3hip_fib_prover_destroy(prover: *mut FibProverC);
+    fn p3hip_take_last_error() -> *const c_char;
+}
+
+fn last_error() -> String {
+    let p = unsafe { p3hip_take_last_error() };
+    if p.is_null() {
+        return String::from("unknown libp3hip error");
+    }
+    unsafe { std::ffi::CStr::from_ptr(p) }.to_string_lossy().into_owned()
+}
+
+/// `prove(&config, &FibonacciAir {}, trace, pis)` (fib_air.rs:61,68-70) in the reference's configuration (Keccak hashes,
+/// MerkleTreeHidingMmcs + HidingFriPcs seeded with 1, create_test_fri_params(_, 2)) for a trace the CALLER built, with the public
+/// values the caller chose: the proof bytes (wire format version 2), or the library's error text.  BabyBear is
+/// `#[repr(transparent)]` over its Montgomery `u32` (backend_hip.rs), so the trace and the public values are handed over as they
+/// lie in memory.  As upstream's release builds, a trace that is no Fibonacci trace, or pis it does not satisfy, is proven all
+/// the same and `verify` rejects the proof; debug builds check the constraints first (P3HIP_PROVE_CHECK_TRACE), as upstream's do.
+pub fn prove_fib_air_hip(trace: &RowMajorMatrix<Val>, pis: &[Val]) -> Result<Vec<u8>, String> {
+    let (h, w) = (trace.height(), trace.width());
+    if w != 2 || pis.len() != 3 || !h.is_power_of_two() {
+        return Err(format!("fib_air: expected a 2^k x 2 trace and 3 public values, got {h} x {w} and {}", pis.len()));
+    }
+    let params = FriParamsC { log_blowup: 2, log_final_poly_len: 2, num_queries: 2, proof_of_work_bits: 1 };
+    let flags: u32 = if cfg!(debug_assertions) { 1 } else { 0 }; // P3HIP_PROVE_CHECK_TRACE
+    let mut prover: *mut FibProverC = core::ptr::null_mut();
+    let log_n = h.trailing_zeros();
+    if unsafe { p3hip_fib_prover_create_hiding(P3HIP_HASH_KECCAK, log_n, &params, 1, core::ptr::null_mut(), 1, &mut prover) } != 0 {
+        return Err(last_error());
+    }
+    let mut proof: *const u8 = core::ptr::null();
+    let mut len = 0usize;
+    let rc = unsafe {
+        p3hip_fib_prover_prove_trace(prover, trace.values.as_ptr() as *const u32, h, pis.as_ptr() as *const u32, flags,
+                                     &mut proof, &mut len)
+    };
+    let out = if rc == 0 { Ok(unsafe { core::slice::from_raw_parts(proof, len) }.to_vec()) } else { Err(last_error()) };
+    unsafe { p3hip_fib_prover_destroy(prover) };
+    out
 }
 
 fn text_of(buf: &[c_char]) -> String {

@@ -97,6 +97,14 @@ _SIGS = {
     "p3hip_fib_batch_collect": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
     "p3hip_fib_batch_destroy": (None, [C.c_void_p]),
     "p3hip_verify_fib_air": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, C.c_void_p]),
+    "p3hip_fib_check_trace_dev": (C.c_int, [C.c_void_p, C.c_size_t, u32p, C.c_void_p, C.c_void_p]),
+    "p3hip_fib_prover_prove_trace_dev": (C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint, C.POINTER(C.POINTER(C.c_uint8)),
+                                                   C.POINTER(C.c_size_t)]),
+    "p3hip_fib_prover_prove_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, u32p, C.c_uint, C.POINTER(C.POINTER(C.c_uint8)),
+                                               C.POINTER(C.c_size_t)]),
+    "p3hip_fib_prover_enqueue_trace_dev": (C.c_int, [C.c_void_p, C.c_void_p, u32p]),
+    "p3hip_fib_batch_prove_traces_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), u32p, C.c_uint,
+                                                   C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
     "p3hip_mmcs_commit": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                     C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
 }

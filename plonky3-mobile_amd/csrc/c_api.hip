@@ -463,6 +463,58 @@ int p3hip_mmcs_commit_hash(int hash, const uint32_t* const* mats, const size_t* 
 }  // extern "C"
 
 // ---- fib_air prover (p3_uni_stark::prove as driven by native/src/fib_air.rs:60-70) ---------------
+// ---- a caller's trace (prove(&config, &FibonacciAir{}, trace, &pis), fib_air.rs:61,68-70): the checks every entry makes before
+// anything is launched, and the optional check_constraints pass ----
+// d_trace must be device memory of `device` (hipPointerGetAttributes) holding `rows` rows of two words from d_trace on
+static int check_device_trace(const uint32_t* d_trace, uint64_t rows, int device, const std::string& who) {
+    if (!d_trace) return fail(ERR_BAD_ARG, who + ": null trace");
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, d_trace) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ERR_BAD_ARG, who + ": the trace is not device memory");
+    }
+    if (attr.type != hipMemoryTypeDevice) return fail(ERR_BAD_ARG, who + ": the trace is not device memory");
+    if (attr.device != device)
+        return fail(ERR_BAD_ARG, who + ": the trace is on device " + std::to_string(attr.device) + ", the work on device " + std::to_string(device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_trace) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ERR_BAD_ARG, who + ": the trace's allocation is unknown");
+    }
+    const uint64_t off = (uint64_t)((const char*)d_trace - (const char*)base);
+    if (off > size || (size - off) / 8 < rows)
+        return fail(ERR_BAD_ARG, who + ": the trace's allocation holds fewer than " + std::to_string(rows) + " rows");
+    return OK;
+}
+static int check_pis_flags(const uint32_t* pis, unsigned flags, const std::string& who) {
+    if (!pis) return fail(ERR_BAD_ARG, who + ": null public values");
+    for (int k = 0; k < 3; k++)
+        if (pis[k] >= bb::P) return fail(ERR_BAD_ARG, who + ": public value " + std::to_string(k) + " is not a field element (>= P)");
+    if (flags & ~P3HIP_PROVE_CHECK_TRACE) return fail(ERR_BAD_ARG, who + ": unknown flag bits");
+    return OK;
+}
+// P3HIP_PROVE_CHECK_TRACE: check_constraints on the prover's stream first (upstream's debug builds, p3_uni_stark::prove);
+// then the proof.  A trace that breaks a rule is refused with upstream's panic text.
+template <class Prover>
+static int prove_trace_with(Prover& pr, const uint32_t* d_trace, const uint32_t* pis, unsigned flags, std::vector<uint8_t>* out) {
+    if (flags & P3HIP_PROVE_CHECK_TRACE) {
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        if (cx->device != pr.device())
+            return fail(ERR_BAD_ARG, "fib prover: created on device " + std::to_string(pr.device()) + ", current device is " + std::to_string(cx->device));
+        TraceCheck c;
+        if ((rc = fib_check_trace(*cx, pr.stream(), d_trace, 1ull << pr.log_n(), pis, &c))) return rc;
+        if (c.first_bad_row >= 0) {
+            char tail[96];
+            snprintf(tail, sizeof tail, " (rules broken: mask 0x%x; %llu bad rows)", c.mask, (unsigned long long)c.bad_rows);
+            return fail(ERR_BAD_ARG, "constraints had nonzero value on row " + std::to_string(c.first_bad_row) + tail);
+        }
+    }
+    return pr.prove_trace(d_trace, pis, out);
+}
+
 struct p3hip_fib_prover {
     std::unique_ptr<FibProver> plain;         // TwoAdicFriPcs + MerkleTreeMmcs
     std::unique_ptr<FibHidingProver> hiding;  // HidingFriPcs + MerkleTreeHidingMmcs (fib_air.rs:40-65)
@@ -474,6 +526,16 @@ struct p3hip_fib_prover {
         else proof_len = last.size();
         return rc;
     }
+    int prove_trace(const uint32_t* d_trace, const uint32_t* pis, unsigned flags) {
+        int rc = hiding ? prove_trace_with(*hiding, d_trace, pis, flags, &last) : prove_trace_with(*plain, d_trace, pis, flags, &last);
+        if (rc) last.clear();
+        else proof_len = last.size();
+        return rc;
+    }
+    int device() const { return hiding ? hiding->device() : plain->device(); }
+    uint32_t log_n() const { return hiding ? hiding->log_n() : plain->log_n(); }
+    hipStream_t stream() const { return hiding ? hiding->stream() : plain->stream(); }
+    uint32_t* arena_trace() const { return hiding ? hiding->arena_trace() : plain->arena_trace(); }
 };
 
 extern "C" {
@@ -581,6 +643,68 @@ int p3hip_fib_prover_finish(p3hip_fib_prover_t* prover, const uint8_t** proof_ou
         *proof_out = prover->last.data();
         *proof_len = prover->last.size();
         return OK;
+    });
+}
+
+int p3hip_fib_check_trace_dev(const uint32_t* d_trace, size_t n, const uint32_t pis[3], p3hip_trace_check_t* out, void* stream) {
+    return guarded([&]() -> int {
+        if (!out || !pis) return fail(ERR_BAD_ARG, "fib_check_trace: null argument");
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        if (!n) { *out = p3hip_trace_check_t{-1, 0, 0}; return OK; }
+        if ((rc = check_device_trace(d_trace, n, cx->device, "fib_check_trace"))) return rc;
+        if ((rc = check_pis_flags(pis, 0, "fib_check_trace"))) return rc;
+        TraceCheck c;
+        if ((rc = fib_check_trace(*cx, (hipStream_t)stream, d_trace, n, pis, &c))) return rc;
+        *out = p3hip_trace_check_t{c.first_bad_row, c.mask, c.bad_rows};
+        return OK;
+    });
+}
+
+int p3hip_fib_prover_prove_trace_dev(p3hip_fib_prover_t* prover, const uint32_t* d_trace, const uint32_t pis[3], unsigned flags,
+                                     const uint8_t** proof_out, size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!prover || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "fib_prover_prove_trace_dev: null argument");
+        int rc = check_pis_flags(pis, flags, "fib_prover_prove_trace_dev");
+        if (rc) return rc;
+        if ((rc = check_device_trace(d_trace, 1ull << prover->log_n(), prover->device(), "fib_prover_prove_trace_dev"))) return rc;
+        if ((rc = prover->prove_trace(d_trace, pis, flags))) return rc;
+        *proof_out = prover->last.data();
+        *proof_len = prover->last.size();
+        return OK;
+    });
+}
+int p3hip_fib_prover_prove_trace(p3hip_fib_prover_t* prover, const uint32_t* host_trace, size_t n, const uint32_t pis[3], unsigned flags,
+                                 const uint8_t** proof_out, size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!prover || !host_trace || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "fib_prover_prove_trace: null argument");
+        int rc = check_pis_flags(pis, flags, "fib_prover_prove_trace");
+        if (rc) return rc;
+        if (n != (1ull << prover->log_n()))
+            return fail(ERR_BAD_ARG, "fib_prover_prove_trace: n = " + std::to_string(n) + " rows, the prover proves 2^" + std::to_string(prover->log_n()));
+        if (prover->plain && prover->plain->has_pending())
+            return fail(ERR_BAD_ARG, "fib prover: finish the enqueued proofs before a synchronous prove");
+        Context* cx;
+        if ((rc = get_context(&cx))) return rc;
+        if (cx->device != prover->device())
+            return fail(ERR_BAD_ARG, "fib prover: created on device " + std::to_string(prover->device()) + ", current device is " + std::to_string(cx->device));
+        // into the arena's trace slot, on the prover's stream: ordered before everything of the proof that reads it
+        P3_HIP(hipMemcpyAsync(prover->arena_trace(), host_trace, (size_t)n * 8, hipMemcpyHostToDevice, prover->stream()));
+        if ((rc = prover->prove_trace(prover->arena_trace(), pis, flags))) return rc;
+        *proof_out = prover->last.data();
+        *proof_len = prover->last.size();
+        return OK;
+    });
+}
+int p3hip_fib_prover_enqueue_trace_dev(p3hip_fib_prover_t* prover, const uint32_t* d_trace, const uint32_t pis[3]) {
+    return guarded([&]() -> int {
+        if (!prover) return fail(ERR_BAD_ARG, "fib_prover_enqueue_trace_dev: null argument");
+        if (!prover->plain) return fail(ERR_BAD_ARG, "fib_prover_enqueue_trace_dev: the hiding prover proves one proof at a time");
+        int rc = check_pis_flags(pis, 0, "fib_prover_enqueue_trace_dev");
+        if (rc) return rc;
+        if ((rc = check_device_trace(d_trace, 1ull << prover->log_n(), prover->device(), "fib_prover_enqueue_trace_dev"))) return rc;
+        return prover->plain->enqueue_trace(d_trace, pis);
     });
 }
 
@@ -732,7 +856,10 @@ struct p3hip_fib_batch {
     // prover that has finished its share of one batch starts on the next at once (no join between batches).
     struct Job {
         uint64_t ticket = 0;
-        std::vector<uint64_t> a, b;
+        std::vector<uint64_t> a, b;           // instances (a[i], b[i]); a.size() is the batch's size
+        std::vector<const uint32_t*> traces;  // or callers' device traces (prove_traces): then a, b are unused zeros
+        std::vector<uint32_t> pis;            // 3 per trace
+        unsigned flags = 0;
         size_t next = 0, done = 0;
         std::vector<std::vector<uint8_t>> proofs;
         int first_error = 0;
@@ -801,7 +928,10 @@ struct p3hip_fib_batch {
             int prc = rc;
             std::string text = start_text;
             if (prc == OK) {
-                prc = no_throw([&]() -> int { return prover.prove(job->a[i], job->b[i], &job->proofs[i]); });
+                prc = no_throw([&]() -> int {
+                    if (!job->traces.empty()) return prove_trace_with(prover, job->traces[i], &job->pis[3 * i], job->flags, &job->proofs[i]);
+                    return prover.prove(job->a[i], job->b[i], &job->proofs[i]);
+                });
                 if (prc != OK) take_error(&text);
             }
             {
@@ -857,6 +987,7 @@ static int fib_batch_create(int hash, unsigned log_n, const p3hip_fri_params_t* 
     });
 }
 
+static int fib_batch_submit_job(p3hip_fib_batch_t* bt, std::shared_ptr<p3hip_fib_batch::Job> job, uint64_t* ticket_out);
 int p3hip_fib_batch_submit(p3hip_fib_batch_t* bt, size_t n, const uint64_t* a, const uint64_t* b, uint64_t* ticket_out) {
     return guarded([&]() -> int {
         if (!bt || !ticket_out || (n && (!a || !b))) return fail(ERR_BAD_ARG, "fib_batch_submit: null argument");
@@ -864,15 +995,18 @@ int p3hip_fib_batch_submit(p3hip_fib_batch_t* bt, size_t n, const uint64_t* a, c
         job->a.assign(a, a + n);
         job->b.assign(b, b + n);
         job->proofs.resize(n);
-        std::unique_lock<std::mutex> lk(bt->mu);
-        if (bt->jobs.size() >= p3hip_fib_batch::MAX_INFLIGHT)
-            return fail(ERR_BAD_ARG, "fib_batch_submit: too many batches in flight (collect one first)");
-        job->ticket = bt->next_ticket++;
-        *ticket_out = job->ticket;
-        bt->jobs.push_back(job);
-        bt->cv_work.notify_all();
-        return OK;
+        return fib_batch_submit_job(bt, job, ticket_out);
     });
+}
+static int fib_batch_submit_job(p3hip_fib_batch_t* bt, std::shared_ptr<p3hip_fib_batch::Job> job, uint64_t* ticket_out) {
+    std::unique_lock<std::mutex> lk(bt->mu);
+    if (bt->jobs.size() >= p3hip_fib_batch::MAX_INFLIGHT)
+        return fail(ERR_BAD_ARG, "fib_batch_submit: too many batches in flight (collect one first)");
+    job->ticket = bt->next_ticket++;
+    *ticket_out = job->ticket;
+    bt->jobs.push_back(job);
+    bt->cv_work.notify_all();
+    return OK;
 }
 
 int p3hip_fib_batch_collect(p3hip_fib_batch_t* bt, uint64_t ticket, const uint8_t** proofs_out, size_t* lens_out) {
@@ -903,6 +1037,33 @@ int p3hip_fib_batch_prove(p3hip_fib_batch_t* bt, size_t n, const uint64_t* a, co
     int rc = p3hip_fib_batch_submit(bt, n, a, b, &ticket);
     if (rc) return rc;
     return p3hip_fib_batch_collect(bt, ticket, proofs_out, lens_out);
+}
+
+int p3hip_fib_batch_prove_traces_dev(p3hip_fib_batch_t* bt, size_t n, const uint32_t* const* d_traces, const uint32_t* pis, unsigned flags,
+                                     const uint8_t** proofs_out, size_t* lens_out) {
+    if (!bt || (n && (!d_traces || !pis || !proofs_out || !lens_out))) return fail(ERR_BAD_ARG, "fib_batch_prove_traces_dev: null argument");
+    if (!n) return OK;
+    int rc = guarded([&]() -> int {
+        // every trace and every public value is checked before any prover is given work
+        auto job = std::make_shared<p3hip_fib_batch::Job>();
+        for (size_t i = 0; i < n; i++) {
+            const std::string who = "fib_batch_prove_traces_dev: instance " + std::to_string(i);
+            int r = check_pis_flags(pis + 3 * i, flags, who);
+            if (r) return r;
+            if ((r = check_device_trace(d_traces[i], 1ull << bt->log_n, bt->device, who))) return r;
+        }
+        job->a.assign(n, 0);
+        job->b.assign(n, 0);
+        job->traces.assign(d_traces, d_traces + n);
+        job->pis.assign(pis, pis + 3 * n);
+        job->flags = flags;
+        job->proofs.resize(n);
+        uint64_t ticket = 0;
+        int r = fib_batch_submit_job(bt, job, &ticket);
+        if (r) return r;
+        return p3hip_fib_batch_collect(bt, ticket, proofs_out, lens_out);
+    });
+    return rc;
 }
 
 void p3hip_fib_batch_destroy(p3hip_fib_batch_t* bt) {

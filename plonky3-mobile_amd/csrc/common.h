@@ -131,6 +131,18 @@ int bit_reverse_rows(hipStream_t stream, const uint32_t* src, uint32_t* dst, uin
 
 // ---- fib_air.hip ----
 int fib_trace(hipStream_t stream, uint64_t a, uint64_t b, uint64_t n, uint32_t* d_out);
+// check_constraints of FibonacciAir over a device trace of n rows x 2 Montgomery words against public values pis (Montgomery
+// words): the rules a row breaks, as bits (include/p3hip.h p3hip_trace_check_t).  Synchronises `stream`.
+enum : uint32_t {
+    TRACE_BAD_FIRST_LEFT = 1, TRACE_BAD_FIRST_RIGHT = 2, TRACE_BAD_NEXT_LEFT = 4, TRACE_BAD_NEXT_RIGHT = 8, TRACE_BAD_LAST_RIGHT = 16,
+    TRACE_BAD_RANGE = 32,
+};
+struct TraceCheck {
+    int64_t first_bad_row;  // -1: every row holds
+    uint32_t mask;          // rules first_bad_row breaks
+    uint64_t bad_rows;
+};
+int fib_check_trace(Context& cx, hipStream_t stream, const uint32_t* d_trace, uint64_t n, const uint32_t pis[3], TraceCheck* out);
 
 inline bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
 inline uint32_t log2u(uint64_t v) {

@@ -37,6 +37,16 @@ class FibProver {
     // behind the first on the prover's stream); finish waits for the oldest one and serialises it
     int enqueue(uint64_t a, uint64_t b);
     int finish(std::vector<uint8_t>* proof);
+    // the same for a CALLER's trace: d_trace = 2^log_n rows x 2 Montgomery words in device memory of the prover's device, read in
+    // place (no copy, no generation) and left unchanged by the caller until the proof is returned; pis = the public values
+    // (Montgomery words) the transcript observes and the quotient uses, whether or not the trace satisfies them
+    int prove_trace(const uint32_t* d_trace, const uint32_t pis[3], std::vector<uint8_t>* proof);
+    int enqueue_trace(const uint32_t* d_trace, const uint32_t pis[3]);
+    uint32_t* arena_trace() const;  // the arena's trace slot (2^log_n x 2 words): what a host trace is uploaded into
+    bool has_pending() const;       // proofs enqueued and not finished
+    hipStream_t stream() const;
+    uint32_t log_n() const;
+    int device() const;
     const StageTimes& times() const;
     void reset_times();
     // proofs so far whose first proof-of-work range held no witness; last_indices = the device's query-index buffer right
@@ -47,6 +57,7 @@ class FibProver {
     struct Impl;
     Impl* im;
     int run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint8_t>* proof, void* pending_rec);
+    int enqueue_any(uint64_t a, uint64_t b, const uint32_t* d_trace, const uint32_t* pis);
 };
 
 // The same prover for the HIDING half of the reference's configuration (native/src/fib_air.rs:40-65:
@@ -58,10 +69,17 @@ class FibHidingProver {
     FibHidingProver(const FibHidingProver&) = delete;
     int init(uint32_t log_n, const FriParams& fp, hipStream_t stream, bool own_stream, int hash, uint64_t seed, int profile = PROFILE_LATENCY);
     int prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof);
+    // a caller's trace and public values, as FibProver::prove_trace (the randomization reads the trace in place)
+    int prove_trace(const uint32_t* d_trace, const uint32_t pis[3], std::vector<uint8_t>* proof);
+    uint32_t* arena_trace() const;
+    hipStream_t stream() const;
+    uint32_t log_n() const;
+    int device() const;
 
   private:
     struct Impl;
     Impl* im;
+    int prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, const uint32_t* pis, std::vector<uint8_t>* proof);
 };
 
 // verifier.hip: p3_uni_stark::verify for FibonacciAir on the host (0 = accept, else the failed check's code)

@@ -368,14 +368,24 @@ struct TsArgs {
     int kind;
     StageLayout lay;
 };
+// the public values of a caller's trace (prove_trace), passed by value; given == 0: read them from the trace, as prove(a, b) does
+struct TsPis {
+    uint32_t w[3];
+    uint32_t given;
+};
 
 // observe the instance, sample alpha: p3_uni_stark::prove up to the quotient computation
-__global__ void __launch_bounds__(64) ts_begin_kernel(TsArgs a, const uint32_t* trace, uint32_t n, uint32_t log_n) {
+__global__ void __launch_bounds__(64) ts_begin_kernel(TsArgs a, const uint32_t* trace, uint32_t n, uint32_t log_n, TsPis given) {
     P3_LATENCY_BOUND_KERNEL();
     __shared__ KState ks;
     DevChal ch;
     ch.begin(a.kind, a.ds, &ks, true);
-    const uint32_t pis[3] = {trace[0], trace[1], trace[2 * (size_t)(n - 1) + 1]};  // first row and last right value
+    uint32_t pis[3];
+    if (given.given) {
+        for (int k = 0; k < 3; k++) pis[k] = given.w[k];
+    } else {  // first row and last right value
+        pis[0] = trace[0]; pis[1] = trace[1]; pis[2] = trace[2 * (size_t)(n - 1) + 1];
+    }
     ch.observe(bb::to_monty(log_n));  // log_ext_degree
     ch.observe(bb::to_monty(log_n));  // log_degree
     ch.observe_n(a.ps + a.lay.root_t, 8);
@@ -664,7 +674,11 @@ struct FibProver::Impl {
     // proof may be enqueued behind the first on the same stream before the first is collected (enqueue / finish)
     uint32_t* host_stage[2] = {nullptr, nullptr};
     hipEvent_t done[2] = {nullptr, nullptr};
-    struct Pending { uint64_t a, b; int slot; std::chrono::steady_clock::time_point t_start, t_enq; uint64_t seq; };
+    struct Pending {
+        uint64_t a, b; int slot; std::chrono::steady_clock::time_point t_start, t_enq; uint64_t seq;
+        const uint32_t* trace;  // a caller's trace (prove_trace), nullptr: generate (a, b)'s into the arena
+        TsPis pis;
+    };
     std::deque<Pending> pending;
     uint64_t next_seq = 1, arena_owner = 0;  // arena_owner: the proof whose launch sequence ran last (its state is in the arena)
     StageLayout lay;
@@ -819,11 +833,28 @@ int FibProver::prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof) {
 // At most two proofs may be in flight (the second one's kernels simply queue behind the first on the prover's stream: the
 // arena is reused in stream order, the two results land in different pinned buffers).  finish: waits for the OLDEST one,
 // continues an empty proof-of-work search if need be, serialises.
-int FibProver::enqueue(uint64_t a, uint64_t b) {
+int FibProver::enqueue(uint64_t a, uint64_t b) { return enqueue_any(a, b, nullptr, nullptr); }
+int FibProver::enqueue_trace(const uint32_t* d_trace, const uint32_t pis[3]) {
+    if (!d_trace || !pis) return fail(ERR_BAD_ARG, "fib prover: null trace or public values");
+    return enqueue_any(0, 0, d_trace, pis);
+}
+int FibProver::prove_trace(const uint32_t* d_trace, const uint32_t pis[3], std::vector<uint8_t>* proof) {
+    if (!im->pending.empty()) return fail(ERR_BAD_ARG, "fib prover: finish the enqueued proofs before a synchronous prove");
+    int rc = enqueue_trace(d_trace, pis);
+    if (rc) return rc;
+    return finish(proof);
+}
+uint32_t* FibProver::arena_trace() const { return im->trace; }
+bool FibProver::has_pending() const { return !im->pending.empty(); }
+hipStream_t FibProver::stream() const { return im->stream; }
+uint32_t FibProver::log_n() const { return im->log_n; }
+int FibProver::device() const { return im->device; }
+int FibProver::enqueue_any(uint64_t a, uint64_t b, const uint32_t* d_trace, const uint32_t* pis) {
     Impl& s = *im;
     if (s.pending.size() >= 2) return fail(ERR_BAD_ARG, "fib prover: two proofs already in flight (finish one first)");
     const int slot = s.pending.empty() ? 0 : 1 - s.pending.back().slot;
-    Impl::Pending p{a, b, slot, std::chrono::steady_clock::now(), {}, s.next_seq++};
+    Impl::Pending p{a, b, slot, std::chrono::steady_clock::now(), {}, s.next_seq++, d_trace, TsPis{{0, 0, 0}, 0}};
+    if (pis) p.pis = TsPis{{pis[0], pis[1], pis[2]}, 1};
     int rc = run(a, b, slot, 0, nullptr, &p);
     if (rc) return rc;
     s.pending.push_back(p);
@@ -897,10 +928,12 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
         P3_HIP(hipEventRecord(ev[0], st));
 
         // ---- trace + commit (pcs.commit: bit-reversed coset LDE, shift GENERATOR) ----
-        if ((rc = fib_trace(st, a, b, n, s.trace))) return rc;
-        if ((rc = ntt_coset_lde(cx, st, s.trace, s.lde_t, n, 2, s.fp.log_blowup, gen, true))) return rc;
+        // a caller's trace is read where it lies (prove_trace); otherwise (a, b)'s trace is generated into the arena
+        const uint32_t* trace = pend.trace ? pend.trace : s.trace;
+        if (!pend.trace && (rc = fib_trace(st, a, b, n, s.trace))) return rc;
+        if ((rc = ntt_coset_lde(cx, st, trace, s.lde_t, n, 2, s.fp.log_blowup, gen, true))) return rc;
         if ((rc = commit(s.lde_t, big, 2, s.layers_t, L.root_t))) return rc;
-        hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, st, ts, s.trace, n, log_n);
+        hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, st, ts, trace, n, log_n, pend.pis);
         P3_HIP(hipGetLastError());
         P3_HIP(hipEventRecord(ev[1], st));
 

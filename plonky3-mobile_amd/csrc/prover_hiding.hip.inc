@@ -300,12 +300,17 @@ struct StageLayoutH {  // extends StageLayout: three roots, 36 opened values
     StageLayout s;
     uint32_t root_r;
 };
-__global__ void __launch_bounds__(64) ts_begin_h_kernel(TsArgs a, const uint32_t* trace, uint32_t h, uint32_t log_n) {
+__global__ void __launch_bounds__(64) ts_begin_h_kernel(TsArgs a, const uint32_t* trace, uint32_t h, uint32_t log_n, TsPis given) {
     P3_LATENCY_BOUND_KERNEL();
     __shared__ KState ks;
     DevChal ch;
     ch.begin(a.kind, a.ds, &ks, true);
-    const uint32_t pis[3] = {trace[0], trace[1], trace[2 * (size_t)(h - 1) + 1]};
+    uint32_t pis[3];
+    if (given.given) {
+        for (int k = 0; k < 3; k++) pis[k] = given.w[k];
+    } else {
+        pis[0] = trace[0]; pis[1] = trace[1]; pis[2] = trace[2 * (size_t)(h - 1) + 1];
+    }
     ch.observe(bb::to_monty(log_n + 1));  // log_ext_degree = log_degree + is_zk
     ch.observe(bb::to_monty(log_n));      // log_degree
     ch.observe_n(a.ps + a.lay.root_t, 8);
@@ -613,8 +618,19 @@ int FibHidingProver::init(uint32_t log_n, const FriParams& fp, hipStream_t strea
     return OK;
 }
 
-int FibHidingProver::prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof) {
+int FibHidingProver::prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof) { return prove_any(a, b, nullptr, nullptr, proof); }
+int FibHidingProver::prove_trace(const uint32_t* d_trace, const uint32_t pis[3], std::vector<uint8_t>* proof) {
+    if (!d_trace || !pis) return fail(ERR_BAD_ARG, "hiding prover: null trace or public values");
+    return prove_any(0, 0, d_trace, pis, proof);
+}
+uint32_t* FibHidingProver::arena_trace() const { return im->trace; }
+hipStream_t FibHidingProver::stream() const { return im->stream; }
+uint32_t FibHidingProver::log_n() const { return im->log_n; }
+int FibHidingProver::device() const { return im->device; }
+// d_trace == nullptr: (a, b)'s trace is generated (in the arena, or inside the one-launch kernel) and the public values are read from it
+int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, const uint32_t* pis, std::vector<uint8_t>* proof) {
     Impl& s = *im;
+    const TsPis given = pis ? TsPis{{pis[0], pis[1], pis[2]}, 1} : TsPis{{0, 0, 0}, 0};
     Context* cxp;
     int rc = get_context(&cxp);
     if (rc) return rc;
@@ -656,7 +672,7 @@ int FibHidingProver::prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof) 
             ta.ch_fri = s.fri_salt_words ? rng_small_chunks(s.fri_salt_words) : 0;
         }
         ta.pcs_draws = s.pcs_draws; ta.mmcs_draws = s.mmcs_draws; ta.fri_salts = s.fri_salts;
-        ta.trace = s.trace; ta.rt = s.rt; ta.lde_t = s.lde_t; ta.salt_t = s.salt_t; ta.layers_t = s.layers_t;
+        ta.trace = s.trace; ta.in_trace = d_trace; ta.pis = given; ta.rt = s.rt; ta.lde_t = s.lde_t; ta.salt_t = s.salt_t; ta.layers_t = s.layers_t;
         ta.qchunks = s.qchunks; ta.co = s.co; ta.ext = s.ext; ta.lde_qb = s.lde_qb; ta.layers_q = s.layers_q; ta.t012 = s.t012;
         for (uint32_t c = 0; c < HCH; c++) ta.salt_q[c] = s.salt_q[c];
         ta.rm = s.rm; ta.lde_r = s.lde_r; ta.salt_r = s.salt_r; ta.layers_r = s.layers_r;
@@ -730,17 +746,18 @@ int FibHidingProver::prove(uint64_t a, uint64_t b, std::vector<uint8_t>* proof) 
         }
 
         // ---- randomized trace + commit ----
-        if ((rc = fib_trace(st, a, b, h, s.trace))) return rc;
+        const uint32_t* trace = d_trace ? d_trace : s.trace;  // a caller's trace is randomized where it lies
+        if (!d_trace && (rc = fib_trace(st, a, b, h, s.trace))) return rc;
         if ((rc = fill(rng_pcs, s.rnd_t, (uint64_t)h * (HW + 2 * HNRC)))) return rc;
         if ((rc = wait_fill(s.ev_pcs))) return rc;
-        hipLaunchKernelGGL(randomize_trace_kernel, dim3((h + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint2*>(s.trace), s.rnd_t, h, s.rt);
+        hipLaunchKernelGGL(randomize_trace_kernel, dim3((h + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint2*>(trace), s.rnd_t, h, s.rt);
         P3_HIP(hipGetLastError());
         if ((rc = ntt_coset_lde(cx, st, s.rt, s.lde_t, h2, HTW, s.fp.log_blowup, gen, true))) return rc;
         if ((rc = fill(rng_mmcs, s.salt_t, (uint64_t)big * HSALT))) return rc;
         if ((rc = wait_fill(s.ev_mmcs))) return rc;
         { const uint32_t* m[1] = {s.lde_t}; size_t w[1] = {HTW}; uint32_t* sl[1] = {s.salt_t};
           if ((rc = commit(m, w, sl, 1, big, s.layers_t, L.root_t))) return rc; }
-        hipLaunchKernelGGL(ts_begin_h_kernel, dim3(1), dim3(64), 0, st, ts, s.trace, h, log_n);
+        hipLaunchKernelGGL(ts_begin_h_kernel, dim3(1), dim3(64), 0, st, ts, trace, h, log_n, given);
         P3_HIP(hipGetLastError());
 
         // ---- quotient on GENERATOR <g_4h>, four blinded chunks, commit ----

@@ -33,6 +33,8 @@ struct TinyArgs {
     uint32_t chunk_log;               // 6: chunks of 64 raw draws (jump = T^64), every stream within 64 of them; 8: chunks of 256 (jump = T^256)
     uint32_t *pcs_draws, *mmcs_draws, *fri_salts;            // pcs: rnd_t | t012 | rm;  mmcs: salt_t | salt_q[0..4) | salt_r
     uint32_t *trace, *rt, *lde_t, *salt_t, *layers_t;
+    const uint32_t* in_trace;         // a caller's trace (prove_trace), read in place; nullptr: generate (a, b)'s into `trace`
+    TsPis pis;                        // the caller's public values (given != 0), else read from the trace
     uint32_t *qchunks, *co, *ext, *lde_qb, *salt_q[HCH], *layers_q, *t012;
     uint32_t *rm, *lde_r, *salt_r, *layers_r;
     uint32_t *d0, *d1, *fri_vec, *fri_layers, *fp_ev;
@@ -220,7 +222,7 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_hiding_prover_kernel(TinyAr
     uint32_t* winv2 = xs + big;
     uint32_t* winvh = winv2 + h2;
     uint32_t* spw = winvh + h;  // 4 x h
-    if (tid == 3 * 64) {
+    if (tid == 3 * 64 && !a.in_trace) {
         uint32_t l = a.a_monty, r = a.b_monty;
         for (uint32_t i = 0; i < h; i++) {
             a.trace[2 * i] = l; a.trace[2 * i + 1] = r;
@@ -241,10 +243,11 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_hiding_prover_kernel(TinyAr
     __syncthreads();
     TINY_STAMP("rng+tables");
     // randomized trace: per trace row w + 2 NRC draws; the row keeps its values + the first NRC draws, the next row is the rest
+    const uint32_t* tr = a.in_trace ? a.in_trace : a.trace;
     for (uint32_t i = tid; i < h; i += TINY_THREADS) {
         const uint32_t* d = a.pcs_draws + (size_t)i * (HW + 2 * HNRC);
         uint32_t* even = a.rt + (size_t)(2 * i) * HTW;
-        even[0] = a.trace[2 * i]; even[1] = a.trace[2 * i + 1];
+        even[0] = tr[2 * i]; even[1] = tr[2 * i + 1];
         for (uint32_t k = 0; k < HNRC; k++) even[HW + k] = d[k];
         for (uint32_t k = 0; k < HTW; k++) even[HTW + k] = d[HNRC + k];
     }
@@ -281,7 +284,8 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_hiding_prover_kernel(TinyAr
     TINY_STAMP("trees t,r");
     // ---- transcript: instance -> alpha (ts_begin_h_kernel) ----
     DevChal ch;
-    uint32_t pis[3] = {a.trace[0], a.trace[1], a.trace[2 * (size_t)(h - 1) + 1]};
+    uint32_t pis[3] = {tr[0], tr[1], tr[2 * (size_t)(h - 1) + 1]};
+    if (a.pis.given) { pis[0] = a.pis.w[0]; pis[1] = a.pis.w[1]; pis[2] = a.pis.w[2]; }
     if (tid < 64) {
         ch.begin(kind, ds, &ks, true);
         ch.observe(bb::to_monty(log_n + 1));  // log_ext_degree = log_degree + is_zk

@@ -7,6 +7,10 @@ from .gpu_dft import _stream_ptr
 NUM_FIBONACCI_COLS = 2  # fib_air.rs:25
 
 
+def _is_numpy(x):
+    return type(x).__module__ == "numpy"
+
+
 def generate_trace_rows(a, b, n, device="cuda"):
     """fib_air.rs:266-284 on the device: returns an (n, 2) int32 device tensor (torch device "cuda" = HIP on ROCm) of Montgomery words."""
     import torch
@@ -15,6 +19,52 @@ def generate_trace_rows(a, b, n, device="cuda"):
     out = torch.empty((n, NUM_FIBONACCI_COLS), dtype=torch.int32, device=device)
     _lib.check(_lib.lib().p3hip_fib_trace_dev(a, b, n, C.c_void_p(out.data_ptr()), _stream_ptr()))
     return out
+
+
+PROVE_CHECK_TRACE = 1  # include/p3hip.h P3HIP_PROVE_CHECK_TRACE
+_P = 0x78000001
+
+
+class TraceCheck(C.Structure):  # include/p3hip.h p3hip_trace_check_t
+    _fields_ = [("first_bad_row", C.c_int64), ("mask", C.c_uint32), ("bad_rows", C.c_uint64)]
+
+
+def _monty_pis(pis):
+    """Public values as canonical ints (reduced mod P, as prove(a, b) reduces a and b) -> three Montgomery words."""
+    pis = [int(v) for v in pis]
+    if len(pis) != 3:
+        raise ValueError("FibonacciAir has three public values")
+    return (C.c_uint32 * 3)(*[((v % _P) << 32) % _P for v in pis])
+
+
+def _device_trace(trace, rows=None):
+    """An (n, 2) torch device tensor of 32-bit Montgomery words, contiguous; returns its data pointer."""
+    import torch
+    if not isinstance(trace, torch.Tensor) or not trace.is_cuda:
+        raise TypeError("expected a torch device tensor")
+    if trace.dtype not in (torch.int32, torch.uint32) or trace.dim() != 2 or trace.shape[1] != NUM_FIBONACCI_COLS:
+        raise ValueError("expected an (n, 2) tensor of 32-bit Montgomery words")
+    if not trace.is_contiguous():
+        raise ValueError("the trace must be contiguous")
+    if rows is not None and trace.shape[0] != rows:
+        raise ValueError("the trace has %d rows, the prover proves %d" % (trace.shape[0], rows))
+    return trace.data_ptr()
+
+
+def _sync_current_stream():
+    """The trace entries read the tensor on the prover's stream: whatever torch queued to write it must be complete."""
+    import torch
+    torch.cuda.current_stream().synchronize()
+
+
+def check_fib_trace(trace, pis):
+    """check_constraints of FibonacciAir (upstream's debug-build check before proving) over an (n, 2) device tensor of Montgomery
+    words against public values `pis` (canonical ints).  Returns (first_bad_row or None, mask of its broken rules, bad row count);
+    mask bits: include/p3hip.h P3HIP_TRACE_BAD_*."""
+    ptr = _device_trace(trace)
+    out = TraceCheck()
+    _lib.check(_lib.lib().p3hip_fib_check_trace_dev(C.c_void_p(ptr), trace.shape[0], _monty_pis(pis), C.byref(out), _stream_ptr()))
+    return (None if out.first_bad_row < 0 else int(out.first_bad_row)), int(out.mask), int(out.bad_rows)
 
 
 class FriParameters:
@@ -104,6 +154,33 @@ class FibAirProver:
         n = C.c_size_t()
         _lib.check(_lib.lib().p3hip_fib_prover_finish(self._h, C.byref(out), C.byref(n)))
         return C.string_at(out, n.value)
+
+    def prove_trace(self, trace, pis, check=False):
+        """prove(&config, &FibonacciAir{}, trace, &pis) for a caller's trace: an (n, 2) torch device tensor of Montgomery words (what
+        generate_trace_rows returns; read in place, after the current torch stream is synchronised) or a numpy array of Montgomery
+        words (uploaded).  pis: three canonical ints.  check=True runs check_constraints first and raises P3HipError naming the
+        first bad row instead of proving.  Without it any trace and pis are proven, and the verifiers reject what does not hold."""
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        flags = PROVE_CHECK_TRACE if check else 0
+        if _is_numpy(trace):
+            import numpy as np
+            host = np.ascontiguousarray(trace, dtype=np.uint32)
+            if host.ndim != 2 or host.shape[1] != NUM_FIBONACCI_COLS:
+                raise ValueError("expected an (n, 2) array of Montgomery words")
+            _lib.check(_lib.lib().p3hip_fib_prover_prove_trace(self._h, C.c_void_p(host.ctypes.data), host.shape[0], _monty_pis(pis), flags,
+                                                               C.byref(out), C.byref(n)))
+        else:
+            ptr = _device_trace(trace, 1 << self.log_n)
+            _sync_current_stream()
+            _lib.check(_lib.lib().p3hip_fib_prover_prove_trace_dev(self._h, C.c_void_p(ptr), _monty_pis(pis), flags, C.byref(out), C.byref(n)))
+        return C.string_at(out, n.value)
+
+    def enqueue_trace(self, trace, pis):
+        """enqueue() for a device trace (non-hiding): keep `trace` alive and unchanged until finish() has returned its proof."""
+        ptr = _device_trace(trace, 1 << self.log_n)
+        _sync_current_stream()
+        _lib.check(_lib.lib().p3hip_fib_prover_enqueue_trace_dev(self._h, C.c_void_p(ptr), _monty_pis(pis)))
 
     @staticmethod
     def proof_bytes(proof):
@@ -360,6 +437,24 @@ class FibAirBatchProver:
         ptrs = (C.POINTER(C.c_uint8) * n)()
         lens = (C.c_size_t * n)()
         _lib.check(_lib.lib().p3hip_fib_batch_prove(self._h, n, a, b, ptrs, lens))
+        return [C.string_at(ptrs[i], lens[i]) for i in range(n)]
+
+    def prove_traces(self, traces, pis, check=False):
+        """prove_trace for a list of (n, 2) device tensors with their public values (lists of three canonical ints); the proofs in
+        the same order."""
+        n = len(traces)
+        if len(pis) != n:
+            raise ValueError("one set of public values per trace")
+        if n == 0:
+            return []
+        ptrs_in = (C.c_void_p * n)(*[_device_trace(t) for t in traces])
+        words = (C.c_uint32 * (3 * n))()
+        for i, p in enumerate(pis):
+            words[3 * i:3 * i + 3] = list(_monty_pis(p))
+        _sync_current_stream()
+        ptrs = (C.POINTER(C.c_uint8) * n)()
+        lens = (C.c_size_t * n)()
+        _lib.check(_lib.lib().p3hip_fib_batch_prove_traces_dev(self._h, n, ptrs_in, words, PROVE_CHECK_TRACE if check else 0, ptrs, lens))
         return [C.string_at(ptrs[i], lens[i]) for i in range(n)]
 
     def submit(self, instances):
