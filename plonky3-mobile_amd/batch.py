@@ -90,13 +90,19 @@ class _Null:
 
 class PendingDescriptors:
     """The descriptors of several steps, scattered in one collective; step(k) gives this rank's shard of step k as a list of
-    (index, a, b).  The first call waits for the one event behind the pinned copy."""
+    (index, a, b).  The first call waits for the one event behind the pinned copy.  A result of DescriptorScatter.run that was
+    not read before the next run() of the same scatterer is superseded: its buffers now hold the next run's descriptors, and
+    its first step() raises instead of returning them.  A result read at least once stays valid."""
 
-    def __init__(self, landing, steps, per):
+    def __init__(self, landing, steps, per, owner=None, run=0):
         self._landing, self._steps, self._per, self._rows = landing, steps, per, None
+        self._owner, self._run = owner, run
 
     def step(self, k):
         if self._rows is None:
+            if self._owner is not None and self._owner.runs != self._run:
+                raise RuntimeError("PendingDescriptors: run %d of this DescriptorScatter was superseded by run %d before it was "
+                                   "read (they share one landing buffer)" % (self._run, self._owner.runs))
             self._rows = self._landing.tolist()
             self._landing = None
         rows = self._rows[k * self._per:(k + 1) * self._per]
@@ -129,6 +135,7 @@ class DescriptorScatter:
                 self.table = self.table.pin_memory()
                 self.table_dev = torch.empty((self.world, rows, 3), dtype=torch.int64, device=device)
         self.last_ms = {}
+        self.runs = 0  # run() calls so far: a PendingDescriptors of an earlier run that was never read is superseded
 
     def run(self, steps):
         """steps (rank 0; ignored elsewhere): one list of instances (a, b) per step, at most max_steps of at most n.  Returns
@@ -148,10 +155,11 @@ class DescriptorScatter:
                     tab[r, k * self.per:k * self.per + len(idx), 0] = idx
                     tab[r, k * self.per:k * self.per + len(idx), 1:] = arr[idx]
         t1 = time.perf_counter()
+        self.runs += 1
         if self.stream is None:
             dist.scatter(self.recv_host, [self.table[r] for r in range(self.world)] if self.rank == 0 else None, src=0)
             self.last_ms = {"fill": 1e3 * (t1 - t0), "issue": 1e3 * (time.perf_counter() - t1)}
-            return PendingDescriptors(self.recv_host, self.max_steps, self.per)
+            return PendingDescriptors(self.recv_host, self.max_steps, self.per, self, self.runs)
         with torch.cuda.stream(self.stream):
             if self.rank == 0:
                 self.table_dev.copy_(self.table, non_blocking=True)
@@ -161,7 +169,7 @@ class DescriptorScatter:
             self.recv_host.copy_(self.recv_dev, non_blocking=True)
             self.event.record(self.stream)
         self.last_ms = {"fill": 1e3 * (t1 - t0), "issue": 1e3 * (time.perf_counter() - t1)}
-        return PendingDescriptors(_Landed(self.recv_host, self.event), self.max_steps, self.per)
+        return PendingDescriptors(_Landed(self.recv_host, self.event), self.max_steps, self.per, self, self.runs)
 
 
 class _Landed:

@@ -237,6 +237,47 @@ def test_one_scatter_for_a_whole_run_world2():
         assert (bad is not None and "announced" in bad) if rank == 0 else bad is None
 
 
+def _worker_superseded(rank, world, port, q):
+    import torch.distributed as dist
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import load_package
+    load_package()
+    from plonky3_mobile_amd import batch
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    # two runs of one DescriptorScatter before the first result is read: both land in the same receive buffer
+    sc = batch.DescriptorScatter(1, 4, "cpu")
+    p1 = sc.run([[(1, 2), (3, 4), (5, 6), (7, 8)]] if rank == 0 else [])
+    p2 = sc.run([[(11, 12), (13, 14)]] if rank == 0 else [])
+    try:
+        late = p1.step(0)
+    except RuntimeError as e:
+        late = "refused: " + str(e)
+    q.put((rank, late, p2.step(0)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_superseded_descriptor_run_is_refused_world2():
+    """A DescriptorScatter result read after the next run() of the same scatterer would hand out that run's descriptors: it raises."""
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_worker_superseded, args=(r, 2, port, q)) for r in range(2)]
+    [p.start() for p in procs]
+    res = sorted(q.get(timeout=120) for _ in range(2))
+    [p.join(60) for p in procs]
+    assert all(p.exitcode == 0 for p in procs)
+    for rank, late, second in res:
+        assert isinstance(late, str) and late.startswith("refused") and "superseded" in late, (rank, late)
+        assert second == [(i, a, b) for i, (a, b) in enumerate([(11, 12), (13, 14)]) if i % 2 == rank], rank
+
+
 def test_shard_instances_partition():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from conftest import load_package
