@@ -330,25 +330,32 @@ __global__ void __launch_bounds__(256) grind_keccak_kernel(DevState* ds, uint32_
     if (ok) atomicMin(&ds->grind_result, w);
 }
 
-// Batched Mmcs::open_batch for the query phase: block (q, t) copies tree t's opened row and sibling path
-// for query q into its fixed slot of the staging buffer.
+// Batched Mmcs::open_batch for the query phase: block (q, tree) copies the opened values of every matrix of the tree, then (hiding
+// MMCS) every salt row, then the sibling path into query q's fixed slot of the staging buffer.  A tree of the plain MMCS is one matrix.
+constexpr uint32_t QTREE_MAX_MATS = 8;  // the hiding quotient commitment: four chunk matrices and their four salts
 struct QTree {
-    const uint32_t* mat;
+    const uint32_t* mat[QTREE_MAX_MATS];
+    uint32_t width[QTREE_MAX_MATS];
+    uint32_t stride[QTREE_MAX_MATS];  // words between two rows
+    uint32_t n_mats;  // values first, then their salts (if any), as listed
     const uint32_t* layers;
-    uint32_t width, log_height, shift, slot_off;  // index used = query_index >> shift; slot_off in words
+    uint32_t log_height, shift, slot_off;  // index used = query_index >> shift; slot_off in words
 };
-__global__ void query_gather_kernel(const QTree* trees, uint32_t n_trees, const uint32_t* indices, uint32_t slot_words,
-                                    uint32_t* out) {
+__global__ void query_gather_kernel(const QTree* trees, const uint32_t* indices, uint32_t slot_words, uint32_t* out) {
     P3_LATENCY_BOUND_KERNEL();
-    const QTree t = trees[blockIdx.y];
+    const QTree& t = trees[blockIdx.y];
     // masked: whatever the index buffer holds, the gather stays inside the tree
-    uint64_t index = (indices[blockIdx.x] >> t.shift) & ((1ull << t.log_height) - 1ull);
+    const uint64_t index = (indices[blockIdx.x] >> t.shift) & ((1ull << t.log_height) - 1ull);
     uint32_t* dst = out + (size_t)blockIdx.x * slot_words + t.slot_off;
-    for (uint32_t c = threadIdx.x; c < t.width; c += blockDim.x) dst[c] = t.mat[index * t.width + c];
+    uint32_t off = 0;
+    for (uint32_t m = 0; m < t.n_mats; m++) {
+        for (uint32_t c = threadIdx.x; c < t.width[m]; c += blockDim.x) dst[off + c] = t.mat[m][index * t.stride[m] + c];
+        off += t.width[m];
+    }
     uint64_t base = 0, len = 1ull << t.log_height;
     for (uint32_t i = 0; i < t.log_height; i++) {
-        uint64_t sib = (index >> i) ^ 1;
-        if (threadIdx.x < 8) dst[t.width + i * 8 + threadIdx.x] = t.layers[base + sib * 8 + threadIdx.x];
+        const uint64_t sib = (index >> i) ^ 1;
+        if (threadIdx.x < 8) dst[off + i * 8 + threadIdx.x] = t.layers[base + sib * 8 + threadIdx.x];
         base += len * 8;
         len >>= 1;
     }
@@ -653,23 +660,264 @@ static void put_words(std::vector<uint8_t>& b, const uint32_t* w, size_t n) {
     b.resize(o + 4 * n);
     memcpy(b.data() + o, w, 4 * n);
 }
+// one BatchOpening of a query slot: n matrices (width, values), one salt per matrix when salt_words > 0, the sibling path
+static void put_opening(std::vector<uint8_t>& pf, const uint32_t*& slot, uint32_t n, const uint32_t* widths, uint32_t salt_words,
+                        uint32_t depth) {
+    put_u32(pf, n);
+    for (uint32_t m = 0; m < n; m++) { put_u32(pf, widths[m]); put_words(pf, slot, widths[m]); slot += widths[m]; }
+    if (salt_words)
+        for (uint32_t m = 0; m < n; m++) { put_u32(pf, salt_words); put_words(pf, slot, salt_words); slot += salt_words; }
+    put_u32(pf, depth); put_words(pf, slot, (size_t)depth * 8); slot += (size_t)depth * 8;
+}
+
+// P3HIP_GRIND_FIRST_LOG (tests): log2 of the whole first proof-of-work range, to exercise the continuation path
+static uint32_t grind_first_log() {
+    const char* e = getenv("P3HIP_GRIND_FIRST_LOG");
+    return e ? (uint32_t)atoi(e) : 0u;
+}
+
+// What FibProver and FibHidingProver (prover_hiding.hip.inc) share: the stream and the arena, and from the FRI commit phase to the
+// end of the proof the launches, the staging layout and the serialisation.  The plain MMCS is the hiding MMCS with no salt: salt_words
+// is 0 or HSALT, and nothing here asks which prover it serves.
+struct ProverCore {
+    int hash = HASH_POSEIDON2, profile = PROFILE_LATENCY;
+    int device = -1;  // the arena's device: a proof refuses to run with another one current
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    FriParams fp{};
+    uint32_t log_big = 0, n_rounds = 0, salt_words = 0;
+    std::vector<void*> allocs;
+    // FRI: vector r has big >> r ext elements; its commitment tree has (big >> (r+1)) leaves, each with a salt when salt_words > 0
+    uint32_t *fri_vec = nullptr, *fri_layers = nullptr, *fri_salts = nullptr, *fp_ev = nullptr;
+    std::vector<size_t> fri_vec_off, fri_layer_off, fri_salt_off;  // word offsets per round
+    size_t fri_vec_words = 0, fri_layer_words = 0, fri_salt_words = 0;
+    // the trees a query opens: the prover's input commitments, then the FRI rounds' (layout() adds those); a query's staging
+    // slot holds their openings in this order
+    std::vector<QTree> trees;
+    QTree* qtrees = nullptr;
+    uint32_t *pstage = nullptr, *qidx = nullptr;
+    StageLayout lay;
+    size_t slot_words = 0;
+
+    ~ProverCore() {
+        for (void* p : allocs) (void)hipFree(p);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+    int alloc(uint32_t** p, size_t words) {
+        P3_HIP(hipMalloc(reinterpret_cast<void**>(p), words * 4 + 64));
+        allocs.push_back(*p);
+        return OK;
+    }
+    static int bad_arg(const char* who, const char* what) { return fail(ERR_BAD_ARG, std::string(who) + ": " + what); }
+
+    // the start of both inits; the stream is recorded first: an owned stream is destroyed with the prover even when init fails
+    int begin(const char* who, hipStream_t st, bool own, int hash_kind, int prof) {
+        stream = st; own_stream = own;
+        if (prof != PROFILE_THROUGHPUT && prof != PROFILE_LATENCY) return bad_arg(who, "unknown profile");
+        if (hash_kind != HASH_POSEIDON2 && hash_kind != HASH_KECCAK) return bad_arg(who, "unknown hash configuration");
+        hash = hash_kind; profile = prof;
+        P3_HIP(hipGetDevice(&device));
+        return OK;
+    }
+    // FRI over the LDE of a committed trace of 2^log_height rows.  p3_fri::prover::prove:
+    // `if log_final_poly_len > 0 { assert!(log_min_height > log_final_poly_len + log_blowup) }`
+    int set_fri(const char* who, const FriParams& p, uint32_t log_height) {
+        if (p.log_final_poly_len >= log_height) return bad_arg(who, "log_final_poly_len must be below the committed trace's log height");
+        if (p.proof_of_work_bits > 30) return bad_arg(who, "proof_of_work_bits too large");
+        fp = p; log_big = log_height + p.log_blowup; n_rounds = log_height - p.log_final_poly_len;
+        if (n_rounds > MAX_FRI_ROUNDS) return bad_arg(who, "too many FRI rounds");
+        return OK;
+    }
+    int alloc_fri() {
+        const size_t big = (size_t)1 << log_big;
+        for (uint32_t r = 0; r <= n_rounds; r++) { fri_vec_off.push_back(fri_vec_words); fri_vec_words += (big >> r) * 4; }
+        for (uint32_t r = 0; r < n_rounds; r++) {
+            fri_layer_off.push_back(fri_layer_words); fri_layer_words += mmcs_layer_words(big >> (r + 1));
+            fri_salt_off.push_back(fri_salt_words); fri_salt_words += (big >> (r + 1)) * salt_words;
+        }
+        int rc;
+        if ((rc = alloc(&fri_vec, fri_vec_words))) return rc;
+        if ((rc = alloc(&fri_layers, fri_layer_words + 8))) return rc;
+        if (salt_words && (rc = alloc(&fri_salts, fri_salt_words + 8))) return rc;
+        return alloc(&fp_ev, ((size_t)4) << fp.log_final_poly_len);
+    }
+    // The staging layout from lay.froots on (the prover's roots and opened values come before): the FRI roots, the final polynomial,
+    // the witness, the status, the query indices and one slot per query (every tree's opening, in `trees` order).  Allocates the
+    // staging buffer with extra_words behind it, the query indices and the trees' device descriptors.
+    int layout(const char* who, uint32_t extra_words) {
+        for (uint32_t r = 0; r < n_rounds; r++) {
+            const uint32_t w = salt_words;
+            trees.push_back(QTree{{fri_vec + fri_vec_off[r], w ? fri_salts + fri_salt_off[r] : nullptr}, {8, w}, {8, w}, w ? 2u : 1u,
+                                  fri_layers + fri_layer_off[r], log_big - 1 - r, r + 1});
+        }
+        slot_words = 0;
+        for (QTree& t : trees) {
+            t.slot_off = (uint32_t)slot_words;
+            for (uint32_t m = 0; m < t.n_mats; m++) slot_words += t.width[m];
+            slot_words += (size_t)t.log_height * 8;
+        }
+        const uint32_t nq = fp.num_queries;
+        StageLayout& L = lay;
+        L.fpoly = L.froots + 8 * n_rounds;
+        L.witness = L.fpoly + (4u << fp.log_final_poly_len);
+        L.status = L.witness + 1;
+        L.qidx = L.status + 1;
+        L.slots = (L.qidx + nq + 3u) & ~3u;
+        const size_t stage_words = (size_t)L.slots + slot_words * nq;
+        if (stage_words > 0xffffffffull) return bad_arg(who, "proof staging buffer too large");
+        L.words = (uint32_t)stage_words;
+        int rc;
+        if ((rc = alloc(&pstage, stage_words + extra_words))) return rc;
+        if ((rc = alloc(&qidx, std::max<uint32_t>(nq, 1)))) return rc;
+        uint32_t* p = nullptr;
+        if ((rc = alloc(&p, (sizeof(QTree) + 3) / 4 * trees.size()))) return rc;
+        qtrees = reinterpret_cast<QTree*>(p);
+        P3_HIP(hipMemcpy(qtrees, trees.data(), trees.size() * sizeof(QTree), hipMemcpyHostToDevice));
+        return OK;
+    }
+
+    // mmcs_commit of n matrices of one height — each followed by its salt when salt_words > 0: leaf row m0 || s0 || m1 || s1 ... —
+    // then the root into the staging buffer if the tree did not write it there.  mat_stride: words between two rows (0: the width);
+    // on: the stream (nullptr: the prover's)
+    int commit(size_t n, const uint32_t* const* mats, const size_t* widths, uint32_t* const* salts, size_t height, uint32_t* layers,
+               uint32_t root_slot, size_t mat_stride = 0, hipStream_t on = nullptr) {
+        hipStream_t cs = on ? on : stream;
+        const uint32_t* mp[QTREE_MAX_MATS]; size_t hh[QTREE_MAX_MATS], ww[QTREE_MAX_MATS], ss[QTREE_MAX_MATS];
+        size_t k = 0;
+        for (size_t i = 0; i < n; i++, k++) {
+            mp[k] = mats[i]; hh[k] = height; ww[k] = widths[i]; ss[k] = mat_stride ? mat_stride : widths[i];
+            if (salt_words) { k++; mp[k] = salts[i]; hh[k] = height; ww[k] = ss[k] = salt_words; }
+        }
+        Tree* tp = nullptr;
+        int r = mmcs_commit(cs, mp, hh, ww, k, &tp, layers, pstage + root_slot, hash, ss, profile);
+        if (r) return r;
+        std::unique_ptr<Tree> t(tp);  // the layers live in the arena; the descriptor is not needed again
+        if (!t->root_copied) P3_HIP(hipMemcpyAsync(pstage + root_slot, t->layers + t->layer_off.back(), 32, hipMemcpyDeviceToDevice, cs));
+        return OK;
+    }
+    // FRI commit phase, rounds [0, r_end): commit the layer (ExtensionMmcs: rows of two ext elements, flattened), observe its root and
+    // sample beta, fold
+    int fri_rounds(Context& cx, const TsArgs& ts, uint32_t r_end) {
+        const uint32_t one_half = bb::inv(bb::to_monty(2));
+        const size_t row = 8;
+        int rc;
+        for (uint32_t r = 0; r < r_end; r++) {
+            const uint32_t log_half = log_big - 1 - r, half = 1u << log_half;
+            uint32_t* vec = fri_vec + fri_vec_off[r];
+            uint32_t* salts = salt_words ? fri_salts + fri_salt_off[r] : nullptr;
+            if ((rc = commit(1, &vec, &row, &salts, half, fri_layers + fri_layer_off[r], lay.froots + 8 * r))) return rc;
+            hipLaunchKernelGGL(ts_fri_round_kernel, dim3(1), dim3(64), 0, stream, ts, r, one_half);
+            P3_HIP(hipGetLastError());
+            TwoLevelTable inv_roots;
+            if ((rc = cx.get_root_table(stream, log_half + 1, true, &inv_roots))) return rc;
+            hipLaunchKernelGGL(fri_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, stream, inv_roots, vec, fri_vec + fri_vec_off[r + 1],
+                               half, log_half, ts.ds, r, one_half);
+            P3_HIP(hipGetLastError());
+        }
+        return OK;
+    }
+    // final polynomial: first 2^lfp entries (bit-reversed order) -> natural order -> inverse DFT (of the four base coordinates: the
+    // transform is linear over the base field) straight into the staging buffer; observed, and the proof-of-work search set up
+    int fri_final(Context& cx, const TsArgs& ts) {
+        const uint32_t fpl = 1u << fp.log_final_poly_len;
+        int rc;
+        if ((rc = bit_reverse_rows(stream, fri_vec + fri_vec_off[n_rounds], fp_ev, fpl, 4))) return rc;
+        if ((rc = ntt_dft(cx, stream, fp_ev, pstage + lay.fpoly, fpl, 4, true))) return rc;
+        hipLaunchKernelGGL(ts_final_kernel, dim3(1), dim3(64), 0, stream, ts, fpl, pow_mask());
+        P3_HIP(hipGetLastError());
+        return OK;
+    }
+
+    uint32_t pow_mask() const { return (1u << fp.proof_of_work_bits) - 1u; }
+    uint32_t grind_range(uint32_t first_log) const {
+        return 1u << std::min<uint32_t>(std::max<uint32_t>(first_log ? first_log : fp.proof_of_work_bits + 4, 8), 24);
+    }
+    int grind(const TsArgs& ts, uint64_t base, uint32_t count) {
+        if (hash == HASH_KECCAK) hipLaunchKernelGGL(grind_keccak_kernel, dim3(count / 256), dim3(256), 0, stream, ts.ds, pow_mask(), (uint32_t)base);
+        else hipLaunchKernelGGL(grind_kernel, dim3(count / 256), dim3(256), 0, stream, ts.ds, pow_mask(), (uint32_t)base);
+        P3_HIP(hipGetLastError());
+        return OK;
+    }
+    // proof of work: two launches, no synchronisation.  The first covers 2x the expected number of candidates (every block of a
+    // launch is resident before the first one finishes, so a wider first launch would simply do all of its work); the second covers
+    // up to 16x and its blocks return at once when the first found a witness (P[first misses] = e^-2, P[both miss] = e^-16: then the
+    // host continues the search after the proof's sync, continue_grind)
+    int grind_start(const TsArgs& ts) {
+        const uint32_t first_log = grind_first_log(), batch = grind_range(first_log);
+        const uint32_t head = first_log ? batch : std::min<uint32_t>(batch, 1u << std::max<uint32_t>(fp.proof_of_work_bits + 1, 8));
+        int rc;
+        if ((rc = grind(ts, 0, head))) return rc;
+        if (batch > head && (rc = grind(ts, head, batch - head))) return rc;
+        return OK;
+    }
+    // query phase: check the witness and sample the indices, gather every tree's opening into the query slots, then copy the first
+    // `words` staging words to the host
+    int queries(const TsArgs& ts, uint32_t* host, size_t words) {
+        const uint32_t nq = fp.num_queries;
+        hipLaunchKernelGGL(ts_queries_kernel, dim3(1), dim3(64), 0, stream, ts, nq, log_big, fp.proof_of_work_bits, qidx);
+        P3_HIP(hipGetLastError());
+        if (nq) {
+            hipLaunchKernelGGL(query_gather_kernel, dim3(nq, (uint32_t)trees.size()), dim3(64), 0, stream, qtrees, qidx, (uint32_t)slot_words,
+                               pstage + lay.slots);
+            P3_HIP(hipGetLastError());
+        }
+        P3_HIP(hipMemcpyAsync(host, pstage, words * 4, hipMemcpyDeviceToHost, stream));
+        return OK;
+    }
+    // the first range held no witness (status ST_GRIND_MISS; the proof's state is in the arena): continue the search range by range
+    // (each 4x the previous one), then redo the query phase; returns once the staging buffer has landed again
+    int continue_grind(const TsArgs& ts, uint32_t* host, size_t words) {
+        uint32_t batch = grind_range(grind_first_log()), found = 0xffffffffu;
+        int rc;
+        for (uint64_t base = batch; base < bb::P && found == 0xffffffffu; base += batch) {
+            batch = std::min<uint32_t>(batch * 4, 1u << 24);
+            if ((rc = grind(ts, base, batch))) return rc;
+            P3_HIP(hipMemcpyAsync(&found, &ts.ds->grind_result, 4, hipMemcpyDeviceToHost, stream));
+            P3_HIP(hipStreamSynchronize(stream));
+        }
+        if (found == 0xffffffffu) return fail(ERR_INTERNAL, "grind: no proof-of-work witness found");
+        if ((rc = queries(ts, host, words))) return rc;
+        P3_HIP(hipStreamSynchronize(stream));
+        return OK;
+    }
+
+    // The proof from the FRI commitments on: the roots; per query the opening of every input commitment, then the FRI walk (per round
+    // the sibling value, the salt when there is one, the path); the final polynomial and the witness
+    void put_fri(std::vector<uint8_t>& pf, const uint32_t* hp) const {
+        const StageLayout& L = lay;
+        const uint32_t nq = fp.num_queries, fpl = 1u << fp.log_final_poly_len, n_inputs = (uint32_t)trees.size() - n_rounds;
+        put_u32(pf, n_rounds); put_words(pf, hp + L.froots, (size_t)n_rounds * 8);
+        put_u32(pf, nq);
+        for (uint32_t q = 0; q < nq; q++) {
+            const uint32_t* slot = hp + L.slots + (size_t)q * slot_words;
+            put_u32(pf, n_inputs);
+            for (uint32_t i = 0; i < n_inputs; i++) {  // a tree lists its matrices, then (salt_words > 0) as many salts
+                const QTree& t = trees[i];
+                put_opening(pf, slot, salt_words ? t.n_mats / 2 : t.n_mats, t.width, salt_words, t.log_height);
+            }
+            put_u32(pf, n_rounds);
+            for (uint32_t r = 0; r < n_rounds; r++) {
+                const uint32_t lh = log_big - 1 - r, idx = hp[L.qidx + q] >> r;
+                put_words(pf, slot + 4 * ((idx ^ 1) & 1), 4);  // sibling_value
+                if (salt_words) { put_u32(pf, salt_words); put_words(pf, slot + 8, salt_words); }
+                put_u32(pf, lh); put_words(pf, slot + 8 + salt_words, (size_t)lh * 8);
+                slot += 8 + salt_words + (size_t)lh * 8;
+            }
+        }
+        put_u32(pf, fpl);
+        put_words(pf, hp + L.fpoly, (size_t)fpl * 4);
+        put_u32(pf, hp[L.witness]);
+    }
+};
 
 constexpr int N_STAGE_EVENTS = 7;
 
-struct FibProver::Impl {
-    int hash = HASH_POSEIDON2;
-    int profile = PROFILE_LATENCY;
-    int device = -1;  // the arena's device: prove() refuses to run with another one current
-    uint32_t log_n = 0, log_big = 0;
-    FriParams fp{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct FibProver::Impl : ProverCore {
+    uint32_t log_n = 0;
     // arena
     uint32_t *trace = nullptr, *lde_t = nullptr, *qflat = nullptr, *lde_q = nullptr, *d0 = nullptr, *d1 = nullptr;
-    uint32_t *layers_t = nullptr, *layers_q = nullptr, *fri_vec = nullptr, *fri_layers = nullptr;
-    uint32_t *partials = nullptr, *qidx = nullptr, *pstage = nullptr, *fp_ev = nullptr;
+    uint32_t *layers_t = nullptr, *layers_q = nullptr, *partials = nullptr;
     DevState* ds = nullptr;
-    QTree* qtrees = nullptr;
     // pinned: the proof staging buffer lands here, one copy per proof.  Two slots (and two sets of stage events): a second
     // proof may be enqueued behind the first on the same stream before the first is collected (enqueue / finish)
     uint32_t* host_stage[2] = {nullptr, nullptr};
@@ -681,12 +929,7 @@ struct FibProver::Impl {
     };
     std::deque<Pending> pending;
     uint64_t next_seq = 1, arena_owner = 0;  // arena_owner: the proof whose launch sequence ran last (its state is in the arena)
-    StageLayout lay;
     hipEvent_t ev[2][N_STAGE_EVENTS] = {{nullptr}, {nullptr}};
-    std::vector<void*> allocs;
-    uint32_t n_rounds = 0;
-    std::vector<size_t> fri_vec_off, fri_layer_off;  // word offsets per round
-    size_t slot_words = 0;
     uint32_t bary_blocks = 0;
     StageTimes times{};
     // diagnostics of the proof-of-work continuation path (p3hip_fib_prover_grind_miss_probe): how often the first search
@@ -694,16 +937,9 @@ struct FibProver::Impl {
     uint64_t grind_misses = 0;
     std::vector<uint32_t> miss_qidx;
     ~Impl() {
-        for (void* p : allocs) (void)hipFree(p);
         for (auto* h : host_stage) if (h) (void)hipHostFree(h);
         for (auto& set : ev) for (auto& e : set) if (e) (void)hipEventDestroy(e);
         for (auto& e : done) if (e) (void)hipEventDestroy(e);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
-    int alloc(uint32_t** p, size_t words) {
-        P3_HIP(hipMalloc(reinterpret_cast<void**>(p), words * 4 + 64));
-        allocs.push_back(*p);
-        return OK;
     }
 };
 
@@ -712,23 +948,15 @@ FibProver::~FibProver() { delete im; }
 
 int FibProver::init(uint32_t log_n, const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile) {
     Impl& s = *im;
-    if (profile != PROFILE_THROUGHPUT && profile != PROFILE_LATENCY) return fail(ERR_BAD_ARG, "fib prover: unknown profile");
-    s.profile = profile;
-    s.stream = stream; s.own_stream = own_stream;  // first: an owned stream is destroyed with the prover even when init fails
-    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return fail(ERR_BAD_ARG, "fib prover: unknown hash configuration");
-    im->hash = hash;
-    P3_HIP(hipGetDevice(&s.device));
+    int rc;
+    if ((rc = s.begin("fib prover", stream, own_stream, hash, profile))) return rc;
     if (log_n < 1) return fail(ERR_BAD_ARG, "fib prover: log_n must be >= 1");
     if (log_n + fp.log_blowup > MAX_LOG_DOMAIN)
         return fail(ERR_BAD_ARG, "fib prover: LDE domain above 2^" + std::to_string(MAX_LOG_DOMAIN) + " points (log_n + log_blowup)");
     if (fp.log_blowup < 1) return fail(ERR_BAD_ARG, "fib prover: log_blowup must be >= 1");
-    // p3_fri::prover::prove: `if log_final_poly_len > 0 { assert!(log_min_height > log_final_poly_len + log_blowup) }`
-    if (fp.log_final_poly_len > log_n || (fp.log_final_poly_len > 0 && fp.log_final_poly_len >= log_n))
-        return fail(ERR_BAD_ARG, "fib prover: log_final_poly_len must be below the trace's log height");
-    if (fp.proof_of_work_bits > 30) return fail(ERR_BAD_ARG, "fib prover: proof_of_work_bits too large");
-    s.log_n = log_n; s.fp = fp; s.log_big = log_n + fp.log_blowup;
+    if ((rc = s.set_fri("fib prover", fp, log_n))) return rc;
+    s.log_n = log_n;
     const size_t n = (size_t)1 << log_n, big = (size_t)1 << s.log_big;
-    int rc;
     if ((rc = s.alloc(&s.trace, n * 2))) return rc;
     if ((rc = s.alloc(&s.lde_t, big * 2))) return rc;
     if ((rc = s.alloc(&s.qflat, n * 4))) return rc;
@@ -737,59 +965,24 @@ int FibProver::init(uint32_t log_n, const FriParams& fp, hipStream_t stream, boo
     if ((rc = s.alloc(&s.d1, big * 4))) return rc;
     if ((rc = s.alloc(&s.layers_t, mmcs_layer_words(big)))) return rc;
     if ((rc = s.alloc(&s.layers_q, mmcs_layer_words(big)))) return rc;
-    // FRI: vector r has big >> r ext elements; its commitment tree has (big >> (r+1)) leaves
-    s.n_rounds = s.log_big - fp.log_blowup - fp.log_final_poly_len;
-    if (s.n_rounds > MAX_FRI_ROUNDS) return fail(ERR_BAD_ARG, "fib prover: too many FRI rounds");
-    size_t vec_words = 0, layer_words = 0;
-    for (uint32_t r = 0; r <= s.n_rounds; r++) { s.fri_vec_off.push_back(vec_words); vec_words += (big >> r) * 4; }
-    for (uint32_t r = 0; r < s.n_rounds; r++) { s.fri_layer_off.push_back(layer_words); layer_words += mmcs_layer_words(big >> (r + 1)); }
-    if ((rc = s.alloc(&s.fri_vec, vec_words))) return rc;
-    if ((rc = s.alloc(&s.fri_layers, layer_words + 8))) return rc;
+    if ((rc = s.alloc_fri())) return rc;
     // 256 workgroups: each lane then folds 16 rows at 2^20 before the 32 wave reductions (which cost as much as ~3 rows),
     // and the transcript kernel that finishes the sums reads 256 x 32 partial words instead of 1024 x 32
     s.bary_blocks = (uint32_t)std::min<size_t>(256, (n + BARY_BLOCK - 1) / BARY_BLOCK);
     if ((rc = s.alloc(&s.partials, (size_t)s.bary_blocks * 32))) return rc;
-    const size_t fpl = (size_t)1 << fp.log_final_poly_len;
-    if ((rc = s.alloc(&s.fp_ev, fpl * 4))) return rc;
     {
         uint32_t* p = nullptr;
         if ((rc = s.alloc(&p, (sizeof(DevState) + 3) / 4))) return rc;
         s.ds = reinterpret_cast<DevState*>(p);
         P3_HIP(hipMemset(s.ds, 0, sizeof(DevState)));
     }
-    // query staging: per query one slot holding every tree's (row, path)
-    size_t slot = (2 + s.log_big * 8) + (4 + s.log_big * 8);
-    for (uint32_t r = 0; r < s.n_rounds; r++) slot += 8 + (size_t)(s.log_big - 1 - r) * 8;
-    s.slot_words = slot;
-    const uint32_t nq = fp.num_queries;
-    StageLayout& L = s.lay;
-    L.fpoly = L.froots + 8 * s.n_rounds;
-    L.witness = L.fpoly + 4 * (uint32_t)fpl;
-    L.status = L.witness + 1;
-    L.qidx = L.status + 1;
-    L.slots = (L.qidx + nq + 3u) & ~3u;
-    const size_t stage_words = (size_t)L.slots + slot * nq;
-    if (stage_words > 0xffffffffull) return fail(ERR_BAD_ARG, "fib prover: proof staging buffer too large");
-    L.words = (uint32_t)stage_words;
-    if ((rc = s.alloc(&s.pstage, stage_words))) return rc;
-    if ((rc = s.alloc(&s.qidx, std::max<uint32_t>(nq, 1)))) return rc;
-    uint32_t* qt = nullptr;
-    if ((rc = s.alloc(&qt, (sizeof(QTree) / 4) * (s.n_rounds + 2)))) return rc;
-    s.qtrees = reinterpret_cast<QTree*>(qt);
-    for (auto& h : s.host_stage) P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&h), stage_words * 4 + 64));
+    // the trees opened per query: trace and quotient (one matrix each), then the FRI rounds'
+    s.trees.push_back(QTree{{s.lde_t}, {2}, {2}, 1, s.layers_t, s.log_big});
+    s.trees.push_back(QTree{{s.lde_q}, {4}, {4}, 1, s.layers_q, s.log_big});
+    if ((rc = s.layout("fib prover", 0))) return rc;
+    for (auto& h : s.host_stage) P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&h), (size_t)s.lay.words * 4 + 64));
     for (auto& set : s.ev) for (auto& e : set) P3_HIP(hipEventCreate(&e));
     for (auto& e : s.done) P3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // device descriptors of the trees opened per query (fixed for the prover's lifetime)
-    std::vector<QTree> qd;
-    uint32_t off = 0;
-    qd.push_back(QTree{s.lde_t, s.layers_t, 2, s.log_big, 0, off}); off += 2 + s.log_big * 8;
-    qd.push_back(QTree{s.lde_q, s.layers_q, 4, s.log_big, 0, off}); off += 4 + s.log_big * 8;
-    for (uint32_t r = 0; r < s.n_rounds; r++) {
-        uint32_t lh = s.log_big - 1 - r;
-        qd.push_back(QTree{s.fri_vec + s.fri_vec_off[r], s.fri_layers + s.fri_layer_off[r], 8, lh, r + 1, off});
-        off += 8 + lh * 8;
-    }
-    P3_HIP(hipMemcpy(s.qtrees, qd.data(), qd.size() * sizeof(QTree), hipMemcpyHostToDevice));
     return OK;
 }
 
@@ -886,41 +1079,8 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
     const uint32_t g_n = bb::two_adic_generator(log_n), g_n_inv = bb::inv(g_n);
     const StageLayout& L = s.lay;
     const TsArgs ts{s.ds, s.pstage, s.hash, L};
-    auto commit = [&](const uint32_t* mat, size_t h, size_t w, uint32_t* layers, uint32_t root_slot) -> int {
-        const uint32_t* mp[1] = {mat};
-        size_t hh[1] = {h}, ww[1] = {w};
-        Tree* tp = nullptr;
-        int r = mmcs_commit(st, mp, hh, ww, 1, &tp, layers, s.pstage + root_slot, s.hash, nullptr, s.profile);
-        if (r) return r;
-        std::unique_ptr<Tree> t(tp);  // the layers live in the arena; the descriptor is not needed again
-        if (!t->root_copied)
-            P3_HIP(hipMemcpyAsync(s.pstage + root_slot, t->layers + t->layer_off.back(), 32, hipMemcpyDeviceToDevice, st));
-        return OK;
-    };
-    const uint32_t one_half = bb::inv(bb::to_monty(2));
-    const uint32_t fpl = 1u << s.fp.log_final_poly_len;
-    const uint32_t pow_mask = (1u << s.fp.proof_of_work_bits) - 1u;
+    const size_t w_trace = 2, w_quot = 4;
     const uint32_t nq = s.fp.num_queries;
-    auto grind = [&](uint64_t base, uint32_t count) -> int {
-        if (s.hash == HASH_KECCAK) hipLaunchKernelGGL(grind_keccak_kernel, dim3(count / 256), dim3(256), 0, st, s.ds, pow_mask, (uint32_t)base);
-        else hipLaunchKernelGGL(grind_kernel, dim3(count / 256), dim3(256), 0, st, s.ds, pow_mask, (uint32_t)base);
-        P3_HIP(hipGetLastError());
-        return OK;
-    };
-    // P3HIP_GRIND_FIRST_LOG (tests): log2 of the whole first search range, to exercise the continuation path
-    const uint32_t first_log = [] { const char* e = getenv("P3HIP_GRIND_FIRST_LOG"); return e ? (uint32_t)atoi(e) : 0u; }();
-    uint32_t batch = 1u << std::min<uint32_t>(std::max<uint32_t>(first_log ? first_log : s.fp.proof_of_work_bits + 4, 8), 24);
-    auto queries = [&]() -> int {
-        hipLaunchKernelGGL(ts_queries_kernel, dim3(1), dim3(64), 0, st, ts, nq, log_big, s.fp.proof_of_work_bits, s.qidx);
-        P3_HIP(hipGetLastError());
-        if (nq) {
-            hipLaunchKernelGGL(query_gather_kernel, dim3(nq, s.n_rounds + 2), dim3(64), 0, st, s.qtrees, s.n_rounds + 2, s.qidx,
-                               (uint32_t)s.slot_words, s.pstage + L.slots);
-            P3_HIP(hipGetLastError());
-        }
-        P3_HIP(hipMemcpyAsync(s.host_stage[slot], s.pstage, (size_t)L.words * 4, hipMemcpyDeviceToHost, st));
-        return OK;
-    };
     // the whole launch sequence of one proof (a lambda: finish() runs it again when a proof-of-work search that came up
     // empty has to be continued after a newer proof has already reused the arena)
     auto body = [&]() -> int {
@@ -932,7 +1092,7 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
         const uint32_t* trace = pend.trace ? pend.trace : s.trace;
         if (!pend.trace && (rc = fib_trace(st, a, b, n, s.trace))) return rc;
         if ((rc = ntt_coset_lde(cx, st, trace, s.lde_t, n, 2, s.fp.log_blowup, gen, true))) return rc;
-        if ((rc = commit(s.lde_t, big, 2, s.layers_t, L.root_t))) return rc;
+        if ((rc = s.commit(1, &s.lde_t, &w_trace, nullptr, big, s.layers_t, L.root_t))) return rc;
         hipLaunchKernelGGL(ts_begin_kernel, dim3(1), dim3(64), 0, st, ts, trace, n, log_n, pend.pis);
         P3_HIP(hipGetLastError());
         P3_HIP(hipEventRecord(ev[1], st));
@@ -953,7 +1113,7 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
             P3_HIP(hipGetLastError());
         }
         if ((rc = ntt_coset_lde(cx, st, s.qflat, s.lde_q, n, 4, s.fp.log_blowup, bb::ONE, true))) return rc;
-        if ((rc = commit(s.lde_q, big, 4, s.layers_q, L.root_q))) return rc;
+        if ((rc = s.commit(1, &s.lde_q, &w_quot, nullptr, big, s.layers_q, L.root_q))) return rc;
         hipLaunchKernelGGL(ts_zeta_kernel, dim3(1), dim3(64), 0, st, ts, g_n);
         P3_HIP(hipGetLastError());
         P3_HIP(hipEventRecord(ev[2], st));
@@ -996,23 +1156,11 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
         uint32_t r_tail = s.n_rounds;
         if (s.profile == PROFILE_LATENCY && s.hash == HASH_POSEIDON2)
             while (r_tail > 0 && (big >> (r_tail - 1)) <= (1u << FRI_TAIL_MAX_LOG)) r_tail--;
-        for (uint32_t r = 0; r < r_tail; r++) {
-            uint32_t len = big >> r, half = len >> 1;
-            // ExtensionMmcs: rows of two ext elements, flattened
-            if ((rc = commit(s.fri_vec + s.fri_vec_off[r], half, 8, s.fri_layers + s.fri_layer_off[r], L.froots + 8 * r))) return rc;
-            hipLaunchKernelGGL(ts_fri_round_kernel, dim3(1), dim3(64), 0, st, ts, r, one_half);
-            P3_HIP(hipGetLastError());
-            TwoLevelTable inv_roots;
-            uint32_t log_half = log_big - 1 - r;
-            if ((rc = cx.get_root_table(st, log_half + 1, true, &inv_roots))) return rc;
-            hipLaunchKernelGGL(fri_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, st, inv_roots,
-                               s.fri_vec + s.fri_vec_off[r], s.fri_vec + s.fri_vec_off[r + 1], half, log_half, s.ds, r, one_half);
-            P3_HIP(hipGetLastError());
-        }
+        if ((rc = s.fri_rounds(cx, ts, r_tail))) return rc;
         if (r_tail < s.n_rounds) {
             FriTailArgs ta{};
             ta.ts = ts; ta.vec = s.fri_vec; ta.layers = s.fri_layers;
-            ta.r0 = r_tail; ta.n_tail = s.n_rounds - r_tail; ta.log_len0 = log_big - r_tail; ta.one_half = one_half;
+            ta.r0 = r_tail; ta.n_tail = s.n_rounds - r_tail; ta.log_len0 = log_big - r_tail; ta.one_half = bb::inv(bb::to_monty(2));
             for (uint32_t k = 0; k <= ta.n_tail; k++) {
                 if (s.fri_vec_off[r_tail + k] > 0xffffffffull) return fail(ERR_INTERNAL, "fri tail: vector offset out of range");
                 ta.vec_off[k] = (uint32_t)s.fri_vec_off[r_tail + k];
@@ -1025,27 +1173,15 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
             hipLaunchKernelGGL(fri_tail_kernel, dim3(1), dim3(1024), 0, st, ta);
             P3_HIP(hipGetLastError());
         }
-        // final polynomial: first 2^lfp entries (bit-reversed order) -> natural order -> inverse DFT (of the four base
-        // coordinates: the transform is linear over the base field) straight into the staging buffer
-        if ((rc = bit_reverse_rows(st, s.fri_vec + s.fri_vec_off[s.n_rounds], s.fp_ev, fpl, 4))) return rc;
-        if ((rc = ntt_dft(cx, st, s.fp_ev, s.pstage + L.fpoly, fpl, 4, true))) return rc;
-        hipLaunchKernelGGL(ts_final_kernel, dim3(1), dim3(64), 0, st, ts, fpl, pow_mask);
-        P3_HIP(hipGetLastError());
+        if ((rc = s.fri_final(cx, ts))) return rc;
         P3_HIP(hipEventRecord(ev[4], st));
 
-        // ---- proof of work: two launches, no synchronisation.  The first covers 2x the expected number of candidates
-        // (every block of a launch is resident before the first one finishes, so a wider first launch would simply do
-        // all of its work); the second covers up to 16x and its blocks return at once when the first found a witness
-        // (P[first misses] = e^-2, P[both miss] = e^-16: then the host continues the search after the proof's sync).
-        {
-            const uint32_t head = first_log ? batch : std::min<uint32_t>(batch, 1u << std::max<uint32_t>(s.fp.proof_of_work_bits + 1, 8));
-            if ((rc = grind(0, head))) return rc;
-            if (batch > head && (rc = grind(head, batch - head))) return rc;
-        }
+        // ---- proof of work ----
+        if ((rc = s.grind_start(ts))) return rc;
         P3_HIP(hipEventRecord(ev[5], st));
 
         // ---- query phase ----
-        if ((rc = queries())) return rc;
+        if ((rc = s.queries(ts, s.host_stage[slot], L.words))) return rc;
         P3_HIP(hipEventRecord(ev[6], st));
         return OK;
     };
@@ -1077,20 +1213,9 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
         s.miss_qidx.assign(nq, 0xdeadbeefu);
         if (nq) P3_HIP(hipMemcpyAsync(s.miss_qidx.data(), s.qidx, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
         P3_HIP(hipStreamSynchronize(st));
-        // continue the search range by range (each 4x the previous one), then redo the query phase
-        uint32_t found = 0xffffffffu;
-        for (uint64_t base = batch; base < bb::P && found == 0xffffffffu; base += batch) {
-            batch = std::min<uint32_t>(batch * 4, 1u << 24);
-            TR("prove: continue search base %llu batch %u\n", (unsigned long long)base, batch);
-            if ((rc = grind(base, batch))) return rc;
-            P3_HIP(hipMemcpyAsync(&found, &s.ds->grind_result, 4, hipMemcpyDeviceToHost, st));
-            P3_HIP(hipStreamSynchronize(st));
-            TR("prove: found %u\n", found);
-        }
-        if (found == 0xffffffffu) return fail(ERR_INTERNAL, "grind: no proof-of-work witness found");
-        if ((rc = queries())) return rc;
-        P3_HIP(hipStreamSynchronize(st));
-        TR("prove: queries redone, status %u\n", hp[L.status]);
+        TR("prove: first proof-of-work range empty, continuing the search\n");
+        if ((rc = s.continue_grind(ts, s.host_stage[slot], L.words))) return rc;
+        TR("prove: witness %u, queries redone, status %u\n", hp[L.witness], hp[L.status]);
     }
     if (hp[L.status] != 0) return fail(ERR_INTERNAL, "grind: witness rejected by the device transcript");
 
@@ -1104,27 +1229,7 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
     put_u32(pf, 2); put_words(pf, op, 8);
     put_u32(pf, 2); put_words(pf, op + 8, 8);
     put_u32(pf, 1); put_u32(pf, 4); put_words(pf, op + 16, 16);
-    put_u32(pf, s.n_rounds); put_words(pf, hp + L.froots, (size_t)s.n_rounds * 8);
-    put_u32(pf, nq);
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint32_t* slot = hp + L.slots + (size_t)q * s.slot_words;
-        put_u32(pf, 2);
-        put_u32(pf, 1); put_u32(pf, 2); put_words(pf, slot, 2); put_u32(pf, log_big); put_words(pf, slot + 2, (size_t)log_big * 8);
-        slot += 2 + log_big * 8;
-        put_u32(pf, 1); put_u32(pf, 4); put_words(pf, slot, 4); put_u32(pf, log_big); put_words(pf, slot + 4, (size_t)log_big * 8);
-        slot += 4 + log_big * 8;
-        put_u32(pf, s.n_rounds);
-        for (uint32_t r = 0; r < s.n_rounds; r++) {
-            uint32_t lh = log_big - 1 - r;
-            uint32_t idx = hp[L.qidx + q] >> r;
-            put_words(pf, slot + 4 * ((idx ^ 1) & 1), 4);  // sibling_value
-            put_u32(pf, lh); put_words(pf, slot + 8, (size_t)lh * 8);
-            slot += 8 + lh * 8;
-        }
-    }
-    put_u32(pf, fpl);
-    put_words(pf, hp + L.fpoly, (size_t)fpl * 4);
-    put_u32(pf, hp[L.witness]);
+    s.put_fri(pf, hp);
     TR("prove: serialised %zu bytes\n", pf.size());
     // stage times on the device timeline (events between the stages of the stream)
     float ms[N_STAGE_EVENTS - 1] = {0};

@@ -264,38 +264,8 @@ __global__ void __launch_bounds__(256) reduced_openings_h_kernel(ReducedHArgs a)
     st_ext(a.ro + 4 * (size_t)i, bb::add(bb::mul(s0, e0), bb::mul(s1, e1)));
 }
 
-// query phase gather for commitments of several (matrix, salt) pairs: block (q, tree) copies the opened values of
-// every matrix, then every salt row, then the sibling path into the query's slot
-constexpr uint32_t HQ_MAX = 2 * HCH;
-struct HQTree {
-    const uint32_t* mat[HQ_MAX];
-    uint32_t width[HQ_MAX];
-    uint32_t stride[HQ_MAX];  // words between two rows
-    uint32_t n_mats;  // values first (n_mats / 2 matrices), then their salts, as listed
-    const uint32_t* layers;
-    uint32_t log_height, shift, slot_off;
-};
-__global__ void query_gather_h_kernel(const HQTree* trees, const uint32_t* indices, uint32_t slot_words, uint32_t* out) {
-    P3_LATENCY_BOUND_KERNEL();
-    const HQTree& t = trees[blockIdx.y];
-    const uint64_t index = (indices[blockIdx.x] >> t.shift) & ((1ull << t.log_height) - 1ull);
-    uint32_t* dst = out + (size_t)blockIdx.x * slot_words + t.slot_off;
-    uint32_t off = 0;
-    for (uint32_t m = 0; m < t.n_mats; m++) {
-        for (uint32_t c = threadIdx.x; c < t.width[m]; c += blockDim.x) dst[off + c] = t.mat[m][index * t.stride[m] + c];
-        off += t.width[m];
-    }
-    uint64_t base = 0, len = 1ull << t.log_height;
-    for (uint32_t i = 0; i < t.log_height; i++) {
-        const uint64_t sib = (index >> i) ^ 1;
-        if (threadIdx.x < 8) dst[off + i * 8 + threadIdx.x] = t.layers[base + sib * 8 + threadIdx.x];
-        base += len * 8;
-        len >>= 1;
-    }
-}
-
-// ---- transcript kernels of the hiding protocol (the FRI rounds, the final polynomial and the queries use the
-// kernels of the non-hiding prover unchanged) ----
+// ---- transcript kernels of the hiding protocol (the FRI rounds, the final polynomial and the queries are the
+// non-hiding prover's kernels, launched by the host code both provers share: ProverCore in prover.hip) ----
 struct StageLayoutH {  // extends StageLayout: three roots, 36 opened values
     StageLayout s;
     uint32_t root_r;
@@ -417,13 +387,9 @@ __global__ void __launch_bounds__(TS_OPEN_H_THREADS) ts_open_h_kernel(TsArgs a, 
 #include "prover_tiny.hip.inc"
 
 // ------------------------------------------------------------------------------------------------
-struct FibHidingProver::Impl {
-    int hash = HASH_POSEIDON2, device = -1;
-    uint32_t log_n = 0, log_ext = 0, log_big = 0;
+struct FibHidingProver::Impl : ProverCore {
+    uint32_t log_n = 0, log_ext = 0;
     uint64_t seed = 1;
-    FriParams fp{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     // the three stream fills depend on nothing but the seed: they run on a side stream from the start of a proof, under the
     // trace generation, its LDE and (the FRI salts) everything up to the commit phase; each consumer waits for its fill's event
     hipStream_t side = nullptr;
@@ -434,7 +400,6 @@ struct FibHidingProver::Impl {
     // gain nothing (186.1 / 187.2 / 188.9 / 186.4 without, 186.1 / 165.3 / 185.6 / 184.7 with: twelve streams on eight hardware queues
     // now and then put one prover's side work in front of another's main chain).  The fills' side stream, in contrast, is worth
     // +7 % to the four-prover bench (176-180 -> 188-194) and stays on.
-    int profile = PROFILE_LATENCY;
     hipStream_t side2 = nullptr;
     hipEvent_t ev_r = nullptr;
     // arena
@@ -445,34 +410,21 @@ struct FibHidingProver::Impl {
     uint32_t* sel_tr = nullptr;
     uint32_t *rm = nullptr, *lde_r = nullptr, *salt_r = nullptr, *layers_r = nullptr;
     uint32_t *d0 = nullptr, *d1 = nullptr, *partials = nullptr;
-    uint32_t *fri_vec = nullptr, *fri_salts = nullptr, *fri_layers = nullptr, *fp_ev = nullptr;
     uint32_t *pcs_draws = nullptr, *mmcs_draws = nullptr;
-    size_t pcs_words = 0, mmcs_words = 0, fri_salt_words = 0;
+    size_t pcs_words = 0, mmcs_words = 0;
     bool one_fill = false;
     bool tiny = false;  // the whole proof in one launch of one workgroup (prover_tiny.hip.inc): latency profile, instances that fit
-    uint32_t *qidx = nullptr, *pstage = nullptr, *rng_ws = nullptr;
+    uint32_t* rng_ws = nullptr;
     DevStateH* hs = nullptr;
     DevRng* rngs = nullptr;  // [0] input mmcs, [1] fri mmcs, [2] pcs
-    HQTree* qtrees = nullptr;
     uint32_t* host_stage = nullptr;
-    StageLayout lay;
     uint32_t root_r_off = 0;
-    std::vector<void*> allocs;
-    uint32_t n_rounds = 0, bary_blocks = 0;
-    std::vector<size_t> fri_vec_off, fri_salt_off, fri_layer_off;
-    size_t slot_words = 0;
+    uint32_t bary_blocks = 0;
     ~Impl() {
-        for (void* p : allocs) (void)hipFree(p);
         if (host_stage) (void)hipHostFree(host_stage);
         for (hipEvent_t e : {ev_start, ev_pcs, ev_mmcs, ev_fri, ev_r}) if (e) (void)hipEventDestroy(e);
         if (side) (void)hipStreamDestroy(side);
         if (side2) (void)hipStreamDestroy(side2);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
-    int alloc(uint32_t** p, size_t words) {
-        P3_HIP(hipMalloc(reinterpret_cast<void**>(p), words * 4 + 64));
-        allocs.push_back(*p);
-        return OK;
     }
 };
 
@@ -481,25 +433,20 @@ FibHidingProver::~FibHidingProver() { delete im; }
 
 int FibHidingProver::init(uint32_t log_n, const FriParams& fp, hipStream_t stream, bool own_stream, int hash, uint64_t seed, int profile) {
     Impl& s = *im;
-    if (profile != PROFILE_THROUGHPUT && profile != PROFILE_LATENCY) return fail(ERR_BAD_ARG, "hiding prover: unknown profile");
-    s.profile = profile;
-    s.stream = stream; s.own_stream = own_stream;
-    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return fail(ERR_BAD_ARG, "hiding prover: unknown hash configuration");
-    s.hash = hash; s.seed = seed;
-    P3_HIP(hipGetDevice(&s.device));
-    if (log_n < 1 || fp.log_blowup < 1) return fail(ERR_BAD_ARG, "hiding prover: log_n and log_blowup must be >= 1");
-    s.log_n = log_n; s.log_ext = log_n + 1; s.log_big = s.log_ext + fp.log_blowup; s.fp = fp;
-    if (s.log_big > MAX_LOG_DOMAIN_HIDING)
-        return fail(ERR_BAD_ARG, "hiding prover: LDE domain above 2^" + std::to_string(MAX_LOG_DOMAIN_HIDING) + " points (log_n + 1 + log_blowup)");
-    if (fp.log_final_poly_len >= s.log_ext) return fail(ERR_BAD_ARG, "hiding prover: log_final_poly_len must be below the randomized trace's log height");
-    if (fp.proof_of_work_bits > 30) return fail(ERR_BAD_ARG, "hiding prover: proof_of_work_bits too large");
-    const size_t h = (size_t)1 << log_n, h2 = 2 * h, big = (size_t)1 << s.log_big;
     int rc;
+    if ((rc = s.begin("hiding prover", stream, own_stream, hash, profile))) return rc;
+    s.seed = seed; s.salt_words = HSALT;
+    if (log_n < 1 || fp.log_blowup < 1) return fail(ERR_BAD_ARG, "hiding prover: log_n and log_blowup must be >= 1");
+    s.log_n = log_n; s.log_ext = log_n + 1;
+    if (s.log_ext + fp.log_blowup > MAX_LOG_DOMAIN_HIDING)
+        return fail(ERR_BAD_ARG, "hiding prover: LDE domain above 2^" + std::to_string(MAX_LOG_DOMAIN_HIDING) + " points (log_n + 1 + log_blowup)");
+    if ((rc = s.set_fri("hiding prover", fp, s.log_ext))) return rc;
+    const size_t h = (size_t)1 << log_n, h2 = 2 * h, big = (size_t)1 << s.log_big;
 #define HA(ptr, words) if ((rc = s.alloc(&(ptr), (words)))) return rc
     // every draw of a proof has a known place in its stream, so each stream is ONE region filled by one launch set:
     //   pcs  : trace randomization | chunk blinding polynomials | randomization matrix
     //   mmcs : salts of the trace commitment | of the four chunks | of the randomization commitment
-    //   fri  : salts of every commit-phase round, in round order (fri_salts below)
+    //   fri  : salts of every commit-phase round, in round order (ProverCore::fri_salts)
     s.pcs_words = h * (HW + 2 * HNRC) + (HCH - 1) * h * HD + h2 * HRW;
     s.mmcs_words = (HCH + 2) * big * HSALT;
     HA(s.pcs_draws, s.pcs_words); HA(s.mmcs_draws, s.mmcs_words);
@@ -519,72 +466,38 @@ int FibHidingProver::init(uint32_t log_n, const FriParams& fp, hipStream_t strea
     HA(s.d0, big * 4); HA(s.d1, big * 4);
     s.bary_blocks = (uint32_t)std::min<size_t>(256, (h2 + BARY_BLOCK - 1) / BARY_BLOCK);
     HA(s.partials, (size_t)7 * s.bary_blocks * 32);
-    s.n_rounds = s.log_big - fp.log_blowup - fp.log_final_poly_len;
-    if (s.n_rounds > MAX_FRI_ROUNDS) return fail(ERR_BAD_ARG, "hiding prover: too many FRI rounds");
-    size_t vec_words = 0, salt_words = 0, layer_words = 0;
-    for (uint32_t r = 0; r <= s.n_rounds; r++) { s.fri_vec_off.push_back(vec_words); vec_words += (big >> r) * 4; }
-    for (uint32_t r = 0; r < s.n_rounds; r++) {
-        s.fri_salt_off.push_back(salt_words); salt_words += (big >> (r + 1)) * HSALT;
-        s.fri_layer_off.push_back(layer_words); layer_words += mmcs_layer_words(big >> (r + 1));
-    }
-    HA(s.fri_vec, vec_words); HA(s.fri_salts, salt_words + 8); HA(s.fri_layers, layer_words + 8);
-    const size_t fpl = (size_t)1 << fp.log_final_poly_len;
-    HA(s.fp_ev, fpl * 4);
+    if ((rc = s.alloc_fri())) return rc;
     { uint32_t* p = nullptr; HA(p, (sizeof(DevStateH) + 3) / 4); s.hs = reinterpret_cast<DevStateH*>(p); P3_HIP(hipMemset(s.hs, 0, sizeof(DevStateH))); }
     { uint32_t* p = nullptr; HA(p, 3 * sizeof(DevRng) / 4); s.rngs = reinterpret_cast<DevRng*>(p); }
     {
         // one fill per stream when the jump tables reach that far (up to 2^30 raw draws), else piece by piece
-        s.fri_salt_words = salt_words;
-        s.one_fill = rng_fill_supported(s.pcs_words) && rng_fill_supported(s.mmcs_words) && rng_fill_supported(salt_words);
+        s.one_fill = rng_fill_supported(s.pcs_words) && rng_fill_supported(s.mmcs_words) && rng_fill_supported(s.fri_salt_words);
         if (const char* e = getenv("P3HIP_HIDING_PIECEWISE")) if (e[0] == '1') s.one_fill = false;  // tests: the large-size path
-        const uint64_t n_max = s.one_fill ? std::max<uint64_t>(std::max<uint64_t>(s.pcs_words, s.mmcs_words), salt_words)
+        const uint64_t n_max = s.one_fill ? std::max<uint64_t>(std::max<uint64_t>(s.pcs_words, s.mmcs_words), s.fri_salt_words)
                                           : std::max<uint64_t>(big * HSALT, h2 * HRW);
         size_t w = 0;
         if ((rc = rng_workspace_words(n_max, &w))) return rc;
         HA(s.rng_ws, w);
     }
-    // per query: [random: 8 + 4 + path] [trace: 6 + 4 + path] [chunks: 16 + 16 + path] [FRI r: 8 + 4 + path_r]
-    const uint32_t lb = s.log_big;
-    size_t slot = (HRW + HSALT + lb * 8) + (HTW + HSALT + lb * 8) + (HCH * HD + HCH * HSALT + lb * 8);
-    for (uint32_t r = 0; r < s.n_rounds; r++) slot += 8 + HSALT + (size_t)(lb - 1 - r) * 8;
-    s.slot_words = slot;
-    const uint32_t nq = fp.num_queries;
-    StageLayout& L = s.lay;
-    L.root_t = 0; L.root_q = 8; s.root_r_off = 16; L.opened = 24; L.froots = L.opened + 4 * HOPEN;
-    L.fpoly = L.froots + 8 * s.n_rounds;
-    L.witness = L.fpoly + 4 * (uint32_t)fpl;
-    L.status = L.witness + 1;
-    L.qidx = L.status + 1;
-    L.slots = (L.qidx + nq + 3u) & ~3u;
-    const size_t stage_words = (size_t)L.slots + slot * nq;
-    if (stage_words > 0xffffffffull) return fail(ERR_BAD_ARG, "hiding prover: proof staging buffer too large");
-    L.words = (uint32_t)stage_words;
-    HA(s.pstage, stage_words + 1); HA(s.qidx, std::max<uint32_t>(nq, 1));  // + the random streams' shortage flag
-    { uint32_t* p = nullptr; HA(p, (sizeof(HQTree) / 4 + 1) * (s.n_rounds + 3)); s.qtrees = reinterpret_cast<HQTree*>(p); }
 #undef HA
-    P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.host_stage), stage_words * 4 + 64));
-    std::vector<HQTree> qd;
-    uint32_t off = 0;
-    { HQTree t{}; t.mat[0] = s.lde_r; t.width[0] = t.stride[0] = HRW; t.mat[1] = s.salt_r; t.width[1] = t.stride[1] = HSALT; t.n_mats = 2;
-      t.layers = s.layers_r; t.log_height = lb; t.shift = 0; t.slot_off = off; qd.push_back(t); off += HRW + HSALT + lb * 8; }
-    { HQTree t{}; t.mat[0] = s.lde_t; t.width[0] = t.stride[0] = HTW; t.mat[1] = s.salt_t; t.width[1] = t.stride[1] = HSALT; t.n_mats = 2;
-      t.layers = s.layers_t; t.log_height = lb; t.shift = 0; t.slot_off = off; qd.push_back(t); off += HTW + HSALT + lb * 8; }
-    { HQTree t{};
-      for (uint32_t c = 0; c < HCH; c++) {
-          t.mat[c] = s.lde_q[c]; t.width[c] = HD; t.stride[c] = HQS;
-          t.mat[HCH + c] = s.salt_q[c]; t.width[HCH + c] = t.stride[HCH + c] = HSALT;
-      }
-      t.n_mats = 2 * HCH; t.layers = s.layers_q; t.log_height = lb; t.shift = 0; t.slot_off = off; qd.push_back(t);
-      off += HCH * HD + HCH * HSALT + lb * 8; }
-    for (uint32_t r = 0; r < s.n_rounds; r++) {
-        HQTree t{};
-        t.mat[0] = s.fri_vec + s.fri_vec_off[r]; t.width[0] = t.stride[0] = 8;
-        t.mat[1] = s.fri_salts + s.fri_salt_off[r]; t.width[1] = t.stride[1] = HSALT; t.n_mats = 2;
-        t.layers = s.fri_layers + s.fri_layer_off[r]; t.log_height = lb - 1 - r; t.shift = r + 1; t.slot_off = off;
-        qd.push_back(t);
-        off += 8 + HSALT + (lb - 1 - r) * 8;
+    // the trees opened per query: the randomization matrix, the randomized trace, the four chunks (then the FRI rounds'), each
+    // matrix with its salt
+    const uint32_t lb = s.log_big, nq = fp.num_queries;
+    s.trees.push_back(QTree{{s.lde_r, s.salt_r}, {HRW, HSALT}, {HRW, HSALT}, 2, s.layers_r, lb});
+    s.trees.push_back(QTree{{s.lde_t, s.salt_t}, {HTW, HSALT}, {HTW, HSALT}, 2, s.layers_t, lb});
+    {
+        QTree t{};
+        for (uint32_t c = 0; c < HCH; c++) {
+            t.mat[c] = s.lde_q[c]; t.width[c] = HD; t.stride[c] = HQS;
+            t.mat[HCH + c] = s.salt_q[c]; t.width[HCH + c] = t.stride[HCH + c] = HSALT;
+        }
+        t.n_mats = 2 * HCH; t.layers = s.layers_q; t.log_height = lb;
+        s.trees.push_back(t);
     }
-    P3_HIP(hipMemcpy(s.qtrees, qd.data(), qd.size() * sizeof(HQTree), hipMemcpyHostToDevice));
+    StageLayout& L = s.lay;
+    s.root_r_off = 16; L.opened = 24; L.froots = L.opened + 4 * HOPEN;
+    if ((rc = s.layout("hiding prover", 1))) return rc;  // + the random streams' shortage flag
+    P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.host_stage), (size_t)L.words * 4 + 64));
     {   // selectors of the trace domain on the quotient coset: fixed by log_n, computed once
         Context* cxp;
         if ((rc = get_context(&cxp))) return rc;
@@ -602,8 +515,8 @@ int FibHidingProver::init(uint32_t log_n, const FriParams& fp, hipStream_t strea
     // 2^8 points, every random stream within one wave's small fill, a proof-of-work search short enough to run candidate by candidate
     // on one wave.  The reference's own instance (n = 8, fib_air.rs:56-72) is one of them.
     s.tiny = profile == PROFILE_LATENCY && s.log_big <= TINY_MAX_LOG_BIG && s.n_rounds <= TINY_MAX_ROUNDS && fp.proof_of_work_bits <= 4 &&
-             nq <= 64 && rng_small_chunks(s.pcs_words) && rng_small_chunks(s.mmcs_words) && (salt_words == 0 || rng_small_chunks(salt_words)) &&
-             vec_words <= 0xffffffffull && layer_words <= 0xffffffffull;
+             nq <= 64 && rng_small_chunks(s.pcs_words) && rng_small_chunks(s.mmcs_words) && (s.fri_salt_words == 0 || rng_small_chunks(s.fri_salt_words)) &&
+             s.fri_vec_words <= 0xffffffffull && s.fri_layer_words <= 0xffffffffull;
     // fills on a side stream under both profiles (+7 % with four provers, profiles/r04_latency_ab.txt); the randomization commitment
     // on a SECOND side stream under the latency profile only (a lone 2^19-row proof 5.5 -> 5.3 ms; four provers gain nothing and now
     // and then lose: twelve streams on eight hardware queues)
@@ -637,7 +550,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
     Context& cx = *cxp;
     if (cx.device != s.device) return fail(ERR_BAD_ARG, "hiding prover: created on another device");
     hipStream_t st = s.stream;
-    const uint32_t log_n = s.log_n, log_ext = s.log_ext, log_big = s.log_big, lb = log_big;
+    const uint32_t log_n = s.log_n, log_ext = s.log_ext, log_big = s.log_big;
     const uint32_t h = 1u << log_n, h2 = 2 * h, big = 1u << log_big, log_q = log_n + 2;
     const uint32_t gen = bb::to_monty(bb::GEN);
     const uint32_t g_h = bb::two_adic_generator(log_n);
@@ -649,7 +562,6 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
     // cleared by the launch that seeds the three streams (no memset, no second copy: at the reference's n = 8 a proof IS its launches)
     uint32_t* err = s.pstage + L.words;
     const uint32_t nq = s.fp.num_queries;
-    const uint32_t fpl = 1u << s.fp.log_final_poly_len;
     const uint32_t* const hp = s.host_stage;
     if (s.tiny) {
         // ---- one launch: prover_tiny.hip.inc ----
@@ -681,7 +593,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
         for (uint32_t r = 0; r <= s.n_rounds; r++) ta.fri_vec_off[r] = (uint32_t)s.fri_vec_off[r];
         for (uint32_t r = 0; r < s.n_rounds; r++) { ta.fri_salt_off[r] = (uint32_t)s.fri_salt_off[r]; ta.fri_layer_off[r] = (uint32_t)s.fri_layer_off[r]; }
         ta.hs = s.hs; ta.pstage = s.pstage; ta.lay = L; ta.root_r_off = s.root_r_off; ta.slot_words = (uint32_t)s.slot_words;
-        ta.qtrees = s.qtrees; ta.n_trees = s.n_rounds + 3; ta.qidx = s.qidx; ta.err = err;
+        ta.qtrees = s.qtrees; ta.n_trees = (uint32_t)s.trees.size(); ta.qidx = s.qidx; ta.err = err;
         // three waves' raw candidates + the domain tables behind them (at most 2^8 + 2^7 + 2^6 + 4 x 2^6 words)
         const size_t lds = (size_t)3 * RNG_SMALL_CHUNKS * RNG_SMALL_STRIDE * 4 + 4096;
         if ((rc = cx.ensure_dynamic_lds(reinterpret_cast<const void*>(tiny_hiding_prover_kernel), (int)lds))) return rc;
@@ -713,29 +625,13 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
             if (s.side) P3_HIP(hipEventRecord(s.ev_fri, s.side));
         }
         auto wait_fill = [&](hipEvent_t e) -> int { if (s.side) P3_HIP(hipStreamWaitEvent(st, e, 0)); return OK; };
-        // hiding commitment of (matrix, salt) pairs: leaf row = m0 || s0 || m1 || s1 ...
-        auto commit = [&](const uint32_t* const* mats, const size_t* widths, uint32_t* const* salts, size_t n, size_t height,
-                          uint32_t* layers, uint32_t root_slot, size_t mat_stride = 0, hipStream_t on = nullptr) -> int {
-            hipStream_t cs = on ? on : st;
-            const uint32_t* mp[HQ_MAX]; size_t hh[HQ_MAX], ww[HQ_MAX], ss[HQ_MAX];
-            for (size_t i = 0; i < n; i++) {
-                mp[2 * i] = mats[i]; hh[2 * i] = height; ww[2 * i] = widths[i]; ss[2 * i] = mat_stride ? mat_stride : widths[i];
-                mp[2 * i + 1] = salts[i]; hh[2 * i + 1] = height; ww[2 * i + 1] = ss[2 * i + 1] = HSALT;
-            }
-            Tree* tp = nullptr;
-            int r = mmcs_commit(cs, mp, hh, ww, 2 * n, &tp, layers, s.pstage + root_slot, s.hash, ss, s.profile);
-            if (r) return r;
-            std::unique_ptr<Tree> t(tp);
-            if (!t->root_copied)
-                P3_HIP(hipMemcpyAsync(s.pstage + root_slot, t->layers + t->layer_off.back(), 32, hipMemcpyDeviceToDevice, cs));
-            return OK;
-        };
+        // hiding commitments (ProverCore::commit): leaf row = m0 || s0 || m1 || s1 ...
+        const size_t w_r = HRW, w_t = HTW, w_q[HCH] = {HD, HD, HD, HD};
         // the randomization polynomial's commitment, early and on its own stream when there is one
         auto commit_random = [&](hipStream_t on) -> int {
             int r = ntt_coset_lde(cx, on, s.rm, s.lde_r, h2, HRW, s.fp.log_blowup, gen, true);
             if (r) return r;
-            const uint32_t* m[1] = {s.lde_r}; size_t w[1] = {HRW}; uint32_t* sl[1] = {s.salt_r};
-            return commit(m, w, sl, 1, big, s.layers_r, s.root_r_off, 0, on);
+            return s.commit(1, &s.lde_r, &w_r, &s.salt_r, big, s.layers_r, s.root_r_off, 0, on);
         };
         if (s.side2) {
             P3_HIP(hipStreamWaitEvent(s.side2, s.ev_start, 0));  // the previous proof's readers of lde_r / layers_r / the root slot
@@ -755,8 +651,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
         if ((rc = ntt_coset_lde(cx, st, s.rt, s.lde_t, h2, HTW, s.fp.log_blowup, gen, true))) return rc;
         if ((rc = fill(rng_mmcs, s.salt_t, (uint64_t)big * HSALT))) return rc;
         if ((rc = wait_fill(s.ev_mmcs))) return rc;
-        { const uint32_t* m[1] = {s.lde_t}; size_t w[1] = {HTW}; uint32_t* sl[1] = {s.salt_t};
-          if ((rc = commit(m, w, sl, 1, big, s.layers_t, L.root_t))) return rc; }
+        if ((rc = s.commit(1, &s.lde_t, &w_t, &s.salt_t, big, s.layers_t, L.root_t))) return rc;
         hipLaunchKernelGGL(ts_begin_h_kernel, dim3(1), dim3(64), 0, st, ts, trace, h, log_n, given);
         P3_HIP(hipGetLastError());
 
@@ -797,9 +692,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
         // from the coefficients where the narrow plan covers the shape (no forward transform to <g_2h> and back)
         if ((rc = ntt_coset_lde_from_coeffs(cx, st, s.ext, s.lde_qb, s.ev2, h2, HQS, s.fp.log_blowup, gen))) return rc;
         for (uint32_t c = 0; c < HCH; c++) if ((rc = fill(rng_mmcs, s.salt_q[c], (uint64_t)big * HSALT))) return rc;
-        { const uint32_t* m[HCH]; size_t w[HCH]; uint32_t* sl[HCH];
-          for (uint32_t c = 0; c < HCH; c++) { m[c] = s.lde_q[c]; w[c] = HD; sl[c] = s.salt_q[c]; }
-          if ((rc = commit(m, w, sl, HCH, big, s.layers_q, L.root_q, HQS))) return rc; }
+        if ((rc = s.commit(HCH, s.lde_q, w_q, s.salt_q, big, s.layers_q, L.root_q, HQS))) return rc;
 
         // ---- randomization polynomial commitment ----
         if (s.side2) {
@@ -844,66 +737,17 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
             P3_HIP(hipGetLastError());
         }
 
-        // ---- FRI commit phase: ExtensionMmcs over the hiding MMCS, salts from the `fri` stream ----
-        const uint32_t one_half = bb::inv(bb::to_monty(2));
+        // ---- FRI commit phase: ExtensionMmcs over the hiding MMCS, salts from the `fri` stream; proof of work; query phase ----
         if ((rc = wait_fill(s.ev_fri))) return rc;
-        for (uint32_t r = 0; r < s.n_rounds; r++) {
-            const uint32_t len = big >> r, half = len >> 1;
-            uint32_t* salts = s.fri_salts + s.fri_salt_off[r];
-            if ((rc = fill(rng_fri, salts, (uint64_t)half * HSALT))) return rc;
-            { const uint32_t* m[1] = {s.fri_vec + s.fri_vec_off[r]}; size_t w[1] = {8}; uint32_t* sl[1] = {salts};
-              if ((rc = commit(m, w, sl, 1, half, s.fri_layers + s.fri_layer_off[r], L.froots + 8 * r))) return rc; }
-            hipLaunchKernelGGL(ts_fri_round_kernel, dim3(1), dim3(64), 0, st, ts, r, one_half);
-            P3_HIP(hipGetLastError());
-            TwoLevelTable inv_roots;
-            const uint32_t log_half = log_big - 1 - r;
-            if ((rc = cx.get_root_table(st, log_half + 1, true, &inv_roots))) return rc;
-            hipLaunchKernelGGL(fri_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, st, inv_roots, s.fri_vec + s.fri_vec_off[r],
-                               s.fri_vec + s.fri_vec_off[r + 1], half, log_half, ds, r, one_half);
-            P3_HIP(hipGetLastError());
-        }
-        if ((rc = bit_reverse_rows(st, s.fri_vec + s.fri_vec_off[s.n_rounds], s.fp_ev, fpl, 4))) return rc;
-        if ((rc = ntt_dft(cx, st, s.fp_ev, s.pstage + L.fpoly, fpl, 4, true))) return rc;
-        const uint32_t pow_mask = (1u << s.fp.proof_of_work_bits) - 1u;
-        hipLaunchKernelGGL(ts_final_kernel, dim3(1), dim3(64), 0, st, ts, fpl, pow_mask);
-        P3_HIP(hipGetLastError());
-        auto grind = [&](uint64_t base, uint32_t count) -> int {
-            if (s.hash == HASH_KECCAK) hipLaunchKernelGGL(grind_keccak_kernel, dim3(count / 256), dim3(256), 0, st, ds, pow_mask, (uint32_t)base);
-            else hipLaunchKernelGGL(grind_kernel, dim3(count / 256), dim3(256), 0, st, ds, pow_mask, (uint32_t)base);
-            P3_HIP(hipGetLastError());
-            return OK;
-        };
-        uint32_t batch = 1u << std::min<uint32_t>(std::max<uint32_t>(s.fp.proof_of_work_bits + 4, 8), 24);
-        {
-            const uint32_t head = std::min<uint32_t>(batch, 1u << std::max<uint32_t>(s.fp.proof_of_work_bits + 1, 8));
-            if ((rc = grind(0, head))) return rc;
-            if (batch > head && (rc = grind(head, batch - head))) return rc;
-        }
-        auto queries = [&]() -> int {
-            hipLaunchKernelGGL(ts_queries_kernel, dim3(1), dim3(64), 0, st, ts, nq, log_big, s.fp.proof_of_work_bits, s.qidx);
-            P3_HIP(hipGetLastError());
-            if (nq) {
-                hipLaunchKernelGGL(query_gather_h_kernel, dim3(nq, s.n_rounds + 3), dim3(64), 0, st, s.qtrees, s.qidx, (uint32_t)s.slot_words,
-                                   s.pstage + L.slots);
-                P3_HIP(hipGetLastError());
-            }
-            P3_HIP(hipMemcpyAsync(s.host_stage, s.pstage, ((size_t)L.words + 1) * 4, hipMemcpyDeviceToHost, st));  // + the shortage flag
-            return OK;
-        };
-        if ((rc = queries())) return rc;
+        for (uint32_t r = 0; r < s.n_rounds; r++)
+            if ((rc = fill(rng_fri, s.fri_salts + s.fri_salt_off[r], (uint64_t)(big >> (r + 1)) * HSALT))) return rc;
+        if ((rc = s.fri_rounds(cx, ts, s.n_rounds))) return rc;
+        if ((rc = s.fri_final(cx, ts))) return rc;
+        if ((rc = s.grind_start(ts))) return rc;
+        const size_t words = (size_t)L.words + 1;  // + the shortage flag
+        if ((rc = s.queries(ts, s.host_stage, words))) return rc;
         P3_HIP(hipStreamSynchronize(st));
-        if (hp[L.status] == ST_GRIND_MISS) {
-            uint32_t found = 0xffffffffu;
-            for (uint64_t base = batch; base < bb::P && found == 0xffffffffu; base += batch) {
-                batch = std::min<uint32_t>(batch * 4, 1u << 24);
-                if ((rc = grind(base, batch))) return rc;
-                P3_HIP(hipMemcpyAsync(&found, &ds->grind_result, 4, hipMemcpyDeviceToHost, st));
-                P3_HIP(hipStreamSynchronize(st));
-            }
-            if (found == 0xffffffffu) return fail(ERR_INTERNAL, "grind: no proof-of-work witness found");
-            if ((rc = queries())) return rc;
-            P3_HIP(hipStreamSynchronize(st));
-        }
+        if (hp[L.status] == ST_GRIND_MISS && (rc = s.continue_grind(ts, s.host_stage, words))) return rc;
     }
     if (hp[L.status] != 0) return fail(ERR_INTERNAL, "grind: witness rejected by the device transcript");
     if (hp[L.words] != 0) return fail(ERR_INTERNAL, "rng: a random stream ran out of raw draws");
@@ -920,33 +764,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
     put_u32(pf, HTW); put_words(pf, op, 4 * HTW); op += 4 * HTW;
     put_u32(pf, HCH);
     for (uint32_t c = 0; c < HCH; c++) { put_u32(pf, HD); put_words(pf, op, 4 * HD); op += 4 * HD; }
-    put_u32(pf, s.n_rounds); put_words(pf, hp + L.froots, (size_t)s.n_rounds * 8);
-    put_u32(pf, nq);
-    auto put_opening = [&](const uint32_t*& slot, uint32_t n, const uint32_t* widths, uint32_t depth) {
-        put_u32(pf, n);
-        for (uint32_t m = 0; m < n; m++) { put_u32(pf, widths[m]); put_words(pf, slot, widths[m]); slot += widths[m]; }
-        for (uint32_t m = 0; m < n; m++) { put_u32(pf, HSALT); put_words(pf, slot, HSALT); slot += HSALT; }
-        put_u32(pf, depth); put_words(pf, slot, (size_t)depth * 8); slot += (size_t)depth * 8;
-    };
-    const uint32_t w_r[1] = {HRW}, w_t[1] = {HTW}, w_q[HCH] = {HD, HD, HD, HD};
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint32_t* slot = hp + L.slots + (size_t)q * s.slot_words;
-        put_u32(pf, 3);
-        put_opening(slot, 1, w_r, lb);
-        put_opening(slot, 1, w_t, lb);
-        put_opening(slot, HCH, w_q, lb);
-        put_u32(pf, s.n_rounds);
-        for (uint32_t r = 0; r < s.n_rounds; r++) {
-            const uint32_t lh = lb - 1 - r, idx = hp[L.qidx + q] >> r;
-            put_words(pf, slot + 4 * ((idx ^ 1) & 1), 4);  // sibling_value
-            put_u32(pf, HSALT); put_words(pf, slot + 8, HSALT);
-            put_u32(pf, lh); put_words(pf, slot + 8 + HSALT, (size_t)lh * 8);
-            slot += 8 + HSALT + (size_t)lh * 8;
-        }
-    }
-    put_u32(pf, fpl);
-    put_words(pf, hp + L.fpoly, (size_t)fpl * 4);
-    put_u32(pf, hp[L.witness]);
+    s.put_fri(pf, hp);
     return OK;
 }
 

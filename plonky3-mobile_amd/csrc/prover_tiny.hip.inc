@@ -44,7 +44,7 @@ struct TinyArgs {
     uint32_t* pstage;
     StageLayout lay;
     uint32_t root_r_off, slot_words;
-    const HQTree* qtrees;
+    const QTree* qtrees;
     uint32_t n_trees;
     uint32_t* qidx;
     uint32_t* err;  // the streams' shortage flag: the word behind the staging buffer
@@ -539,10 +539,10 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_hiding_prover_kernel(TinyAr
     }
     __syncthreads();
     TINY_STAMP("grind+query");
-    // ---- query openings: every (query, tree) pair by one wave (query_gather_h_kernel) ----
+    // ---- query openings: every (query, tree) pair by one wave (query_gather_kernel) ----
     for (uint32_t job = wave; job < a.nq * a.n_trees; job += TINY_THREADS / 64) {
         const uint32_t q = job / a.n_trees;
-        const HQTree& t = a.qtrees[job - q * a.n_trees];
+        const QTree& t = a.qtrees[job - q * a.n_trees];
         const uint32_t index = (a.qidx[q] >> t.shift) & ((1u << t.log_height) - 1u);
         uint32_t* dst = ps + L.slots + (size_t)q * a.slot_words + t.slot_off;
         uint32_t off = 0;

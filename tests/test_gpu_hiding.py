@@ -105,6 +105,25 @@ def test_hiding_one_fill_per_stream_equals_piecewise_fills(p3, oracle, monkeypat
     whole.close(), pieces.close()
 
 
+@pytest.mark.parametrize("hash", ["poseidon2", "keccak"])
+def test_hiding_grind_search_continues_after_an_empty_first_range(p3, oracle, hash, monkeypatch):
+    """The proof-of-work continuation through the hiding prover (the query phase both provers share, prover.hip ProverCore):
+    a first range of 256 candidates against 12 proof-of-work bits at log_n = 9, past the one-launch sizes.  Every proof
+    equals the oracle's, and at least one witness lies past the first range."""
+    monkeypatch.setenv("P3HIP_GRIND_FIRST_LOG", "8")
+    gfp, ofp = _fp(p3, oracle, 1, 0, 12, 12)
+    kind = oracle.HASH_KECCAK if hash == "keccak" else oracle.HASH_POSEIDON2
+    pr = p3.FibAirProver(9, params=gfp, hash=hash, hiding=True, seed=1)
+    hit_continuation = False
+    for a in range(4):
+        proof = pr.prove(a, a + 1)
+        assert proof == oracle.prove_fib_air_hiding(a, a + 1, 9, ofp, hash=kind, seed=1)
+        witness = int(np.frombuffer(proof[-4:], np.uint32)[0])
+        hit_continuation |= int(oracle.from_monty(np.array([witness]))[0]) >= 256
+    assert hit_continuation, "no instance needed the continuation path: pick other instances"
+    pr.close()
+
+
 def test_hiding_batch_pool(p3, oracle):
     """The prover pool in the reference's hiding configuration: every proof equals the oracle's (the streams restart from
     the seed for every proof), through prove and through submit / collect."""
