@@ -39,6 +39,13 @@ __device__ __forceinline__ Magic pin_magic() {
 struct Uni { double npm1, pinv, fbias; };
 
 // a * b mod P for integers |b| < 2^51 / |a/P|, aP = a / P: |result| <= (1/2 + 2^-9) P
+// Largest |b| any input reaches: 2^B (P-1), the all-sum of a digit over a tile of P-1 words, which scale_by then multiplies by
+// the inter-digit twiddle or the coset scale; inside a digit, x - y = 2^(B-k) (P-1) for a tile holding P-1 at every 2^k-th
+// position.  tests/test_gpu_structured_inputs.py::test_narrow_f64_extreme_tiles (and .._headline_2_20_x_2) put both into every
+// digit: all-equal tiles from const(P-1) (K1), block(n2, P-1) (K2 inverse), coeff_comb(n1, (P+-1)/2) (K2 forward: products,
+// so centred, 2^B (P-1)/2) and coeff_block(n1, P-1) (K3); strided and part-filled tiles from the sweep of comb, block,
+// coeff_comb and coeff_block over every m (which input fills which tile: tests/test_structured_inputs_host.py).  Uniform
+// random words stay near 2^(B-1) P on the x + y chain.
 __device__ __forceinline__ double mulm(double a, double aP, double b, const Magic& k, double npm1) {
     const double qb = __fma_rn(b, aP, k.m);     // M + rint(ab / P)
     const double c = __fma_rn(qb, npm1, k.mp);  // M - q (P - 1), exact
@@ -50,12 +57,17 @@ __device__ __forceinline__ double mulm(double a, double aP, double b, const Magi
 __device__ __forceinline__ double canon(uint32_t monty) { return (double)bb::from_monty(monty); }
 
 // word of a value that came out of a product: |r| <= P/2 + 2^22
+// At +-(P-1)/2 and (P+1)/2 themselves, and at 0 and P-1: the coefficient families of test_narrow_f64_extreme_tiles, whose
+// scaled coefficients (K2's products) are exactly those words on a block or comb and exactly 0 elsewhere.
 __device__ __forceinline__ uint32_t word_centered(double r) {
     const uint32_t w = (uint32_t)(int32_t)r;
     return min(w, w + bb::P);
 }
 // word of any integer |x| < 2^43: q = rint(x / P - 1/2 + 2^-33) = floor(x / P) exactly (x / P is at least 2^-31 away
 // from the next integer unless it is one; the product and the fma round off by less than 2^-40), r = x - qP in [0, P)
+// Largest |x| any input reaches: K3's all-sum output of a tile of P-1 words, 2^B (P-1) < 2^41 (B <= 10), from
+// coeff_block(n1, P-1) in test_narrow_f64_extreme_tiles; the floor's margin case, x an exact multiple of P (x / P an integer,
+// results = 0), is what the delta, block and comb columns of the same test produce at shift 1 on every subgroup row outside the pattern.
 __device__ __forceinline__ uint32_t word_any(double x, const Uni& u) {
     const double q = __builtin_rint(__fma_rn(x, u.pinv, u.fbias));
     return (uint32_t)__fma_rn(q, -PD, x);
