@@ -152,6 +152,51 @@ const uint32_t *p3hip_mmcs_layer_dev(const p3hip_tree_t *tree, size_t layer, siz
 int p3hip_mmcs_open_batch(const p3hip_tree_t *tree, size_t index, uint32_t *rows_out, uint32_t *path_out,
                           void *stream);
 void p3hip_mmcs_free(p3hip_tree_t *tree);
+/* Mmcs::verify_batch (upstream p3_commit::Mmcs::verify_batch; the fourth method of the MMCS the reference passes into its PCS,
+ * native/src/fib_air.rs:40-51), either hash configuration (P3HIP_HASH_*).  HOST code, no GPU needed, like p3hip_verify_fib_air: the
+ * proof verifiers check their openings with it.  Returns 0 to accept, one of the positive codes below to reject (message via
+ * p3hip_take_last_error), P3HIP_ERR_BAD_ARG for a malformed call (a null pointer, n_mats 0 or above 64, a height that is no power
+ * of two, an unknown hash).  Mixed heights as MerkleTree::new injects them: the matrices of the tallest height form the leaf row,
+ * and after the compression at each level the rows of the matrices whose height equals that level's length are hashed and
+ * compressed in; matrix m contributes row index >> (log_max - log_h_m).  rows: the opened rows, sum(widths) words in matrix order;
+ * path: path_len x 8 words.  A HIDING tree is verified by listing every salt as a width-4 matrix of its matrix's height,
+ * interleaved m0, s0, m1, s1 ... — the order p3hip_mmcs_open_batch returns on such a tree. */
+#define P3HIP_MMCS_ROOT_MISMATCH 1   /* upstream MerkleTreeError::RootMismatch */
+#define P3HIP_MMCS_WRONG_HEIGHT  2   /* path_len != log2(tallest matrix) */
+#define P3HIP_MMCS_NOT_CANONICAL 3   /* an opened value >= P, or (Poseidon2 only) a digest word >= P */
+#define P3HIP_MMCS_BAD_INDEX     4   /* index >= tallest height */
+int p3hip_mmcs_verify_batch(int hash, const uint32_t root[8], const size_t *heights, const size_t *widths, size_t n_mats,
+                            size_t index, const uint32_t *rows, const uint32_t *path, size_t path_len);
+/* Mmcs::open_batch (fib_air.rs:40-51) for n indices in ONE launch, device to device: opening i is row_words words at d_rows + i *
+ * row_words (the rows of every matrix in matrix order, salts included on a hiding tree) and log_max_height x 8 words at d_paths +
+ * i * log_max_height * 8.  d_indices: n 32-bit words in device memory; an index is MASKED into the tree (index mod the tallest
+ * height), so whatever the buffer holds the gather stays inside the tree.  Enqueues only: no allocation, no copy to the host, no
+ * synchronise (it can be captured).  d_paths must be 16-byte aligned for p3hip_mmcs_verify_batch_many_dev. */
+size_t p3hip_mmcs_row_words(const p3hip_tree_t *tree);   /* sum of the widths, salts included on a hiding tree */
+int p3hip_mmcs_open_batch_many_dev(const p3hip_tree_t *tree, const uint32_t *d_indices, size_t n,
+                                   uint32_t *d_rows /* n x row_words */, uint32_t *d_paths /* n x log_max_height x 8 */, void *stream);
+/* Mmcs::verify_batch (upstream; fib_air.rs:40-51) for n openings of ONE commitment in one launch, in exactly the layout
+ * p3hip_mmcs_open_batch_many_dev writes: commit, open and verify chain on one stream with no host touch.  root, heights and widths
+ * are host memory, read before the call returns; d_status[i] = 0 or P3HIP_MMCS_ROOT_MISMATCH / _NOT_CANONICAL / _BAD_INDEX (the
+ * path length is given by the dimensions); *d_rejected (device word, may be null) = how many are nonzero.  Enqueues only, allocates
+ * nothing.  One opening per lane.  (A lane-cooperative form for small n exists — one opening per 16 lanes under Poseidon2, per wave
+ * under Keccak — but this entry does not take it until it has been timed against the per-lane form: DESIGN.md section 4.2, and the
+ * diagnostics below.)  Heights up to 2^31. */
+int p3hip_mmcs_verify_batch_many_dev(int hash, const uint32_t root[8] /* host, passed by value */,
+                                     const size_t *heights, const size_t *widths, size_t n_mats,
+                                     const uint32_t *d_indices, size_t n, const uint32_t *d_rows, const uint32_t *d_paths,
+                                     uint32_t *d_status /* n codes: 0 or P3HIP_MMCS_* */, uint32_t *d_rejected /* one word, may be null */,
+                                     void *stream);
+/* Diagnostics of the two kernel forms (no reference counterpart; tests and tools/mmcs_verify_bench.py time one form against the
+ * other, as p3hip_poseidon2_permute_variant_dev does for the two arithmetic forms).  The statuses never differ between forms.
+ *   _form_dev   p3hip_mmcs_verify_batch_many_dev with the form chosen by the caller: 0 = by n, as that entry does; 1 = one opening
+ *               per lane; 2 = cooperative (at most 2^24 openings);
+ *   _coop_max   the largest n that form 0 sends to the cooperative form, by hash and profile (P3HIP_PROFILE_*); 0 = the per-lane
+ *               form always (or an unknown hash / profile). */
+int p3hip_mmcs_verify_batch_many_form_dev(int form, int hash, const uint32_t root[8], const size_t *heights, const size_t *widths,
+                                          size_t n_mats, const uint32_t *d_indices, size_t n, const uint32_t *d_rows,
+                                          const uint32_t *d_paths, uint32_t *d_status, uint32_t *d_rejected, void *stream);
+size_t p3hip_mmcs_verify_coop_max(int hash, int profile);
 /* host-pointer convenience: uploads the matrices, commits, keeps its own device copies inside the tree */
 int p3hip_mmcs_commit(const uint32_t *const *mats, const size_t *heights, const size_t *widths,
                       size_t n_mats, uint32_t root_out[8], p3hip_tree_t **tree_out);

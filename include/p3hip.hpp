@@ -4,7 +4,7 @@
 //   GpuDft::{default, with_backend, dft_batch} + Plonky3's provided idft/coset methods     native/src/gpu_dft.rs:70-115
 //   RowMajorMatrix (p3_matrix::dense): row-major values + width
 //   benchmark_input / percentile_ms / generate_trace_rows                                   native/src/fib_air.rs:77-96,266-284
-//   MerkleTreeMmcs (Mmcs::commit / open_batch) and FibAirProver (prove)                      native/src/fib_air.rs:40-70
+//   MerkleTreeMmcs (Mmcs::commit / open_batch / verify_batch) and FibAirProver (prove)       native/src/fib_air.rs:40-70
 // Rust's `Result<_, String>` becomes p3hip::Error (thrown); there is NO CPU fallback here — the reference's
 // GpuDft falls back to Radix2DitParallel on Err (gpu_dft.rs:100-112); a C++ caller catches and decides.
 #pragma once
@@ -146,6 +146,37 @@ class MerkleTreeMmcs {  // Mmcs<BabyBear>: Poseidon2 hashes (north_star) or the 
         for (size_t w : t.widths_) { out.emplace_back(rows.begin() + off, rows.begin() + off + w); off += w; }
         path.resize(t.log_max_height() * 8);
         return {std::move(out), std::move(path)};
+    }
+    // Mmcs::verify_batch (host code): dims = (height, width) per matrix, rows = the opened rows in matrix order, path = the sibling
+    // digests.  true / false for accept / RootMismatch; every other reject throws Error with the library's message.
+    bool verify_batch(const std::vector<uint32_t>& root, const std::vector<std::pair<size_t, size_t>>& dims, size_t index,
+                      const std::vector<std::vector<uint32_t>>& opened_values, const std::vector<uint32_t>& path) const {
+        std::vector<size_t> hs, ws;
+        for (auto& d : dims) { hs.push_back(d.first); ws.push_back(d.second); }
+        std::vector<uint32_t> rows;
+        for (auto& v : opened_values) rows.insert(rows.end(), v.begin(), v.end());
+        if (root.size() != 8 || path.size() % 8) throw Error(P3HIP_ERR_BAD_ARG, "verify_batch: digests have 8 words");
+        rows.push_back(0);  // never a null pointer
+        const int rc = p3hip_mmcs_verify_batch(hash_, root.data(), hs.data(), ws.data(), dims.size(), index, rows.data(),
+                                               path.empty() ? rows.data() : path.data(), path.size() / 8);
+        if (rc == P3HIP_MMCS_ROOT_MISMATCH) { (void)p3hip_take_last_error(); return false; }
+        check(rc);
+        return true;
+    }
+    // the bulk, device-resident forms (thin wrappers: device pointers in and out, enqueue only)
+    size_t row_words(const MerkleTree& t) const { return p3hip_mmcs_row_words(t.h_); }
+    void open_batch_many_dev(const MerkleTree& t, const uint32_t* d_indices, size_t n, uint32_t* d_rows, uint32_t* d_paths,
+                             void* stream = nullptr) const {
+        check(p3hip_mmcs_open_batch_many_dev(t.h_, d_indices, n, d_rows, d_paths, stream));
+    }
+    void verify_batch_many_dev(const std::vector<uint32_t>& root, const std::vector<std::pair<size_t, size_t>>& dims, const uint32_t* d_indices,
+                               size_t n, const uint32_t* d_rows, const uint32_t* d_paths, uint32_t* d_status, uint32_t* d_rejected = nullptr,
+                               void* stream = nullptr) const {
+        std::vector<size_t> hs, ws;
+        for (auto& d : dims) { hs.push_back(d.first); ws.push_back(d.second); }
+        if (root.size() != 8) throw Error(P3HIP_ERR_BAD_ARG, "verify_batch_many: the root has 8 words");
+        check(p3hip_mmcs_verify_batch_many_dev(hash_, root.data(), hs.data(), ws.data(), dims.size(), d_indices, n, d_rows, d_paths, d_status,
+                                               d_rejected, stream));
     }
 
   private:

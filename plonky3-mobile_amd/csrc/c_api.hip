@@ -425,6 +425,45 @@ int p3hip_mmcs_open_batch(const p3hip_tree_t* tree, size_t index, uint32_t* rows
         return mmcs_open((hipStream_t)stream, *tree->t, index, rows_out, path_out);
     });
 }
+// Mmcs::verify_batch, host code (mmcs_verify.hip): no device context is touched
+int p3hip_mmcs_verify_batch(int hash, const uint32_t root[8], const size_t* heights, const size_t* widths, size_t n_mats, size_t index,
+                            const uint32_t* rows, const uint32_t* path, size_t path_len) {
+    return guarded([&]() -> int {
+        std::string why;
+        int rc = mmcs_verify_batch(hash, root, heights, widths, n_mats, index, rows, path, path_len, &why);
+        if (rc != 0) set_error(why);
+        return rc;
+    });
+}
+size_t p3hip_mmcs_row_words(const p3hip_tree_t* tree) { return tree ? mmcs_row_words(*tree->t) : 0; }
+int p3hip_mmcs_open_batch_many_dev(const p3hip_tree_t* tree, const uint32_t* d_indices, size_t n, uint32_t* d_rows, uint32_t* d_paths,
+                                   void* stream) {
+    return guarded([&]() -> int {
+        if (!tree) return fail(ERR_BAD_ARG, "mmcs_open_batch_many: null tree");
+        return mmcs_open_many((hipStream_t)stream, *tree->t, d_indices, n, d_rows, d_paths);
+    });
+}
+int p3hip_mmcs_verify_batch_many_form_dev(int form, int hash, const uint32_t root[8], const size_t* heights, const size_t* widths, size_t n_mats,
+                                          const uint32_t* d_indices, size_t n, const uint32_t* d_rows, const uint32_t* d_paths,
+                                          uint32_t* d_status, uint32_t* d_rejected, void* stream) {
+    return guarded([&]() -> int {
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        return mmcs_verify_many((hipStream_t)stream, hash, root, heights, widths, n_mats, d_indices, n, d_rows, d_paths, d_status, d_rejected,
+                                form, cx->profile);
+    });
+}
+int p3hip_mmcs_verify_batch_many_dev(int hash, const uint32_t root[8], const size_t* heights, const size_t* widths, size_t n_mats,
+                                     const uint32_t* d_indices, size_t n, const uint32_t* d_rows, const uint32_t* d_paths,
+                                     uint32_t* d_status, uint32_t* d_rejected, void* stream) {
+    return p3hip_mmcs_verify_batch_many_form_dev(MMCS_FORM_AUTO, hash, root, heights, widths, n_mats, d_indices, n, d_rows, d_paths, d_status,
+                                                 d_rejected, stream);
+}
+size_t p3hip_mmcs_verify_coop_max(int hash, int profile) {
+    if ((hash != HASH_POSEIDON2 && hash != HASH_KECCAK) || (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY)) return 0;
+    return mmcs_verify_coop_max(hash, profile == P3HIP_PROFILE_LATENCY ? PROFILE_LATENCY : PROFILE_THROUGHPUT);
+}
 void p3hip_mmcs_free(p3hip_tree_t* tree) {
     if (!tree) return;
     delete tree->t;

@@ -739,6 +739,30 @@ __global__ void open_gather_kernel(OpenArgs a, const uint32_t* layers, uint64_t 
     }
 }
 
+// The same gather for n indices, one workgroup (one wave) per index, rows and paths to their own packed arrays (the layout
+// mmcs_verify_many reads; query_gather_kernel of prover.hip is the model).  Masked: whatever the index buffer holds, the gather
+// stays inside the tree.
+__global__ void __launch_bounds__(64) open_gather_many_kernel(OpenArgs a, const uint32_t* layers, const uint32_t* indices, uint32_t row_words,
+                                                              uint32_t* rows, uint32_t* paths) {
+    if (gridDim.x <= 512u) P3_LATENCY_BOUND_KERNEL();
+    const uint64_t index = (uint64_t)indices[blockIdx.x] & ((1ull << a.log_max_height) - 1ull);
+    uint32_t* dst = rows + (size_t)blockIdx.x * row_words;
+    uint32_t off = 0;
+    for (uint32_t m = 0; m < a.n_mats; m++) {
+        const uint64_t r = index >> a.shift[m];
+        for (uint32_t c = threadIdx.x; c < a.width[m]; c += blockDim.x) dst[off + c] = a.mat[m][r * a.stride[m] + c];
+        off += a.width[m];
+    }
+    uint32_t* pdst = paths + (size_t)blockIdx.x * a.log_max_height * 8;
+    uint64_t base = 0, len = 1ull << a.log_max_height;
+    for (uint32_t i = 0; i < a.log_max_height; i++) {
+        const uint64_t sib = (index >> i) ^ 1;
+        if (threadIdx.x < 8) pdst[i * 8 + threadIdx.x] = layers[base + sib * 8 + threadIdx.x];
+        base += len * 8;
+        len >>= 1;
+    }
+}
+
 static RowSet make_rowset(const Tree& t, uint64_t h) {
     RowSet rs{};
     for (size_t m = 0; m < t.mats.size(); m++)
@@ -934,21 +958,30 @@ int mmcs_root(hipStream_t stream, const Tree& t, uint32_t root_out[8]) {
     return OK;
 }
 
-int mmcs_open(hipStream_t stream, const Tree& tc, uint64_t index, uint32_t* rows_out, uint32_t* path_out) {
-    Tree& t = const_cast<Tree&>(tc);
-    if (index >> t.log_max_height) return fail(ERR_BAD_ARG, "mmcs_open: index out of range");
-    if (!t.staging) P3_HIP(hipMalloc(reinterpret_cast<void**>(&t.staging), t.staging_words * 4));
+static OpenArgs make_open_args(const Tree& t) {
     OpenArgs a{};
     a.n_mats = (uint32_t)t.mats.size();
     a.log_max_height = t.log_max_height;
-    size_t row_words = 0;
     for (size_t m = 0; m < t.mats.size(); m++) {
         a.mat[m] = t.mats[m];
         a.width[m] = (uint32_t)t.widths[m];
         a.stride[m] = (uint32_t)t.strides[m];
         a.shift[m] = t.log_max_height - log2u(t.heights[m]);
-        row_words += t.widths[m];
     }
+    return a;
+}
+size_t mmcs_row_words(const Tree& t) {
+    size_t row_words = 0;
+    for (size_t w : t.widths) row_words += w;
+    return row_words;
+}
+
+int mmcs_open(hipStream_t stream, const Tree& tc, uint64_t index, uint32_t* rows_out, uint32_t* path_out) {
+    Tree& t = const_cast<Tree&>(tc);
+    if (index >> t.log_max_height) return fail(ERR_BAD_ARG, "mmcs_open: index out of range");
+    if (!t.staging) P3_HIP(hipMalloc(reinterpret_cast<void**>(&t.staging), t.staging_words * 4));
+    const OpenArgs a = make_open_args(t);
+    const size_t row_words = mmcs_row_words(t);
     hipLaunchKernelGGL(open_gather_kernel, dim3(1), dim3(64), 0, stream, a, t.layers, index, t.staging);
     P3_HIP(hipGetLastError());
     std::vector<uint32_t> host(row_words + (size_t)t.log_max_height * 8);
@@ -958,6 +991,18 @@ int mmcs_open(hipStream_t stream, const Tree& tc, uint64_t index, uint32_t* rows
     }
     if (row_words) memcpy(rows_out, host.data(), row_words * 4);
     if (t.log_max_height) memcpy(path_out, host.data() + row_words, (size_t)t.log_max_height * 32);
+    return OK;
+}
+
+int mmcs_open_many(hipStream_t stream, const Tree& t, const uint32_t* d_indices, size_t n, uint32_t* d_rows, uint32_t* d_paths) {
+    const size_t row_words = mmcs_row_words(t);
+    if (n > 0x7fffffffull) return fail(ERR_BAD_ARG, "mmcs_open_batch_many: more than 2^31 - 1 indices");
+    if (row_words > 0xffffffffull) return fail(ERR_BAD_ARG, "mmcs_open_batch_many: row too wide");
+    if (n && (!d_indices || (row_words && !d_rows) || (t.log_max_height && !d_paths))) return fail(ERR_BAD_ARG, "mmcs_open_batch_many: null argument");
+    if (!n) return OK;
+    hipLaunchKernelGGL(open_gather_many_kernel, dim3((uint32_t)n), dim3(64), 0, stream, make_open_args(t), t.layers, d_indices, (uint32_t)row_words,
+                       d_rows, d_paths);
+    P3_HIP(hipGetLastError());
     return OK;
 }
 

@@ -28,25 +28,12 @@ struct Reader {
     void digests(int hash, uint32_t* w, size_t n) { if (hash == HASH_POSEIDON2) felts(w, 8 * n); else for (size_t i = 0; i < 8 * n; i++) w[i] = u32(); }
 };
 
-void hash_row(const uint32_t* items, size_t n, uint32_t out[8]) {  // PaddingFreeSponge<_, 16, 8, 8>
-    uint32_t st[16] = {0};
-    for (size_t i = 0; i < n; i += 8) { size_t take = n - i < 8 ? n - i : 8; memcpy(st, items + i, take * 4); p2::permute(st); }
-    memcpy(out, st, 32);
-}
-void compress(const uint32_t* l, const uint32_t* r, uint32_t out[8]) {  // TruncatedPermutation<_, 2, 8, 16>
-    uint32_t st[16]; memcpy(st, l, 32); memcpy(st + 8, r, 32); p2::permute(st); memcpy(out, st, 32);
-}
-// MerkleTreeMmcs::verify_batch: the leaf row (every opened matrix's values, each followed by its salt under the hiding MMCS) up the path
+// MerkleTreeMmcs::verify_batch (mmcs_verify.hip) of ONE matrix of 2^depth rows: the leaf row (every opened matrix's values, each followed by
+// its salt under the hiding MMCS, all of one height) up the path.  Words are hashed as they are: the Reader flags a word >= P (rd.bad),
+// and which reject code such a proof gets is this file's business, unchanged.
 bool verify_opening(int hash, const uint32_t root[8], size_t index, const uint32_t* row, size_t width, const uint32_t* path, unsigned depth) {
-    uint32_t cur[8], nxt[8];
-    auto cmp = hash == HASH_KECCAK ? keccak_compress_host : compress;
-    if (hash == HASH_KECCAK) keccak_hash_row_host(row, width, cur); else hash_row(row, width, cur);
-    for (unsigned l = 0; l < depth; l++) {
-        const uint32_t* sib = path + 8 * (size_t)l;
-        if ((index >> l) & 1) cmp(sib, cur, nxt); else cmp(cur, sib, nxt);
-        memcpy(cur, nxt, 32);
-    }
-    return memcmp(cur, root, 32) == 0;
+    const size_t height = (size_t)1 << depth;
+    return mmcs_verify_batch(hash, root, &height, &width, 1, index, row, path, depth, nullptr, false) == 0;
 }
 size_t rev_bits_host(size_t x, unsigned bits) { size_t y = 0; for (unsigned i = 0; i < bits; i++) { y = (y << 1) | (x & 1); x >>= 1; } return y; }
 

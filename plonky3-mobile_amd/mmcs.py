@@ -1,8 +1,10 @@
 """Host-side mirror of Plonky3's Mmcs contract: MerkleTreeMmcs over either hash configuration —
 "poseidon2" (north_star: Poseidon2 sponge 16/8/8 + TruncatedPermutation, digest 8 field elements) or "keccak"
 (what the reference itself wires at native/src/fib_air.rs:28-51: PaddingFreeSponge<KeccakF,25,17,4> behind
-SerializingHasher + CompressionFunctionFromHasher, digest [u64;4]; non-hiding).  commit / open_batch /
-get_matrices keep everything device-resident; verify_batch is the verifier's job and lives in the test oracle."""
+SerializingHasher + CompressionFunctionFromHasher, digest [u64;4]), plain or hiding.  All four methods are here: commit /
+open_batch / get_matrices keep everything device-resident; verify_batch is host code of the library (p3hip_mmcs_verify_batch: what
+the proof verifiers run on their openings); open_batch_many / verify_batch_many open and verify n indices of one commitment in one
+launch each, device to device."""
 import ctypes as C
 
 import numpy as np
@@ -122,6 +124,83 @@ class MerkleTreeMmcs:
         return out, path[: tree.log_max_height].copy()
 
 
+    # ---- Mmcs::verify_batch and the bulk, device-resident forms of both halves ----
+    @staticmethod
+    def _dims(dims):
+        n = len(dims)
+        return (C.c_size_t * n)(*[int(d[0]) for d in dims]), (C.c_size_t * n)(*[int(d[1]) for d in dims]), n
+
+    def _verify(self, root, dims, index, rows, path):
+        hs, ws, n = self._dims(dims)
+        root = np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        path = np.ascontiguousarray(path, dtype=np.uint32).reshape(-1, 8)
+        if root.size != 8 or rows.size != sum(int(d[1]) for d in dims):
+            raise ValueError("verify_batch: the root has 8 words and the opened values one row per matrix of dims")
+        rc = _lib.lib().p3hip_mmcs_verify_batch(self._kind, root.ctypes.data_as(C.c_void_p), hs, ws, n, int(index),
+                                                rows.ctypes.data_as(C.c_void_p), path.ctypes.data_as(C.c_void_p), path.shape[0])
+        if rc == 0:
+            return True
+        msg = _lib.take_last_error() or ""
+        if rc == ROOT_MISMATCH:
+            return False
+        if rc > 0:
+            raise ValueError(msg)
+        raise _lib.P3HipError(rc, msg)
+
+    def verify_batch(self, root, dims, index, opened_values, proof):
+        """Mmcs::verify_batch: dims = [(height, width)] per matrix, opened_values = the opened row of every matrix, proof = the
+        sibling path (log_max_height, 8).  True / False for accept / RootMismatch; the other rejects (wrong path length, a word
+        that is no canonical field element, an index outside the tree) raise ValueError with the library's message."""
+        rows = np.concatenate([np.asarray(v, dtype=np.uint32).reshape(-1) for v in opened_values]) if len(opened_values) else np.zeros(0, np.uint32)
+        return self._verify(root, dims, index, rows, proof)
+
+    def _open_many(self, indices, tree):
+        import torch
+        L = _lib.lib()
+        idx = indices.contiguous() if _is_torch(indices) else dev_u32(np.asarray(indices, dtype=np.uint32).reshape(-1))
+        assert idx.is_cuda and idx.element_size() == 4
+        n, depth, rw = idx.numel(), tree.log_max_height, L.p3hip_mmcs_row_words(tree._h)
+        rows = torch.empty((n, rw), dtype=torch.int32, device=idx.device)
+        paths = torch.empty((n, depth, 8), dtype=torch.int32, device=idx.device)
+        _lib.check(L.p3hip_mmcs_open_batch_many_dev(tree._h, C.c_void_p(idx.data_ptr()), n, C.c_void_p(rows.data_ptr()),
+                                                    C.c_void_p(paths.data_ptr()), _stream_ptr()))
+        return rows, paths
+
+    def open_batch_many(self, indices, tree):
+        """Mmcs::open_batch for n indices (a device int32 tensor, or anything numpy takes) in one launch -> device tensors
+        rows [n, row_words] (matrix order) and paths [n, log_max_height, 8].  An index is masked into the tree."""
+        return self._open_many(indices, tree)
+
+    def _verify_many(self, root, dims, indices, rows, paths, form=0, with_rejected=False):
+        import torch
+        hs, ws, nm = self._dims(dims)
+        root = np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+        assert root.size == 8
+        idx = indices.contiguous() if _is_torch(indices) else dev_u32(np.asarray(indices, dtype=np.uint32).reshape(-1))
+        rows, paths = rows.contiguous(), paths.contiguous()
+        n, rw = idx.numel(), sum(int(d[1]) for d in dims)
+        depth = max(int(d[0]) for d in dims).bit_length() - 1 if nm else 0
+        if rows.numel() != n * rw or paths.numel() != n * depth * 8 or rows.element_size() != 4 or paths.element_size() != 4:
+            raise ValueError("verify_batch_many: rows is [n, sum of the widths] and paths [n, log2 of the tallest height, 8], 32-bit words")
+        status = torch.empty(n, dtype=torch.int32, device=idx.device)
+        rejected = torch.empty(1, dtype=torch.int32, device=idx.device) if with_rejected else None  # the counter may be null
+        _lib.check(_lib.lib().p3hip_mmcs_verify_batch_many_form_dev(
+            int(form), self._kind, root.ctypes.data_as(C.c_void_p), hs, ws, nm, C.c_void_p(idx.data_ptr()), n, C.c_void_p(rows.data_ptr()),
+            C.c_void_p(paths.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(rejected.data_ptr()) if with_rejected else None, _stream_ptr()))
+        return (status, rejected) if with_rejected else status
+
+    def verify_batch_many(self, root, dims, indices, rows, paths, form=0, with_rejected=False):
+        """Mmcs::verify_batch for n openings of one commitment in one launch, in the layout open_batch_many returns -> a device
+        tensor of n codes (0 = accept, ROOT_MISMATCH, NOT_CANONICAL, BAD_INDEX); with_rejected: also the device word counting the
+        nonzero ones.  form: 0 = the library chooses by n, FORM_LANE / FORM_COOP force a kernel form (same codes)."""
+        return self._verify_many(root, dims, indices, rows, paths, form, with_rejected)
+
+
+ROOT_MISMATCH, WRONG_HEIGHT, NOT_CANONICAL, BAD_INDEX = 1, 2, 3, 4
+FORM_AUTO, FORM_LANE, FORM_COOP = 0, 1, 2
+
+
 class MerkleTreeHidingMmcs(MerkleTreeMmcs):
     """MerkleTreeHidingMmcs<.., SmallRng, .., SALT_ELEMS 4> (native/src/fib_air.rs:40-51): commit salts every matrix with
     draws from the MMCS's own rng (a DeviceRng: the stream lives in HBM); open_batch returns (values, (salts, siblings))."""
@@ -129,8 +208,19 @@ class MerkleTreeHidingMmcs(MerkleTreeMmcs):
 
     def __init__(self, hash="keccak", rng=None, seed=1):
         super().__init__(hash)
-        from .fib_air import DeviceRng
-        self.rng = rng or DeviceRng(seed)
+        self._rng, self._seed = rng, seed
+
+    @property
+    def rng(self):
+        """the MMCS's own rng, created on first use: verify_batch is host code and needs none"""
+        if self._rng is None:
+            from .fib_air import DeviceRng
+            self._rng = DeviceRng(self._seed)
+        return self._rng
+
+    @rng.setter
+    def rng(self, value):
+        self._rng = value
 
     def commit(self, mats):
         import torch
@@ -162,3 +252,49 @@ class MerkleTreeHidingMmcs(MerkleTreeMmcs):
             off += w + self.SALT_ELEMS
         assert len(vals) == n
         return vals, (salts, path[: tree.log_max_height].copy())
+
+    # the leaf layout of a hiding tree: every salt a width-4 matrix of its matrix's height, m0, s0, m1, s1 ...
+    def _salted_dims(self, dims):
+        out = []
+        for h, w in dims:
+            out += [(h, w), (h, self.SALT_ELEMS)]
+        return out
+
+    def _columns(self, widths):
+        """positions of the value words and of the salt words inside an interleaved row"""
+        vals, salts, off = [], [], 0
+        for w in widths:
+            vals += range(off, off + w)
+            salts += range(off + w, off + w + self.SALT_ELEMS)
+            off += w + self.SALT_ELEMS
+        return vals, salts
+
+    def verify_batch(self, root, dims, index, opened_values, proof):
+        """MerkleTreeHidingMmcs::verify_batch: proof = (salts, siblings) as open_batch returns it."""
+        salts, path = proof
+        parts = []
+        for v, s in zip(opened_values, salts):
+            parts += [np.asarray(v, dtype=np.uint32).reshape(-1), np.asarray(s, dtype=np.uint32).reshape(-1)]
+        if len(parts) != 2 * len(dims):
+            raise ValueError("verify_batch: one opened row and one salt per matrix of dims")
+        return self._verify(root, self._salted_dims(dims), index, np.concatenate(parts), path)
+
+    def open_batch_many(self, indices, tree):
+        """-> (values [n, sum of the widths], (salts [n, n_mats, SALT_ELEMS], paths [n, log_max_height, 8])), device tensors."""
+        import torch
+        rows, paths = self._open_many(indices, tree)
+        vc, sc = self._columns([m.shape[1] for m in tree.mats])
+        vi = torch.tensor(vc, dtype=torch.long, device=rows.device)
+        si = torch.tensor(sc, dtype=torch.long, device=rows.device)
+        return rows[:, vi].contiguous(), (rows[:, si].reshape(rows.shape[0], len(tree.mats), self.SALT_ELEMS).contiguous(), paths)
+
+    def verify_batch_many(self, root, dims, indices, values, proof, form=0, with_rejected=False):
+        """values / proof = (salts, paths) as open_batch_many returns them; dims = the matrices' own (height, width)."""
+        import torch
+        salts, paths = proof
+        vc, sc = self._columns([int(d[1]) for d in dims])
+        n = values.shape[0]
+        rows = torch.empty((n, len(vc) + len(sc)), dtype=values.dtype, device=values.device)
+        rows[:, torch.tensor(vc, dtype=torch.long, device=values.device)] = values.reshape(n, -1)
+        rows[:, torch.tensor(sc, dtype=torch.long, device=values.device)] = salts.reshape(n, -1)
+        return self._verify_many(root, self._salted_dims(dims), indices, rows, paths, form, with_rejected)
