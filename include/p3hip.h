@@ -395,6 +395,39 @@ int p3hip_fib_prover_enqueue_trace_dev(p3hip_fib_prover_t *prover, const uint32_
 int p3hip_fib_batch_prove_traces_dev(p3hip_fib_batch_t *batch, size_t n, const uint32_t *const *d_traces, const uint32_t *pis,
                                      unsigned flags, const uint8_t **proofs_out, size_t *lens_out);
 
+/* ---- batches of proofs verified ON THE DEVICE: verify(&config, &FibonacciAir{}, &proof, &pis) (native/src/fib_air.rs:70-72,
+ * upstream p3_uni_stark::verify) for many proofs of ONE configuration at once — a pool's caller, a rank that gathers proofs, an
+ * aggregator.  p3hip_verify_fib_air_hash / _hiding (host, one proof) are the specification; DESIGN.md "device verifier".
+ * REJECT CODES.  status 0 = accept, exactly when the host verifier accepts the same bytes and public values.  Otherwise status is the
+ * host verifier's code H whenever H is 10 (OodEvaluationMismatch), 11 (InvalidPowWitness), 13 (commitment opening), 14 (FRI layer
+ * opening) or 15 (FinalPolyMismatch) and every field word of the proof is canonical: the first failure in the host's order.  In every
+ * other case — a wrong length, a count / width / length word that is not what the parameters dictate (the host's 1..9 and 12), a field
+ * word >= P anywhere in the proof, a public value >= P — status is P3HIP_VERIFY_MALFORMED: the device never follows a length word, so
+ * it does not tell these apart. ---- */
+typedef struct p3hip_fib_verifier p3hip_fib_verifier_t;
+#define P3HIP_VERIFY_MALFORMED 16
+/* fib_air.rs:70-72, p3_uni_stark::verify: the byte length every proof of this configuration has (DESIGN.md "proof bytes"); host only,
+ * no GPU touched.  Refuses the parameters the host verifiers refuse, with their messages. */
+int p3hip_fib_proof_len(int hash, int hiding, unsigned log_n, const p3hip_fri_params_t *params, size_t *len_out);
+/* fib_air.rs:70-72, p3_uni_stark::verify: a verifier of up to max_proofs proofs per call on the calling thread's current device, which
+ * it remembers (as trees and provers do).  Owns all scratch of the device entry, allocated here. */
+int p3hip_fib_verifier_create(int hash, int hiding, unsigned log_n, const p3hip_fri_params_t *params, size_t max_proofs,
+                              p3hip_fib_verifier_t **out);
+/* fib_air.rs:70-72, p3_uni_stark::verify: n <= max_proofs proofs in device memory, proof i at d_proofs + i * stride_bytes (d_proofs
+ * 4-byte aligned, stride a multiple of 4, >= p3hip_fib_proof_len); d_lens: n u32 byte lengths, or NULL = every proof has
+ * p3hip_fib_proof_len bytes (a proof of another length is rejected without being read); d_pis: n x 3 Montgomery words [a, b, x] (the
+ * convention of p3hip_fib_prover_prove_trace_dev); d_status: n codes; *d_rejected (may be NULL) = count of nonzero codes.  Enqueues
+ * only (four launches and one 4-byte memset on `stream`): no allocation, no host copy, no synchronise; can be captured.  One call at
+ * a time per verifier: the scratch is reused in stream order. */
+int p3hip_fib_verifier_verify_dev(p3hip_fib_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,
+                                  const uint32_t *d_pis, size_t n, uint32_t *d_status, uint32_t *d_rejected, void *stream);
+/* fib_air.rs:70-72, p3_uni_stark::verify: host convenience.  proofs[i] / lens[i]: host pointers (what p3hip_fib_batch_prove hands
+ * out), a / b / x as p3hip_verify_fib_air takes them (reduced mod P); uploads on a stream of the verifier's own (staging allocated by
+ * the first call), verifies, downloads status_out[n]; synchronises.  Splits n > max_proofs into several rounds itself. */
+int p3hip_fib_verifier_verify(p3hip_fib_verifier_t *v, size_t n, const uint8_t *const *proofs, const size_t *lens,
+                              const uint64_t *a, const uint64_t *b, const uint64_t *x, uint32_t *status_out);
+void p3hip_fib_verifier_destroy(p3hip_fib_verifier_t *v);
+
 /* ---- The reference's report-returning entry points (native/src/lib.rs:37-131 call fib_air::run_fib_air_zk /
  * fib_air::run_dft_benchmark and hand the returned String to Java).  Both write a NUL-terminated text of at most cap - 1 bytes
  * to out and return the length of the WHOLE text (snprintf convention); they never fail by status: a failure is text that

@@ -265,6 +265,44 @@ inline void verify_fib_air(const std::vector<uint8_t>& proof, uint64_t a, uint64
     p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
     check(p3hip_verify_fib_air_hash(hash, proof.data(), proof.size(), a, b, x, log_n, &c));
 }
+// verify(&config, &FibonacciAir{}, &proof, &pis) (fib_air.rs:71-72) for batches of proofs of one configuration, on the device
+// (p3hip.h "batches of proofs verified ON THE DEVICE": statuses 0, the host verifier's 10 / 11 / 13 / 14 / 15, or P3HIP_VERIFY_MALFORMED)
+inline size_t fib_proof_len(unsigned log_n, FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2, bool hiding = false) {
+    p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+    size_t len = 0;
+    check(p3hip_fib_proof_len(hash, hiding ? 1 : 0, log_n, &c, &len));
+    return len;
+}
+class FibVerifier {
+  public:
+    FibVerifier(unsigned log_n, FriParameters fp, int hash, bool hiding, size_t max_proofs) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        check(p3hip_fib_verifier_create(hash, hiding ? 1 : 0, log_n, &c, max_proofs, &h_));
+    }
+    FibVerifier(const FibVerifier&) = delete;
+    FibVerifier& operator=(const FibVerifier&) = delete;
+    ~FibVerifier() { p3hip_fib_verifier_destroy(h_); }
+    // proofs with their (a, b, x); one status per proof
+    std::vector<uint32_t> verify(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<uint64_t>& a,
+                                 const std::vector<uint64_t>& b, const std::vector<uint64_t>& x) {
+        const size_t n = proofs.size();
+        if (a.size() != n || b.size() != n || x.size() != n) throw Error(P3HIP_ERR_BAD_ARG, "FibVerifier: one (a, b, x) per proof");
+        std::vector<const uint8_t*> ptrs(n);
+        std::vector<size_t> lens(n);
+        for (size_t i = 0; i < n; i++) { ptrs[i] = proofs[i].data(); lens[i] = proofs[i].size(); }
+        std::vector<uint32_t> status(n);
+        check(p3hip_fib_verifier_verify(h_, n, ptrs.data(), lens.data(), a.data(), b.data(), x.data(), status.data()));
+        return status;
+    }
+    // device-resident proofs: enqueues on `stream`, nothing is waited for
+    void verify_dev(const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens, const uint32_t* d_pis, size_t n,
+                    uint32_t* d_status, uint32_t* d_rejected, void* stream) {
+        check(p3hip_fib_verifier_verify_dev(h_, d_proofs, stride_bytes, d_lens, d_pis, n, d_status, d_rejected, stream));
+    }
+
+  private:
+    p3hip_fib_verifier_t* h_ = nullptr;
+};
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"
 inline std::string run_fib_air(unsigned log_n = 3, uint64_t a = 0, uint64_t b = 1, FriParameters fp = FriParameters(),
                                int hash = P3HIP_HASH_POSEIDON2) {

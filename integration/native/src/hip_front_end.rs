@@ -28,6 +28,10 @@ struct FriParamsC {
 struct FibProverC {
     _opaque: [u8; 0],
 }
+#[repr(C)]
+struct FibVerifierC {
+    _opaque: [u8; 0],
+}
 const P3HIP_HASH_KECCAK: i32 = 1;
 
 // include/p3hip.h, "report-returning entry points" and "a CALLER's trace"
@@ -40,6 +44,15 @@ extern "C" {
                                     proof_out: *mut *const u8, proof_len: *mut usize) -> i32;
     fn p3hip_fib_prover_destroy(prover: *mut FibProverC);
     fn p3hip_take_last_error() -> *const c_char;
+    // "batches of proofs verified ON THE DEVICE": verify(&config, &FibonacciAir {}, &proof, pis) (fib_air.rs:71-72) for many proofs
+    fn p3hip_fib_proof_len(hash: i32, hiding: i32, log_n: u32, params: *const FriParamsC, len_out: *mut usize) -> i32;
+    fn p3hip_fib_verifier_create(hash: i32, hiding: i32, log_n: u32, params: *const FriParamsC, max_proofs: usize,
+                                 out: *mut *mut FibVerifierC) -> i32;
+    fn p3hip_fib_verifier_verify_dev(v: *mut FibVerifierC, d_proofs: *const u8, stride_bytes: usize, d_lens: *const u32,
+                                     d_pis: *const u32, n: usize, d_status: *mut u32, d_rejected: *mut u32, stream: *mut c_void) -> i32;
+    fn p3hip_fib_verifier_verify(v: *mut FibVerifierC, n: usize, proofs: *const *const u8, lens: *const usize, a: *const u64,
+                                 b: *const u64, x: *const u64, status_out: *mut u32) -> i32;
+    fn p3hip_fib_verifier_destroy(v: *mut FibVerifierC);
 }
 
 fn last_error() -> String {

@@ -114,6 +114,13 @@ _SIGS = {
     "p3hip_fib_prover_enqueue_trace_dev": (C.c_int, [C.c_void_p, C.c_void_p, u32p]),
     "p3hip_fib_batch_prove_traces_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), u32p, C.c_uint,
                                                    C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+    "p3hip_fib_proof_len": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "p3hip_fib_verifier_create": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "p3hip_fib_verifier_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "p3hip_fib_verifier_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
+    "p3hip_fib_verifier_destroy": (None, [C.c_void_p]),
     "p3hip_mmcs_commit": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                     C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
 }

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "mmcs.h"
 #include "prover.h"
+#include "verifier_dev.h"
 #include "rng.h"
 
 namespace p3 {
@@ -1116,4 +1117,44 @@ void p3hip_fib_batch_destroy(p3hip_fib_batch_t* bt) {
     delete bt;
 }
 
+}  // extern "C"
+
+// ---- batches of proofs verified on the device (verifier_dev.hip) ----
+struct p3hip_fib_verifier {
+    FibVerifierDev v;
+};
+extern "C" {
+int p3hip_fib_proof_len(int hash, int hiding, unsigned log_n, const p3hip_fri_params_t* params, size_t* len_out) {
+    return guarded([&]() -> int {
+        if (!params || !len_out) return fail(ERR_BAD_ARG, "fib_proof_len: null argument");
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        return fib_proof_len(hash, hiding != 0, log_n, fp, len_out);
+    });
+}
+int p3hip_fib_verifier_create(int hash, int hiding, unsigned log_n, const p3hip_fri_params_t* params, size_t max_proofs,
+                              p3hip_fib_verifier_t** out) {
+    return guarded([&]() -> int {
+        if (!params || !out) return fail(ERR_BAD_ARG, "fib_verifier_create: null argument");
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::unique_ptr<p3hip_fib_verifier> h(new p3hip_fib_verifier());
+        if (int rc = h->v.init(hash, hiding != 0, log_n, fp, max_proofs)) return rc;
+        *out = h.release();
+        return OK;
+    });
+}
+int p3hip_fib_verifier_verify_dev(p3hip_fib_verifier_t* v, const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens,
+                                  const uint32_t* d_pis, size_t n, uint32_t* d_status, uint32_t* d_rejected, void* stream) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "fib_verifier_verify_dev: null verifier");
+        return v->v.verify_dev(d_proofs, stride_bytes, d_lens, d_pis, n, d_status, d_rejected, static_cast<hipStream_t>(stream));
+    });
+}
+int p3hip_fib_verifier_verify(p3hip_fib_verifier_t* v, size_t n, const uint8_t* const* proofs, const size_t* lens, const uint64_t* a,
+                              const uint64_t* b, const uint64_t* x, uint32_t* status_out) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "fib_verifier_verify: null verifier");
+        return v->v.verify_host(n, proofs, lens, a, b, x, status_out);
+    });
+}
+void p3hip_fib_verifier_destroy(p3hip_fib_verifier_t* v) { delete v; }
 }  // extern "C"

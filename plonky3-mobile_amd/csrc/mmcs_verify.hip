@@ -134,6 +134,8 @@ __device__ __forceinline__ void count_rejected(bool rejected, uint32_t* d_reject
     if (d_rejected && b && (threadIdx.x & 63u) == 0u) atomicAdd(d_rejected, (uint32_t)__builtin_popcountll(b));
 }
 
+// (verifier_dev.hip lane_open_mismatch<> restates the two per-lane walks below for ONE height class and 4-byte-aligned paths read out
+// of proof bytes: a fix to the absorb, the reduce after a permutation or the last-block digest form belongs in both files.)
 // ---- per lane, Poseidon2 (fp64) ----
 __global__ void __launch_bounds__(256) verify_lane_p2_kernel(VerifySched a, const uint32_t* indices, uint64_t n, const uint32_t* rows,
                                                              const uint32_t* paths, uint32_t* status, uint32_t* d_rejected) {

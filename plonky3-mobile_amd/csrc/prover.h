@@ -88,5 +88,7 @@ int verify_fib_air(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_
 // the verifier of hiding proofs (wire format version 2)
 int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
                           const FriParams& fp, std::string* why, int hash);
+// the parameter gates of the two verifiers above (0, or ERR_BAD_ARG with the format's message in *why)
+int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriParams& fp, std::string* why);
 
 }  // namespace p3

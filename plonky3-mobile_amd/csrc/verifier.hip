@@ -155,12 +155,19 @@ struct FriCheck {
 
 }  // namespace
 
+// check_parameters for either wire format, with that format's own messages (the device verifier refuses what these refuse)
+int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriParams& fp, std::string* why) {
+    if (hiding)
+        return check_parameters(hash, log_n, log_n + 1, fp, why, "bad parameters: LDE height outside the two-adic subgroup",
+                                "bad parameters: log_final_poly_len must be below the randomized trace's log height");
+    return check_parameters(hash, log_n, log_n, fp, why, "bad parameters: LDE height outside [2^2, 2^27]",
+                            "bad parameters: log_final_poly_len must be below the trace's log height");
+}
+
 // 0 = accept; otherwise a positive code naming the failed check (same numbering as the error strings below).
 int verify_fib_air(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
                    const FriParams& fp, std::string* why, int hash) {
-    if (int rc = check_parameters(hash, log_n, log_n, fp, why, "bad parameters: LDE height outside [2^2, 2^27]",
-                                  "bad parameters: log_final_poly_len must be below the trace's log height"))
-        return rc;
+    if (int rc = verify_check_parameters(hash, false, log_n, fp, why)) return rc;
     Reader rd{proof, len};
     const uint32_t log_big = log_n + fp.log_blowup;
     const uint64_t n = 1ull << log_n;
@@ -258,9 +265,7 @@ static_assert(VH_CH <= MAX_MATS && VH_SALT <= MAX_SALT && VH_CH * (VH_D + VH_SAL
 int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
                           const FriParams& fp, std::string* why, int hash) {
     const uint32_t log_ext = log_n + 1, log_big = log_ext + fp.log_blowup;
-    if (int rc = check_parameters(hash, log_n, log_ext, fp, why, "bad parameters: LDE height outside the two-adic subgroup",
-                                  "bad parameters: log_final_poly_len must be below the randomized trace's log height"))
-        return rc;
+    if (int rc = verify_check_parameters(hash, true, log_n, fp, why)) return rc;
     Reader rd{proof, len};
     const uint64_t h = 1ull << log_n;
     const uint32_t gen = bb::to_monty(bb::GEN);

@@ -484,3 +484,85 @@ class FibAirBatchProver:
             self.close()
         except Exception:
             pass
+
+
+VERIFY_MALFORMED = 16  # include/p3hip.h P3HIP_VERIFY_MALFORMED
+
+
+def proof_len(log_n, params=None, hash="poseidon2", hiding=False):
+    """p3hip_fib_proof_len: the byte length every proof of this configuration has; host only."""
+    params = params or FriParameters()
+    out = C.c_size_t()
+    _lib.check(_lib.lib().p3hip_fib_proof_len(_hash_kind(hash), 1 if hiding else 0, log_n, C.cast(params._c(), C.c_void_p), C.byref(out)))
+    return out.value
+
+
+class FibAirVerifier:
+    """verify(&config, &FibonacciAir{}, &proof, &pis) (fib_air.rs:71-72) for batches of proofs of ONE configuration, on the device
+    (include/p3hip.h "batches of proofs verified ON THE DEVICE").  Statuses: 0 = accept, the host verifier's codes 10 / 11 / 13 / 14 / 15,
+    or VERIFY_MALFORMED."""
+
+    def __init__(self, log_n, params=None, hash="poseidon2", hiding=False, max_proofs=64):
+        self.params = params or FriParameters()
+        self.log_n, self.hash, self.hiding, self.max_proofs = log_n, hash, hiding, max_proofs
+        self.proof_len = proof_len(log_n, self.params, hash, hiding)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p3hip_fib_verifier_create(_hash_kind(hash), 1 if hiding else 0, log_n, C.cast(self.params._c(), C.c_void_p),
+                                                        max_proofs, C.byref(self._h)))
+
+    def verify_many(self, proofs, instances):
+        """proofs: a list of bytes; instances: a list of (a, b, x) canonical ints.  Returns a numpy uint32 array of statuses; batches
+        larger than max_proofs are split."""
+        import numpy as np
+        n = len(proofs)
+        if len(instances) != n:
+            raise ValueError("one (a, b, x) per proof")
+        status = np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return status
+        ptrs = (C.c_char_p * n)(*[bytes(p) for p in proofs])
+        lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+        a = (C.c_uint64 * n)(*[i[0] for i in instances])
+        b = (C.c_uint64 * n)(*[i[1] for i in instances])
+        x = (C.c_uint64 * n)(*[i[2] for i in instances])
+        _lib.check(_lib.lib().p3hip_fib_verifier_verify(self._h, n, ptrs, lens, a, b, x, status.ctypes.data_as(_lib.u32p)))
+        return status
+
+    def verify_many_dev(self, proofs, pis, lens=None, status=None, rejected=None, n=None, stride=None):
+        """The device entry on torch tensors, enqueued on torch's current stream and not synchronised.  proofs: a contiguous uint8 /
+        int32 device tensor, proof i at byte i * stride (default: the row length of a 2-d tensor); pis: (n, 3) 32-bit Montgomery
+        words; lens: n 32-bit byte lengths or None.  Returns (status, rejected): int32 device tensors of n codes and one count."""
+        import torch
+        if n is None:
+            n = pis.shape[0]
+        if stride is None:
+            stride = proofs.stride(0) * proofs.element_size() if proofs.dim() == 2 else self.proof_len
+        for t in (proofs, pis) + ((lens,) if lens is not None else ()):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("expected contiguous device tensors")
+        if pis.dtype not in (torch.int32, torch.uint32) or pis.numel() < 3 * n:
+            raise ValueError("pis: n x 3 32-bit Montgomery words")
+        if n and proofs.numel() * proofs.element_size() < (n - 1) * stride + self.proof_len:
+            raise ValueError("the proofs tensor is shorter than n proofs")
+        if lens is not None and (lens.dtype not in (torch.int32, torch.uint32) or lens.numel() < n):
+            raise ValueError("lens: n 32-bit byte lengths")
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=proofs.device)
+        if rejected is None:
+            rejected = torch.empty(1, dtype=torch.int32, device=proofs.device)
+        _lib.check(_lib.lib().p3hip_fib_verifier_verify_dev(self._h, C.c_void_p(proofs.data_ptr()), stride,
+                                                            C.c_void_p(lens.data_ptr()) if lens is not None else None,
+                                                            C.c_void_p(pis.data_ptr()), n, C.c_void_p(status.data_ptr()),
+                                                            C.c_void_p(rejected.data_ptr()), _stream_ptr()))
+        return status[:n], rejected
+
+    def close(self):
+        if self._h:
+            _lib.lib().p3hip_fib_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
