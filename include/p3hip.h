@@ -438,6 +438,64 @@ void p3hip_fib_verifier_destroy(p3hip_fib_verifier_t *v);
  * host: "fib_air zk ok (n=8, x=21)" (fib_air.rs:74) or "fib_air zk failed: <check>".  Honours the selector: with a backend other
  * than "hip" selected nothing is run and the text says so (fib_air.rs:60 hard-codes Vulkan; see integration/native/src/fib_air.rs.patch). */
 int p3hip_run_fib_air_zk(char *out, size_t cap);
+
+/* ---- Fiat-Shamir on the host: the challengers a caller drives between PCS calls.  hash = P3HIP_HASH_POSEIDON2:
+ *      DuplexChallenger<BabyBear, Poseidon2-16, 16, 8>; P3HIP_HASH_KECCAK: SerializingChallenger32<BabyBear, HashChallenger<u8,
+ *      Keccak256Hash, 32>> (native/src/fib_air.rs:53).  Words are Montgomery words below P. ---- */
+typedef struct p3hip_challenger p3hip_challenger_t;
+int p3hip_challenger_create(int hash, p3hip_challenger_t **out);                                     /* ::new */
+int p3hip_challenger_observe(p3hip_challenger_t *c, const uint32_t *monty_words, size_t n);          /* CanObserve<F>::observe_slice */
+int p3hip_challenger_observe_digest(p3hip_challenger_t *c, const uint32_t digest[8]);                /* CanObserve<Hash<..>>::observe */
+int p3hip_challenger_sample_ext(p3hip_challenger_t *c, uint32_t out[4]);                             /* sample_algebra_element */
+int p3hip_challenger_sample_bits(p3hip_challenger_t *c, unsigned bits, uint32_t *out);               /* CanSampleBits::sample_bits, bits <= 30 */
+int p3hip_challenger_clone(const p3hip_challenger_t *c, p3hip_challenger_t **out);                   /* Clone */
+void p3hip_challenger_destroy(p3hip_challenger_t *c);
+
+/* ---- TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over CALLER-SUPPLIED matrices: the Pcs contract the reference
+ *      hands to prove (HidingFriPcs::new(dft, val_mmcs, fri_params, ..), native/src/fib_air.rs:62-65), NON-HIDING, for either hash
+ *      configuration and either profile.  DESIGN.md section 5.2.
+ *      Scope: every matrix that takes part in one open / verify has the same height h = 2^log_h, 1 <= log_h and log_h + log_blowup
+ *      <= 26 — what p3_uni_stark produces for any AIR (trace, preprocessed trace, quotient chunks).  Mixed heights are refused with
+ *      P3HIP_ERR_BAD_ARG and a message naming the matrix.  Capacities (larger inputs are refused by name, never truncated): 8 matrices
+ *      per commitment, 4 commitments ("rounds") per open, 4 distinct opening points per open, 8192 batched columns (the sum of width
+ *      over every (matrix, point) pair; also the widest single matrix).  The FRI parameter gates are the fib prover's with log_h for
+ *      the trace's log height.  An opening point on the LDE coset GENERATOR * <g_big> (a base-field z with (z / GENERATOR)^big = 1:
+ *      upstream panics on the zero denominator) is refused on the host before anything is launched, naming round, matrix and point.
+ *      Not covered: HidingFriPcs, mixed heights, a device batch verifier. ---- */
+typedef struct p3hip_pcs p3hip_pcs_t;
+typedef struct p3hip_pcs_data p3hip_pcs_data_t;
+/* TwoAdicFriPcs::new(dft, mmcs, fri_params); stream / own_stream as p3hip_fib_prover_create */
+int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t *params, void *stream, int own_stream, p3hip_pcs_t **out);
+/* Pcs::commit: d_evals[m] = heights[m] x widths[m] evaluations (device memory, read in place) over domain_shifts[m] * <g_h> in
+ * natural row order.  The LDE is coset_lde_batch(evals, log_blowup, GENERATOR / shift), bit-reversed by row; one Merkle tree covers
+ * the LDEs of the call, in input order.  The prover data owns the LDEs.  One synchronisation: the root read-back. */
+int p3hip_pcs_commit_dev(p3hip_pcs_t *pcs, const uint32_t *const *d_evals, const size_t *heights, const size_t *widths,
+                         const uint32_t *domain_shifts /* Montgomery, NULL = all 1 */, size_t n_mats,
+                         uint32_t root_out[8], p3hip_pcs_data_t **data_out);
+/* Pcs::get_evaluations_on_domain: the stored LDE of matrix `mat` (*height = h << log_blowup rows in HBM, no copy, no launch).  The
+ * evaluations over the disjoint coset GENERATOR * <g_m>, h <= m <= *height, are its first m rows: natural index i at row bitrev(i, log m). */
+int p3hip_pcs_lde_dev(const p3hip_pcs_data_t *data, size_t mat, const uint32_t **d_lde, size_t *height, size_t *width);
+/* Pcs::open.  points_per_mat: one count per matrix, round -> matrix; points: 4 Montgomery words each, round -> matrix -> point.
+ * opened_out: every opened value (4 words) in the order they are observed, round -> matrix -> point -> column.  *proof_out: the
+ * FriProof section of the wire format (DESIGN.md "proof bytes": from the count of commit-phase roots through the witness; each
+ * query's input_proof carries one BatchOpening per round, in round order), valid until the next open / destroy.  challenger: in, the
+ * transcript before the open; out, the transcript after the last query index (unchanged when the call fails).  One synchronisation. */
+int p3hip_pcs_open(p3hip_pcs_t *pcs, const p3hip_pcs_data_t *const *rounds, size_t n_rounds,
+                   const size_t *points_per_mat, const uint32_t *points /* 4 words each, round -> matrix -> point */,
+                   p3hip_challenger_t *challenger /* in: state before the open; out: state after the last query */,
+                   uint32_t *opened_out, size_t opened_cap_words, const uint8_t **proof_out, size_t *proof_len);
+/* Pcs::verify, host code.  roots: 8 words per round; mats_per_round / widths / points_per_mat / points / opened as for open.
+ * Returns P3HIP_OK with *reject_code = 0 to accept, or = the failed check (the numbering of p3hip_verify_fib_air's FRI half: 5 commit
+ * phase length, 6 query count, 7 final polynomial length, 8 trailing or missing bytes, 9 truncated, 11 InvalidPowWitness, 12 query
+ * shape, 13 input opening, 14 FRI layer opening, 15 FinalPolyMismatch; message via p3hip_take_last_error) with the challenger where
+ * the verifier stopped; P3HIP_ERR_BAD_ARG for a refused argument (challenger unchanged). */
+int p3hip_pcs_verify(int hash, const p3hip_fri_params_t *params, unsigned log_h, const uint32_t *roots /* 8 per round */,
+                     const size_t *mats_per_round, const size_t *widths, size_t n_rounds, const size_t *points_per_mat,
+                     const uint32_t *points, const uint32_t *opened, const uint8_t *proof, size_t len,
+                     p3hip_challenger_t *challenger, int *reject_code);
+void p3hip_pcs_data_free(p3hip_pcs_data_t *d);
+void p3hip_pcs_destroy(p3hip_pcs_t *pcs);
+
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */
 typedef int (*p3hip_cpu_dft_fn)(void *user, const uint32_t *in, uint32_t *out, size_t height, size_t width);

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
+#include <array>
 #include <string>
 #include <utility>
 #include <vector>
@@ -303,6 +304,96 @@ class FibVerifier {
   private:
     p3hip_fib_verifier_t* h_ = nullptr;
 };
+// The challengers a PCS caller drives (p3hip.h "Fiat-Shamir on the host"): DuplexChallenger (Poseidon2) or SerializingChallenger32 over a
+// Keccak-256 HashChallenger.  Field elements are Montgomery words.
+class Challenger {
+  public:
+    explicit Challenger(int hash = P3HIP_HASH_POSEIDON2) { check(p3hip_challenger_create(hash, &h_)); }
+    Challenger(const Challenger& o) { check(p3hip_challenger_clone(o.h_, &h_)); }
+    Challenger& operator=(const Challenger&) = delete;
+    ~Challenger() { p3hip_challenger_destroy(h_); }
+    void observe(const std::vector<uint32_t>& words) { check(p3hip_challenger_observe(h_, words.data(), words.size())); }
+    void observe_digest(const uint32_t digest[8]) { check(p3hip_challenger_observe_digest(h_, digest)); }
+    std::array<uint32_t, 4> sample_ext() { std::array<uint32_t, 4> e{}; check(p3hip_challenger_sample_ext(h_, e.data())); return e; }
+    uint32_t sample_bits(unsigned bits) { uint32_t v = 0; check(p3hip_challenger_sample_bits(h_, bits, &v)); return v; }
+    p3hip_challenger_t* handle() const { return h_; }
+
+  private:
+    p3hip_challenger_t* h_ = nullptr;
+};
+// TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over caller matrices in device memory (p3hip.h; non-hiding, one
+// height per open).  Points are 4 Montgomery words each, round -> matrix -> point; opened values come back in observation order.
+class TwoAdicFriPcs {
+  public:
+    struct ProverData {  // Pcs::ProverData: the LDEs in HBM and their tree
+        p3hip_pcs_data_t* h = nullptr;
+        std::array<uint32_t, 8> root{};
+        ProverData() = default;
+        ProverData(ProverData&& o) noexcept : h(o.h), root(o.root) { o.h = nullptr; }
+        ProverData(const ProverData&) = delete;
+        ProverData& operator=(const ProverData&) = delete;
+        ~ProverData() { p3hip_pcs_data_free(h); }
+    };
+    struct Opening {
+        std::vector<uint32_t> opened;  // 4 words per value
+        std::vector<uint8_t> proof;    // the FriProof section of the wire format
+    };
+    explicit TwoAdicFriPcs(FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2, int profile = P3HIP_PROFILE_LATENCY,
+                           void* stream = nullptr, bool own_stream = true)
+        : fp_(fp), hash_(hash) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        check(p3hip_pcs_create(profile, hash, &c, stream, own_stream ? 1 : 0, &h_));
+    }
+    TwoAdicFriPcs(const TwoAdicFriPcs&) = delete;
+    TwoAdicFriPcs& operator=(const TwoAdicFriPcs&) = delete;
+    ~TwoAdicFriPcs() { p3hip_pcs_destroy(h_); }
+    // Pcs::commit: evaluations over shifts[m] * <g_h>, natural row order (shifts empty: all 1)
+    ProverData commit(const std::vector<const uint32_t*>& d_evals, const std::vector<size_t>& heights, const std::vector<size_t>& widths,
+                      const std::vector<uint32_t>& shifts = {}) {
+        if (heights.size() != d_evals.size() || widths.size() != d_evals.size() || (!shifts.empty() && shifts.size() != d_evals.size()))
+            throw Error(P3HIP_ERR_BAD_ARG, "TwoAdicFriPcs::commit: one height, width and shift per matrix");
+        ProverData d;
+        check(p3hip_pcs_commit_dev(h_, d_evals.data(), heights.data(), widths.data(), shifts.empty() ? nullptr : shifts.data(), d_evals.size(),
+                                   d.root.data(), &d.h));
+        return d;
+    }
+    // Pcs::get_evaluations_on_domain: the stored LDE (a pointer into HBM); the coset GENERATOR * <g_m> is its first m rows, bit-reversed
+    const uint32_t* lde(const ProverData& d, size_t mat, size_t* height, size_t* width) const {
+        const uint32_t* p = nullptr;
+        check(p3hip_pcs_lde_dev(d.h, mat, &p, height, width));
+        return p;
+    }
+    // Pcs::open; opened_words = 4 x the batched columns (sum of width over every (matrix, point) pair)
+    Opening open(const std::vector<const ProverData*>& rounds, const std::vector<size_t>& points_per_mat, const std::vector<uint32_t>& points,
+                 Challenger& challenger, size_t opened_words) {
+        std::vector<const p3hip_pcs_data_t*> hs;
+        for (const ProverData* r : rounds) hs.push_back(r ? r->h : nullptr);
+        Opening o;
+        o.opened.resize(opened_words);
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_pcs_open(h_, hs.data(), hs.size(), points_per_mat.data(), points.data(), challenger.handle(), o.opened.data(), o.opened.size(),
+                             &p, &n));
+        o.proof.assign(p, p + n);
+        return o;
+    }
+    // Pcs::verify (host): 0 = accept, otherwise the failed check's code (message via take_last_error); throws on a refused argument
+    int verify(unsigned log_h, const std::vector<uint32_t>& roots, const std::vector<size_t>& mats_per_round, const std::vector<size_t>& widths,
+               const std::vector<size_t>& points_per_mat, const std::vector<uint32_t>& points, const std::vector<uint32_t>& opened,
+               const std::vector<uint8_t>& proof, Challenger& challenger) const {
+        p3hip_fri_params_t c{fp_.log_blowup, fp_.log_final_poly_len, fp_.num_queries, fp_.proof_of_work_bits};
+        int code = 0;
+        check(p3hip_pcs_verify(hash_, &c, log_h, roots.data(), mats_per_round.data(), widths.data(), mats_per_round.size(), points_per_mat.data(),
+                               points.data(), opened.data(), proof.data(), proof.size(), challenger.handle(), &code));
+        return code;
+    }
+
+  private:
+    p3hip_pcs_t* h_ = nullptr;
+    FriParameters fp_;
+    int hash_;
+};
+
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"
 inline std::string run_fib_air(unsigned log_n = 3, uint64_t a = 0, uint64_t b = 1, FriParameters fp = FriParameters(),
                                int hash = P3HIP_HASH_POSEIDON2) {

@@ -1,0 +1,339 @@
+// NEVER COMPILED HERE (no Rust toolchain in the build image; p3-* 0.4.2 path dependencies absent).
+//
+// native/src/hip_pcs.rs — `HipPcs`: the `Pcs<Challenge, Challenger>` the reference builds at native/src/fib_air.rs:62-65, with
+// commit / get_evaluations_on_domain / open on the device (libp3hip's TwoAdicFriPcs over caller matrices: include/p3hip.h
+// "TwoAdicFriPcs over CALLER-SUPPLIED matrices") and verify on the host.  NON-HIDING (TwoAdicFriPcs, not HidingFriPcs); every matrix
+// of one open has the same height, which is what p3_uni_stark hands a PCS (trace, preprocessed trace, quotient chunks).
+//
+//     let pcs = HipPcs::keccak(fri_params);        // the reference's hashes (fib_air.rs:28-53)
+//     let pcs = HipPcs::poseidon2(fri_params);     // north_star's configuration
+//
+// The Fiat-Shamir transcript lives in a `HipChallenger` (p3hip_challenger_*): the library hands it to the device for the open and
+// back, so it must be the library's own object; it implements the p3-challenger traits uni-stark uses by forwarding.
+// Trait shapes are those of p3-commit / p3-challenger 0.4.2 as recalled (the crates are not in this container) — [UPSTREAM-RECALL].
+use core::ffi::c_void;
+
+use p3_baby_bear::BabyBear;
+use p3_challenger::{CanObserve, CanSample, CanSampleBits};
+use p3_field::coset::TwoAdicMultiplicativeCoset;
+use p3_field::extension::BinomialExtensionField;
+use p3_field::PrimeField32;
+use p3_fri::FriParameters;
+use p3_matrix::dense::RowMajorMatrix;
+use p3_matrix::Matrix;
+
+pub type Val = BabyBear;
+pub type Challenge = BinomialExtensionField<Val, 4>;
+
+pub const P3HIP_HASH_POSEIDON2: i32 = 0;
+pub const P3HIP_HASH_KECCAK: i32 = 1;
+pub const P3HIP_PROFILE_LATENCY: i32 = 2;
+
+#[repr(C)]
+pub struct p3hip_fri_params_t {
+    pub log_blowup: u32,
+    pub log_final_poly_len: u32,
+    pub num_queries: u32,
+    pub proof_of_work_bits: u32,
+}
+#[repr(C)]
+pub struct p3hip_challenger_t {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct p3hip_pcs_t {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct p3hip_pcs_data_t {
+    _private: [u8; 0],
+}
+
+// include/p3hip.h
+extern "C" {
+    fn p3hip_take_last_error() -> *const core::ffi::c_char;
+    fn p3hip_challenger_create(hash: i32, out: *mut *mut p3hip_challenger_t) -> i32;
+    fn p3hip_challenger_observe(c: *mut p3hip_challenger_t, monty_words: *const u32, n: usize) -> i32;
+    fn p3hip_challenger_observe_digest(c: *mut p3hip_challenger_t, digest: *const u32) -> i32;
+    fn p3hip_challenger_sample_ext(c: *mut p3hip_challenger_t, out: *mut u32) -> i32;
+    fn p3hip_challenger_sample_bits(c: *mut p3hip_challenger_t, bits: u32, out: *mut u32) -> i32;
+    fn p3hip_challenger_clone(c: *const p3hip_challenger_t, out: *mut *mut p3hip_challenger_t) -> i32;
+    fn p3hip_challenger_destroy(c: *mut p3hip_challenger_t);
+    fn p3hip_pcs_create(
+        profile: i32,
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        stream: *mut c_void,
+        own_stream: i32,
+        out: *mut *mut p3hip_pcs_t,
+    ) -> i32;
+    fn p3hip_pcs_commit_dev(
+        pcs: *mut p3hip_pcs_t,
+        d_evals: *const *const u32,
+        heights: *const usize,
+        widths: *const usize,
+        domain_shifts: *const u32,
+        n_mats: usize,
+        root_out: *mut u32,
+        data_out: *mut *mut p3hip_pcs_data_t,
+    ) -> i32;
+    fn p3hip_pcs_lde_dev(
+        data: *const p3hip_pcs_data_t,
+        mat: usize,
+        d_lde: *mut *const u32,
+        height: *mut usize,
+        width: *mut usize,
+    ) -> i32;
+    fn p3hip_pcs_open(
+        pcs: *mut p3hip_pcs_t,
+        rounds: *const *const p3hip_pcs_data_t,
+        n_rounds: usize,
+        points_per_mat: *const usize,
+        points: *const u32,
+        challenger: *mut p3hip_challenger_t,
+        opened_out: *mut u32,
+        opened_cap_words: usize,
+        proof_out: *mut *const u8,
+        proof_len: *mut usize,
+    ) -> i32;
+    fn p3hip_pcs_verify(
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        log_h: u32,
+        roots: *const u32,
+        mats_per_round: *const usize,
+        widths: *const usize,
+        n_rounds: usize,
+        points_per_mat: *const usize,
+        points: *const u32,
+        opened: *const u32,
+        proof: *const u8,
+        len: usize,
+        challenger: *mut p3hip_challenger_t,
+        reject_code: *mut i32,
+    ) -> i32;
+    fn p3hip_pcs_data_free(d: *mut p3hip_pcs_data_t);
+    fn p3hip_pcs_destroy(pcs: *mut p3hip_pcs_t);
+    fn p3hip_malloc(dev_ptr: *mut *mut c_void, bytes: usize) -> i32;
+    fn p3hip_free(dev_ptr: *mut c_void) -> i32;
+    fn p3hip_upload(dev_dst: *mut c_void, host_src: *const c_void, bytes: usize) -> i32;
+    fn p3hip_download(host_dst: *mut c_void, dev_src: *const c_void, bytes: usize) -> i32;
+}
+
+// BabyBear is a transparent u32 holding the Montgomery word (the same reinterpretation backend_hip.rs makes of `shift`), and
+// BinomialExtensionField<Val, 4> is its four coefficients in order [UPSTREAM-RECALL]
+fn vals_from_monty_words(words: Vec<u32>) -> Vec<Val> {
+    words.into_iter().map(|w| unsafe { *(&w as *const u32 as *const Val) }).collect()
+}
+fn ext_from_monty_words(w: [u32; 4]) -> Challenge {
+    unsafe { *(&w as *const [u32; 4] as *const Challenge) }
+}
+
+fn last_error(rc: i32) -> String {
+    let p = unsafe { p3hip_take_last_error() };
+    let msg = if p.is_null() { String::new() } else { unsafe { core::ffi::CStr::from_ptr(p) }.to_string_lossy().into_owned() };
+    format!("libp3hip error {rc}: {msg}")
+}
+
+/// DuplexChallenger<Val, Poseidon2-16, 16, 8> or SerializingChallenger32<Val, HashChallenger<u8, Keccak256Hash, 32>>, inside libp3hip.
+pub struct HipChallenger {
+    h: *mut p3hip_challenger_t,
+}
+impl HipChallenger {
+    pub fn new(hash: i32) -> Result<Self, String> {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { p3hip_challenger_create(hash, &mut h) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(Self { h }) }
+    }
+}
+impl Clone for HipChallenger {
+    fn clone(&self) -> Self {
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { p3hip_challenger_clone(self.h, &mut h) };
+        assert_eq!(rc, 0, "{}", last_error(rc));
+        Self { h }
+    }
+}
+impl Drop for HipChallenger {
+    fn drop(&mut self) {
+        unsafe { p3hip_challenger_destroy(self.h) }
+    }
+}
+impl CanObserve<Val> for HipChallenger {
+    fn observe(&mut self, value: Val) {
+        let w = value.to_unique_u32(); // the Montgomery word (backend_vulkan.rs:2002-2005)
+        let rc = unsafe { p3hip_challenger_observe(self.h, &w, 1) };
+        assert_eq!(rc, 0, "{}", last_error(rc));
+    }
+}
+impl CanObserve<[u32; 8]> for HipChallenger {
+    // a commitment: Hash<Val, Val, 8> as 8 Montgomery words, or Hash<Val, u64, 4> as the same 32 little-endian bytes
+    fn observe(&mut self, digest: [u32; 8]) {
+        let rc = unsafe { p3hip_challenger_observe_digest(self.h, digest.as_ptr()) };
+        assert_eq!(rc, 0, "{}", last_error(rc));
+    }
+}
+impl CanSample<Challenge> for HipChallenger {
+    fn sample(&mut self) -> Challenge {
+        let mut w = [0u32; 4];
+        let rc = unsafe { p3hip_challenger_sample_ext(self.h, w.as_mut_ptr()) };
+        assert_eq!(rc, 0, "{}", last_error(rc));
+        ext_from_monty_words(w)
+    }
+}
+impl CanSampleBits<usize> for HipChallenger {
+    fn sample_bits(&mut self, bits: usize) -> usize {
+        let mut v = 0u32;
+        let rc = unsafe { p3hip_challenger_sample_bits(self.h, bits as u32, &mut v) };
+        assert_eq!(rc, 0, "{}", last_error(rc));
+        v as usize
+    }
+}
+
+/// Pcs::ProverData: the bit-reversed LDEs in HBM and their Merkle tree, owned by libp3hip.
+pub struct HipPcsData {
+    h: *mut p3hip_pcs_data_t,
+    pub root: [u32; 8],
+    pub dims: Vec<(usize, usize)>,
+}
+impl Drop for HipPcsData {
+    fn drop(&mut self) {
+        unsafe { p3hip_pcs_data_free(self.h) }
+    }
+}
+
+/// What `open` returns and `verify` takes beside the opened values: the FriProof section of the wire format (DESIGN.md "proof bytes").
+pub type HipFriProof = Vec<u8>;
+
+pub struct HipPcs {
+    h: *mut p3hip_pcs_t,
+    hash: i32,
+    params: p3hip_fri_params_t,
+}
+impl HipPcs {
+    pub fn new<M>(hash: i32, fri: &FriParameters<M>) -> Result<Self, String> {
+        let params = p3hip_fri_params_t {
+            log_blowup: fri.log_blowup as u32,
+            log_final_poly_len: fri.log_final_poly_len as u32,
+            num_queries: fri.num_queries as u32,
+            proof_of_work_bits: fri.proof_of_work_bits as u32,
+        };
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { p3hip_pcs_create(P3HIP_PROFILE_LATENCY, hash, &params, core::ptr::null_mut(), 1, &mut h) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(Self { h, hash, params }) }
+    }
+    pub fn keccak<M>(fri: &FriParameters<M>) -> Result<Self, String> {
+        Self::new(P3HIP_HASH_KECCAK, fri)
+    }
+    pub fn poseidon2<M>(fri: &FriParameters<M>) -> Result<Self, String> {
+        Self::new(P3HIP_HASH_POSEIDON2, fri)
+    }
+
+    /// Pcs::commit: uploads each (domain, evaluations) pair (4hw bytes; nothing if the caller already holds them in HBM and uses
+    /// commit_dev) and commits; the root is the only thing that comes back.
+    pub fn commit_host(&self, evaluations: &[(TwoAdicMultiplicativeCoset<Val>, RowMajorMatrix<Val>)]) -> Result<HipPcsData, String> {
+        let mut dev: Vec<*mut c_void> = Vec::new();
+        let (mut hs, mut ws, mut shifts, mut dims) = (Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        for (domain, m) in evaluations {
+            let bytes = m.height() * m.width() * 4;
+            let mut p = core::ptr::null_mut();
+            let rc = unsafe { p3hip_malloc(&mut p, bytes) };
+            if rc != 0 { return Err(last_error(rc)); }
+            let rc = unsafe { p3hip_upload(p, m.values.as_ptr() as *const c_void, bytes) };
+            if rc != 0 { return Err(last_error(rc)); }
+            dev.push(p);
+            hs.push(m.height());
+            ws.push(m.width());
+            shifts.push(domain.shift().to_unique_u32());
+            dims.push((m.height(), m.width()));
+        }
+        let ptrs: Vec<*const u32> = dev.iter().map(|p| *p as *const u32).collect();
+        let mut root = [0u32; 8];
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe {
+            p3hip_pcs_commit_dev(self.h, ptrs.as_ptr(), hs.as_ptr(), ws.as_ptr(), shifts.as_ptr(), ptrs.len(), root.as_mut_ptr(), &mut h)
+        };
+        for p in dev { unsafe { p3hip_free(p) }; } // the prover data owns the LDEs, not the evaluations
+        if rc != 0 { Err(last_error(rc)) } else { Ok(HipPcsData { h, root, dims }) }
+    }
+
+    /// Pcs::get_evaluations_on_domain for GENERATOR * <g_m>: the first m rows of the stored LDE (natural index i at row bitrev(i)).
+    /// A device pointer; `download_rows` brings them to the host for a quotient computed there.
+    pub fn evaluations_on_domain_dev(&self, data: &HipPcsData, idx: usize) -> Result<(*const u32, usize, usize), String> {
+        let (mut p, mut h, mut w) = (core::ptr::null(), 0usize, 0usize);
+        let rc = unsafe { p3hip_pcs_lde_dev(data.h, idx, &mut p, &mut h, &mut w) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok((p, h, w)) }
+    }
+    pub fn download_rows(&self, data: &HipPcsData, idx: usize, rows: usize) -> Result<RowMajorMatrix<Val>, String> {
+        let (p, _, w) = self.evaluations_on_domain_dev(data, idx)?;
+        let mut words = vec![0u32; rows * w];
+        let rc = unsafe { p3hip_download(words.as_mut_ptr() as *mut c_void, p as *const c_void, rows * w * 4) };
+        if rc != 0 { return Err(last_error(rc)); }
+        Ok(RowMajorMatrix::new(vals_from_monty_words(words), w))
+    }
+
+    /// Pcs::open: rounds = (prover data, points per matrix); returns the opened values in observation order (round -> matrix ->
+    /// point -> column, 4 Montgomery words each) and the FRI proof bytes; the challenger is advanced on the device.
+    pub fn open_words(
+        &self,
+        rounds: &[(&HipPcsData, Vec<Vec<[u32; 4]>>)],
+        challenger: &mut HipChallenger,
+    ) -> Result<(Vec<u32>, HipFriProof), String> {
+        let handles: Vec<*const p3hip_pcs_data_t> = rounds.iter().map(|(d, _)| d.h as *const _).collect();
+        let (mut counts, mut points, mut total) = (Vec::new(), Vec::new(), 0usize);
+        for (d, per_mat) in rounds {
+            for (m, pts) in per_mat.iter().enumerate() {
+                counts.push(pts.len());
+                total += pts.len() * d.dims[m].1;
+                for z in pts { points.extend_from_slice(z); }
+            }
+        }
+        let mut opened = vec![0u32; 4 * total];
+        let (mut proof, mut len) = (core::ptr::null(), 0usize);
+        let rc = unsafe {
+            p3hip_pcs_open(self.h, handles.as_ptr(), handles.len(), counts.as_ptr(), points.as_ptr(), challenger.h, opened.as_mut_ptr(),
+                           opened.len(), &mut proof, &mut len)
+        };
+        if rc != 0 { return Err(last_error(rc)); }
+        Ok((opened, unsafe { core::slice::from_raw_parts(proof, len) }.to_vec()))
+    }
+
+    /// Pcs::verify on the host: Ok(()) or the failed check's code and text.
+    #[allow(clippy::too_many_arguments)]
+    pub fn verify_words(
+        &self,
+        log_h: u32,
+        roots: &[[u32; 8]],
+        widths: &[Vec<usize>],
+        points: &[Vec<Vec<[u32; 4]>>],
+        opened: &[u32],
+        proof: &[u8],
+        challenger: &mut HipChallenger,
+    ) -> Result<(), String> {
+        let flat_roots: Vec<u32> = roots.iter().flatten().copied().collect();
+        let mats: Vec<usize> = widths.iter().map(|w| w.len()).collect();
+        let flat_w: Vec<usize> = widths.iter().flatten().copied().collect();
+        let counts: Vec<usize> = points.iter().flatten().map(|p| p.len()).collect();
+        let flat_p: Vec<u32> = points.iter().flatten().flatten().flatten().copied().collect();
+        let mut code = 0i32;
+        let rc = unsafe {
+            p3hip_pcs_verify(self.hash, &self.params, log_h, flat_roots.as_ptr(), mats.as_ptr(), flat_w.as_ptr(), mats.len(), counts.as_ptr(),
+                             flat_p.as_ptr(), opened.as_ptr(), proof.as_ptr(), proof.len(), challenger.h, &mut code)
+        };
+        if rc != 0 { return Err(last_error(rc)); }
+        if code != 0 { return Err(last_error(code)); }
+        Ok(())
+    }
+}
+impl Drop for HipPcs {
+    fn drop(&mut self) {
+        unsafe { p3hip_pcs_destroy(self.h) }
+    }
+}
+
+// `impl Pcs<Challenge, HipChallenger> for HipPcs` (p3-commit 0.4.2, as recalled): Domain = TwoAdicMultiplicativeCoset<Val>,
+// Commitment = [u32; 8] digest words, ProverData = HipPcsData, EvaluationsOnDomain = RowMajorMatrix<Val> (download_rows), Proof =
+// HipFriProof, Error = String.  natural_domain_for_degree is TwoAdicFriPcs's own; commit = commit_host; get_evaluations_on_domain =
+// download_rows of the first `domain.size()` rows, un-bit-reversed by the caller's `.bit_reverse_rows()`; open = open_words with the
+// points' Montgomery words, reshaped into OpenedValues<Challenge> (round -> matrix -> point -> column is already upstream's nesting);
+// verify = verify_words over the same flattening.  The trait impl itself is left to the crate that has p3-commit to compile against.

@@ -123,6 +123,23 @@ _SIGS = {
     "p3hip_fib_verifier_destroy": (None, [C.c_void_p]),
     "p3hip_mmcs_commit": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                     C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "p3hip_challenger_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "p3hip_challenger_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "p3hip_challenger_observe_digest": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "p3hip_challenger_sample_ext": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "p3hip_challenger_sample_bits": (C.c_int, [C.c_void_p, C.c_uint, u32p]),
+    "p3hip_challenger_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "p3hip_challenger_destroy": (None, [C.c_void_p]),
+    "p3hip_pcs_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "p3hip_pcs_commit_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "p3hip_pcs_lde_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "p3hip_pcs_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+    "p3hip_pcs_verify": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t,
+                                   C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
+    "p3hip_pcs_data_free": (None, [C.c_void_p]),
+    "p3hip_pcs_destroy": (None, [C.c_void_p]),
 }
 
 

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "bb31.hip.h"
+#include "challenger.h"
 #include "common.h"
 #include "mmcs.h"
 #include "prover.h"
@@ -1157,4 +1158,155 @@ int p3hip_fib_verifier_verify(p3hip_fib_verifier_t* v, size_t n, const uint8_t* 
     });
 }
 void p3hip_fib_verifier_destroy(p3hip_fib_verifier_t* v) { delete v; }
+}  // extern "C"
+
+// ---- TwoAdicFriPcs over caller matrices (pcs.hip.inc, verifier.hip) and the host challengers its callers drive ----
+struct p3hip_challenger {
+    Challenger c;
+};
+struct p3hip_pcs_data {
+    std::unique_ptr<PcsData> d;
+};
+struct p3hip_pcs {
+    Pcs pcs;
+    std::vector<uint32_t> opened;
+    std::vector<uint8_t> proof;
+};
+
+extern "C" {
+
+int p3hip_challenger_create(int hash, p3hip_challenger_t** out) {
+    return guarded([&]() -> int {
+        if (!out) return fail(ERR_BAD_ARG, "challenger_create: null argument");
+        if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return fail(ERR_BAD_ARG, "challenger_create: unknown hash configuration");
+        *out = new p3hip_challenger{Challenger(hash)};
+        return OK;
+    });
+}
+int p3hip_challenger_observe(p3hip_challenger_t* c, const uint32_t* monty_words, size_t n) {
+    return guarded([&]() -> int {
+        if (!c || (!monty_words && n)) return fail(ERR_BAD_ARG, "challenger_observe: null argument");
+        for (size_t i = 0; i < n; i++)
+            if (monty_words[i] >= bb::P) return fail(ERR_BAD_ARG, "challenger_observe: word " + std::to_string(i) + " is not a canonical field element");
+        c->c.observe_n(monty_words, n);
+        return OK;
+    });
+}
+int p3hip_challenger_observe_digest(p3hip_challenger_t* c, const uint32_t digest[8]) {
+    return guarded([&]() -> int {
+        if (!c || !digest) return fail(ERR_BAD_ARG, "challenger_observe_digest: null argument");
+        if (c->c.kind == HASH_POSEIDON2)
+            for (int i = 0; i < 8; i++)
+                if (digest[i] >= bb::P) return fail(ERR_BAD_ARG, "challenger_observe_digest: word " + std::to_string(i) + " is not a canonical field element");
+        c->c.observe_digest(digest);
+        return OK;
+    });
+}
+int p3hip_challenger_sample_ext(p3hip_challenger_t* c, uint32_t out[4]) {
+    return guarded([&]() -> int {
+        if (!c || !out) return fail(ERR_BAD_ARG, "challenger_sample_ext: null argument");
+        const bb::Ext e = c->c.sample_ext();
+        memcpy(out, e.c, 16);
+        return OK;
+    });
+}
+int p3hip_challenger_sample_bits(p3hip_challenger_t* c, unsigned bits, uint32_t* out) {
+    return guarded([&]() -> int {
+        if (!c || !out) return fail(ERR_BAD_ARG, "challenger_sample_bits: null argument");
+        if (bits > 30) return fail(ERR_BAD_ARG, "challenger_sample_bits: at most 30 bits");
+        *out = (uint32_t)c->c.sample_bits(bits);
+        return OK;
+    });
+}
+int p3hip_challenger_clone(const p3hip_challenger_t* c, p3hip_challenger_t** out) {
+    return guarded([&]() -> int {
+        if (!c || !out) return fail(ERR_BAD_ARG, "challenger_clone: null argument");
+        *out = new p3hip_challenger{c->c};
+        return OK;
+    });
+}
+void p3hip_challenger_destroy(p3hip_challenger_t* c) { delete c; }
+
+int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t* params, void* stream, int own_stream, p3hip_pcs_t** out) {
+    return guarded([&]() -> int {
+        if (!params || !out) return fail(ERR_BAD_ARG, "pcs_create: null argument");
+        if (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY) return fail(ERR_BAD_ARG, "pcs_create: unknown profile");
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        bool own = false;
+        if (own_stream) {
+            P3_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            own = true;
+        }
+        std::unique_ptr<p3hip_pcs> p(new p3hip_pcs());
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        // on failure the object's destructor destroys the owned stream
+        if ((rc = p->pcs.init(fp, st, own, hash, profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY))) return rc;
+        *out = p.release();
+        return OK;
+    });
+}
+int p3hip_pcs_commit_dev(p3hip_pcs_t* pcs, const uint32_t* const* d_evals, const size_t* heights, const size_t* widths,
+                         const uint32_t* domain_shifts, size_t n_mats, uint32_t root_out[8], p3hip_pcs_data_t** data_out) {
+    return guarded([&]() -> int {
+        if (!pcs || !data_out) return fail(ERR_BAD_ARG, "pcs_commit: null argument");
+        PcsData* d = nullptr;
+        int rc = pcs->pcs.commit(d_evals, heights, widths, domain_shifts, n_mats, root_out, &d);
+        if (rc) return rc;
+        *data_out = new p3hip_pcs_data{std::unique_ptr<PcsData>(d)};
+        return OK;
+    });
+}
+int p3hip_pcs_lde_dev(const p3hip_pcs_data_t* data, size_t mat, const uint32_t** d_lde, size_t* height, size_t* width) {
+    return guarded([&]() -> int {
+        if (!data || !d_lde || !height || !width) return fail(ERR_BAD_ARG, "pcs_lde: null argument");
+        if (mat >= data->d->lde.size()) return fail(ERR_BAD_ARG, "pcs_lde: matrix " + std::to_string(mat) + " of a commitment of " + std::to_string(data->d->lde.size()));
+        *d_lde = data->d->lde[mat];
+        *height = (size_t)1 << data->d->log_big;
+        *width = data->d->widths[mat];
+        return OK;
+    });
+}
+int p3hip_pcs_open(p3hip_pcs_t* pcs, const p3hip_pcs_data_t* const* rounds, size_t n_rounds, const size_t* points_per_mat,
+                   const uint32_t* points, p3hip_challenger_t* challenger, uint32_t* opened_out, size_t opened_cap_words,
+                   const uint8_t** proof_out, size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!pcs || !rounds || !challenger || !opened_out || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "pcs_open: null argument");
+        if (n_rounds > PCS_MAX_ROUNDS) return fail(ERR_BAD_ARG, "pcs open: " + std::to_string(n_rounds) + " rounds, an open takes at most " + std::to_string(PCS_MAX_ROUNDS));
+        const PcsData* rr[PCS_MAX_ROUNDS] = {nullptr};
+        for (size_t r = 0; r < n_rounds; r++) rr[r] = rounds[r] ? rounds[r]->d.get() : nullptr;
+        // the challenger is handed over only when the open succeeds: a failed call leaves the caller's transcript as it was
+        Challenger ch = challenger->c;
+        int rc = pcs->pcs.open(rr, n_rounds, points_per_mat, points, &ch, &pcs->opened, &pcs->proof);
+        if (rc) { pcs->proof.clear(); return rc; }
+        if (pcs->opened.size() > opened_cap_words)
+            return fail(ERR_BAD_ARG, "pcs_open: the opened values take " + std::to_string(pcs->opened.size()) + " words, the buffer holds " + std::to_string(opened_cap_words));
+        memcpy(opened_out, pcs->opened.data(), pcs->opened.size() * 4);
+        challenger->c = ch;
+        *proof_out = pcs->proof.data();
+        *proof_len = pcs->proof.size();
+        return OK;
+    });
+}
+int p3hip_pcs_verify(int hash, const p3hip_fri_params_t* params, unsigned log_h, const uint32_t* roots, const size_t* mats_per_round,
+                     const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
+                     const uint8_t* proof, size_t len, p3hip_challenger_t* challenger, int* reject_code) {
+    return guarded([&]() -> int {
+        if (!params || !challenger || !reject_code) return fail(ERR_BAD_ARG, "pcs_verify: null argument");
+        *reject_code = 0;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::string why;
+        Challenger ch = challenger->c;
+        int rc = pcs_verify(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, &ch, &why);
+        if (rc < 0) return fail(rc, why);
+        challenger->c = ch;  // accepted or rejected, the transcript is where the verifier left it
+        if (rc > 0) { *reject_code = rc; set_error("pcs verification failed: " + why); }
+        return OK;
+    });
+}
+void p3hip_pcs_data_free(p3hip_pcs_data_t* d) { delete d; }
+void p3hip_pcs_destroy(p3hip_pcs_t* pcs) { delete pcs; }
+
 }  // extern "C"

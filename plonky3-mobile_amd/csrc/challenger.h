@@ -60,6 +60,17 @@ inline void keccak256_host(const uint8_t* in, size_t n, uint8_t out[32]) {
     keccak_f_host(st);
     memcpy(out, st, 32);
 }
+// the same from a sponge state that has already absorbed some complete blocks (all zero: Keccak256Hash itself)
+inline void keccak256_resume_host(uint64_t st[25], const uint8_t* in, size_t n, uint8_t out[32]) {
+    size_t off = keccak256_absorb_full(st, in, n);
+    uint8_t blk[136] = {0};
+    memcpy(blk, in + off, n - off);
+    blk[n - off] ^= 0x01;
+    blk[135] ^= 0x80;
+    for (int i = 0; i < 17; i++) { uint64_t w; memcpy(&w, blk + 8 * i, 8); st[i] ^= w; }
+    keccak_f_host(st);
+    memcpy(out, st, 32);
+}
 // SerializingHasher<PaddingFreeSponge<KeccakF, 25, 17, 4>> over a row of Montgomery words
 inline void keccak_hash_row_host(const uint32_t* items, size_t n, uint32_t out[8]) {
     uint64_t st[25] = {0};
@@ -92,6 +103,9 @@ struct Challenger {
     std::vector<uint8_t> ibuf;
     uint8_t obuf[32] = {0};
     int n_obuf = 0;
+    // the sponge state of the complete input blocks a DEVICE transcript has already absorbed (the PCS hands its challenger to the
+    // device and takes it back: pcs.hip.inc); all zero on a challenger that has only ever run here
+    uint64_t kst[25] = {0};
 
     explicit Challenger(int k = HASH_POSEIDON2) : kind(k) {}
     void duplex() {
@@ -102,7 +116,8 @@ struct Challenger {
         n_out = 8;
     }
     void flush() {  // output = H(input); the digest also becomes the next input's prefix (chaining value)
-        keccak256_host(ibuf.data(), ibuf.size(), obuf);
+        keccak256_resume_host(kst, ibuf.data(), ibuf.size(), obuf);
+        memset(kst, 0, sizeof kst);
         n_obuf = 32;
         ibuf.assign(obuf, obuf + 32);
     }

@@ -8,6 +8,9 @@
 
 namespace p3 {
 
+struct Tree;        // mmcs.h
+struct Challenger;  // challenger.h
+
 // p3_fri::FriParameters (the mmcs field is implied: ExtensionMmcs over the Poseidon2 tree)
 struct FriParams {
     uint32_t log_blowup, log_final_poly_len, num_queries, proof_of_work_bits;
@@ -90,5 +93,56 @@ int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint
                           const FriParams& fp, std::string* why, int hash);
 // the parameter gates of the two verifiers above (0, or ERR_BAD_ARG with the format's message in *why)
 int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriParams& fp, std::string* why);
+
+
+// ---- TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over caller-supplied matrices (pcs.hip.inc), non-hiding ----
+// Every matrix of one open / verify has the same height h = 2^log_h (what p3_uni_stark produces for any AIR: trace, preprocessed
+// trace and quotient chunks); mixed heights are refused by name.  Capacities, refused by name when exceeded:
+constexpr size_t PCS_MAX_MATS = 8;      // matrices per commitment (QTREE_MAX_MATS)
+constexpr size_t PCS_MAX_ROUNDS = 4;    // commitments per open
+constexpr size_t PCS_MAX_POINTS = 4;    // distinct opening points per open
+constexpr size_t PCS_MAX_COLS = 8192;   // batched columns: sum of width over every (matrix, point) pair; also the widest matrix
+
+// prover data of one commitment: the bit-reversed LDEs (owned, in HBM) and their tree
+struct PcsData {
+    std::vector<uint32_t*> lde;
+    std::vector<size_t> widths;
+    uint32_t log_h = 0, log_big = 0;
+    int hash = 0, device = -1;
+    Tree* tree = nullptr;
+    PcsData() = default;
+    PcsData(const PcsData&) = delete;
+    ~PcsData();
+};
+
+class Pcs {
+  public:
+    Pcs();
+    ~Pcs();
+    Pcs(const Pcs&) = delete;
+    int init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile);
+    // Pcs::commit: d_evals[m] = heights[m] x widths[m] evaluations over shifts[m] * <g_h> in natural row order (device memory; shifts
+    // null: all 1); one synchronisation (the root)
+    int commit(const uint32_t* const* d_evals, const size_t* heights, const size_t* widths, const uint32_t* shifts, size_t n_mats,
+               uint32_t root_out[8], PcsData** out);
+    // Pcs::open: points_per_mat per matrix in round -> matrix order, points 4 words each in round -> matrix -> point order; chal: the
+    // transcript before the open, on return the transcript after the last query index; opened: extension elements in observation
+    // order; proof: the FriProof section of the wire format.  One synchronisation.
+    int open(const PcsData* const* rounds, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, Challenger* chal,
+             std::vector<uint32_t>* opened, std::vector<uint8_t>* proof);
+    hipStream_t stream() const;
+
+  private:
+    struct Impl;
+    Impl* im;
+};
+
+bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big);
+// verifier.hip: Pcs::verify on the host.  0 = accept; ERR_BAD_ARG for a refused argument; a positive code names the failed check
+// (the numbering of verify_fib_air's FRI half: 5 commit phase length, 6 query count, 7 final polynomial length, 8 trailing or missing
+// bytes, 9 truncated, 11 InvalidPowWitness, 12 query shape, 13 input opening, 14 FRI layer opening, 15 FinalPolyMismatch)
+int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
+               size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
+               size_t len, Challenger* chal, std::string* why);
 
 }  // namespace p3

@@ -13,6 +13,7 @@
 // All of these passes are HBM- or integer-VALU-bound element-wise / reduction kernels: one lane per row,
 // 16-byte accesses, no MFMA.
 #include <chrono>
+#include <cstddef>
 #include <deque>
 #include <memory>
 #include <cstring>
@@ -1249,3 +1250,4 @@ uint64_t FibProver::grind_misses(std::vector<uint32_t>* last_indices) const {
 }  // namespace p3
 
 #include "prover_hiding.hip.inc"
+#include "pcs.hip.inc"

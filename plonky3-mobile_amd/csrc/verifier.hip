@@ -3,12 +3,15 @@
 // "fib_air zk ok").  Verification is a few thousand permutations — it is the verifier's role, runs on the host
 // exactly as in the reference, and is not a fallback for any device kernel.  Written against the wire format
 // of prover.hip; independent of the test oracle.
+#include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "bb31.hip.h"
 #include "challenger.h"
 #include "common.h"
+#include "mmcs.h"
 #include "poseidon2.hip.h"
 #include "prover.h"
 
@@ -374,6 +377,127 @@ int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint
         for (uint32_t j = 0; j < VH_TW; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(trow[j])), d0)));
         for (uint32_t j = 0; j < VH_TW; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(trow[j])), d1)));
         for (uint32_t j = 0; j < VH_CH * VH_D; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(qrow[j])), d0)));
+        if (int rc = fri.query(rd, index, ro, path.data())) return rc;
+    }
+    if (why) why->clear();
+    return 0;
+}
+
+// ---- Pcs::verify of TwoAdicFriPcs over caller matrices (the prover half: pcs.hip.inc), host only.  The opened values arrive beside
+// the proof bytes (the FriProof section of the wire format); the FRI half is FriCheck, shared with the two fib verifiers.  The
+// transcript follows the test oracle's verifier (stark.c:216-294) generalised to the call's dimensions: opened values observed
+// round -> matrix -> point -> column, alpha sampled, and per query
+//   ro = sum over (matrix, point) pairs in that order, over columns c:  alpha^k (opened_k - row[c]) / (z - x),  k running on.
+// Every size of the query section follows from the arguments: no loop bound or offset is read from the proof.
+int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
+               size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
+               size_t len, Challenger* chal, std::string* why) {
+    auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
+    if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
+    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
+    if (chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
+    if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
+    if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
+    if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
+    if (fp.num_queries == 0) return bad("pcs verify: num_queries must be positive");
+    if (n_rounds == 0) return bad("pcs verify: zero rounds");
+    if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
+    const uint32_t log_big = log_h + fp.log_blowup;
+    struct Pair { Ext z; uint32_t width; };
+    std::vector<Pair> pairs;                   // round -> matrix -> point
+    std::vector<uint32_t> mat_pairs;           // per matrix: how many pairs
+    Ext zs[PCS_MAX_POINTS];
+    size_t n_points = 0, total = 0, mi = 0, pi = 0, row_max = 0;
+    for (size_t r = 0; r < n_rounds; r++) {
+        if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
+        if (mats_per_round[r] > PCS_MAX_MATS) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(PCS_MAX_MATS) + " matrices");
+        size_t row = 0;
+        for (size_t m = 0; m < mats_per_round[r]; m++, mi++) {
+            const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
+            if (widths[mi] < 1 || widths[mi] > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
+            if (points_per_mat[mi] > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
+            row += widths[mi];
+            mat_pairs.push_back((uint32_t)points_per_mat[mi]);
+            for (size_t p = 0; p < points_per_mat[mi]; p++, pi++) {
+                const uint32_t* z = points + 4 * pi;
+                const std::string pw = who + " point " + std::to_string(p);
+                for (int c = 0; c < 4; c++) if (z[c] >= bb::P) return bad(pw + " is not a canonical field element");
+                if (pcs_point_on_lde_coset(z, log_big)) return bad(pw + " lies on the LDE coset GENERATOR * <g_big>");
+                size_t k = 0;
+                while (k < n_points && memcmp(zs[k].c, z, 16)) k++;
+                if (k == n_points) {
+                    if (n_points == PCS_MAX_POINTS) return bad(pw + ": more than " + std::to_string(PCS_MAX_POINTS) + " distinct opening points");
+                    memcpy(zs[n_points++].c, z, 16);
+                }
+                pairs.push_back(Pair{zs[k], (uint32_t)widths[mi]});
+                total += widths[mi];
+                if (total > PCS_MAX_COLS) return bad(pw + ": more than " + std::to_string(PCS_MAX_COLS) + " batched columns");
+            }
+        }
+        row_max = std::max(row_max, row);
+    }
+    if (total == 0) return bad("pcs verify: no opening point");
+    for (size_t i = 0; i < 4 * total; i++) if (opened[i] >= bb::P) return bad("pcs verify: opened value word " + std::to_string(i) + " is not a canonical field element");
+    Challenger& ch = *chal;
+    std::vector<Ext> ov(total), alp(total);
+    for (size_t i = 0; i < total; i++) { memcpy(ov[i].c, opened + 4 * i, 16); ch.observe_ext(ov[i]); }
+    const Ext al = ch.sample_ext();
+    alp[0] = bb::ext_one();
+    for (size_t k = 1; k < total; k++) alp[k] = bb::mul(alp[k - 1], al);
+    Reader rd{proof, len};
+    FriCheck fri{hash, fp, log_big, 0, why};
+    if (int rc = fri.commit_phase(rd, ch)) return rc;
+    const size_t qstart = rd.pos;
+    {   // the query section's length: per query the rounds' BatchOpenings, then the FRI walk
+        size_t qbytes = 4;
+        mi = 0;
+        for (size_t r = 0; r < n_rounds; r++) {
+            qbytes += 4;
+            for (size_t m = 0; m < mats_per_round[r]; m++, mi++) qbytes += 4 + 4 * widths[mi];
+            qbytes += 4 + 32 * (size_t)log_big;
+        }
+        qbytes += 4;
+        for (uint32_t r = 0; r < fri.n_rounds; r++) qbytes += 16 + 4 + 32 * (size_t)(log_big - 1 - r);
+        const size_t all = qbytes * fp.num_queries;
+        if (all > len - rd.pos) return reject(why, 9, "truncated proof");
+        rd.pos += all;
+    }
+    if (int rc = fri.final_poly(rd, ch)) return rc;
+    rd.pos = qstart;
+    std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(row_max);
+    std::vector<size_t> hh(PCS_MAX_MATS, (size_t)1 << log_big);
+    const uint32_t gen = bb::to_monty(bb::GEN);
+    for (uint32_t q = 0; q < fp.num_queries; q++) {
+        const size_t index = ch.sample_bits(log_big);
+        const uint32_t xi = bb::mul(gen, bb::pow(bb::two_adic_generator(log_big), rev_bits_host(index, log_big)));
+        if (rd.u32() != n_rounds) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
+        Ext ro = bb::ext_zero();
+        size_t k = 0, pair = 0;
+        mi = 0;
+        for (size_t r = 0; r < n_rounds; r++) {
+            const size_t nm = mats_per_round[r], m0 = mi;
+            if (rd.u32() != nm) return reject(why, 12, "query shape");
+            size_t off = 0;
+            for (size_t m = 0; m < nm; m++) {
+                if (rd.u32() != widths[m0 + m]) return reject(why, 12, "query shape");
+                rd.felts(row.data() + off, widths[m0 + m]);
+                off += widths[m0 + m];
+            }
+            if (rd.u32() != log_big) return reject(why, 12, "query shape");
+            rd.digests(hash, path.data(), log_big);
+            if (rd.bad) return reject(why, 9, "truncated proof");
+            if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index, row.data(), path.data(), log_big, nullptr, false) != 0)
+                return reject(why, 13, "input opening");
+            off = 0;
+            for (size_t m = 0; m < nm; m++, mi++) {
+                for (uint32_t p = 0; p < mat_pairs[mi]; p++, pair++) {
+                    const Ext dz = bb::inv(bb::sub(pairs[pair].z, bb::ext_from_base(xi)));
+                    for (size_t c = 0; c < widths[mi]; c++, k++)
+                        ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(ov[k], bb::ext_from_base(row[off + c])), dz)));
+                }
+                off += widths[mi];
+            }
+        }
         if (int rc = fri.query(rd, index, ro, path.data())) return rc;
     }
     if (why) why->clear();

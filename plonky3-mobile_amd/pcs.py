@@ -1,0 +1,204 @@
+"""Host-side mirror of Plonky3's Pcs contract for TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over
+caller-supplied matrices (include/p3hip.h "TwoAdicFriPcs over CALLER-SUPPLIED matrices"), and of the challengers a caller
+drives between its calls.  Non-hiding; every matrix of one open / verify has the same height.  commit / open keep everything
+device-resident (one synchronisation each); verify is host code of the library."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .fib_air import FriParameters, _hash_kind, profile_kind
+from .gpu_dft import MONTY_ONE, P, _is_torch, _stream_ptr, dev_u32
+
+MAX_MATS, MAX_ROUNDS, MAX_POINTS, MAX_COLS = 8, 4, 4, 8192  # csrc/prover.h PCS_MAX_*
+
+
+def _words(a, n=None):
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    if n is not None and a.size != n:
+        raise ValueError("expected %d words, got %d" % (n, a.size))
+    return a
+
+
+class PcsRejected(_lib.P3HipError):
+    """verify refused the proof: .code is the failed check (include/p3hip.h p3hip_pcs_verify)."""
+
+
+class Challenger:
+    """DuplexChallenger<BabyBear, Poseidon2-16, 16, 8> (hash="poseidon2") or SerializingChallenger32 over a Keccak-256
+    HashChallenger (hash="keccak") on the host.  Field elements are Montgomery words."""
+
+    def __init__(self, hash="poseidon2", _handle=None):
+        self.hash = hash
+        self._h = _handle
+        if _handle is None:
+            self._h = C.c_void_p()
+            _lib.check(_lib.lib().p3hip_challenger_create(_hash_kind(hash), C.byref(self._h)))
+
+    def observe(self, words):
+        w = _words(words)
+        _lib.check(_lib.lib().p3hip_challenger_observe(self._h, w.ctypes.data_as(C.c_void_p), w.size))
+
+    def observe_digest(self, digest):
+        d = _words(digest, 8)
+        _lib.check(_lib.lib().p3hip_challenger_observe_digest(self._h, d.ctypes.data_as(C.c_void_p)))
+
+    def sample_ext(self):
+        out = np.zeros(4, dtype=np.uint32)
+        _lib.check(_lib.lib().p3hip_challenger_sample_ext(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sample_bits(self, bits):
+        out = C.c_uint32()
+        _lib.check(_lib.lib().p3hip_challenger_sample_bits(self._h, bits, C.byref(out)))
+        return out.value
+
+    def clone(self):
+        h = C.c_void_p()
+        _lib.check(_lib.lib().p3hip_challenger_clone(self._h, C.byref(h)))
+        return Challenger(self.hash, h)
+
+    def free(self):
+        if self._h:
+            _lib.lib().p3hip_challenger_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PcsProverData:
+    """Prover data of one commitment: the bit-reversed LDEs in HBM and their Merkle tree."""
+
+    def __init__(self, handle, root, dims, keep):
+        self._h, self.root, self.dims, self._keep = handle, root, dims, keep  # dims: (height, width) of the committed evaluations
+
+    def free(self):
+        if self._h:
+            _lib.lib().p3hip_pcs_data_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _flatten(rounds):
+    """rounds = [(x, [points of matrix 0, points of matrix 1, ...])] -> per-matrix point counts and the points' words, round ->
+    matrix -> point."""
+    counts, pts = [], []
+    for _, mat_points in rounds:
+        for ps in mat_points:
+            counts.append(len(ps))
+            pts += [_words(z, 4) for z in ps]
+    points = np.concatenate(pts) if pts else np.zeros(4, dtype=np.uint32)
+    return (C.c_size_t * max(len(counts), 1))(*counts), points, counts
+
+
+class TwoAdicFriPcs:
+    def __init__(self, params=None, hash="poseidon2", profile="latency", own_stream=False):
+        import torch
+        self.params = params or FriParameters()
+        self.hash, self._kind = hash, _hash_kind(hash)
+        self._h = C.c_void_p()
+        torch.cuda.current_stream()  # make sure a context exists
+        _lib.check(_lib.lib().p3hip_pcs_create(profile_kind(profile), self._kind, C.cast(self.params._c(), C.c_void_p),
+                                               None if own_stream else _stream_ptr(), 1 if own_stream else 0, C.byref(self._h)))
+
+    def commit(self, evaluations):
+        """Pcs::commit.  evaluations: [(matrix, domain shift)] — the matrix a (h, w) torch device tensor (read in place) or numpy
+        array (uploaded) of evaluations over shift * <g_h> in natural row order; shift a Montgomery word (None: 1).  Returns
+        (root as numpy uint32[8], PcsProverData)."""
+        L = _lib.lib()
+        mats = [m.contiguous() if _is_torch(m) else dev_u32(m) for m, _ in evaluations]
+        for m in mats:
+            if m.dim() != 2 or m.element_size() != 4 or not m.is_cuda:
+                raise ValueError("commit: (h, w) device matrices of 32-bit words")
+        n = len(mats)
+        ptrs = (C.c_void_p * max(n, 1))(*[m.data_ptr() for m in mats])
+        hs = (C.c_size_t * max(n, 1))(*[m.shape[0] for m in mats])
+        ws = (C.c_size_t * max(n, 1))(*[m.shape[1] for m in mats])
+        shifts = np.array([MONTY_ONE if s is None else int(s) for _, s in evaluations], dtype=np.uint32)
+        root = np.zeros(8, dtype=np.uint32)
+        h = C.c_void_p()
+        _lib.check(L.p3hip_pcs_commit_dev(self._h, ptrs, hs, ws, shifts.ctypes.data_as(C.c_void_p), n, root.ctypes.data_as(C.c_void_p),
+                                          C.byref(h)))
+        return root, PcsProverData(h, root, [tuple(m.shape) for m in mats], mats)
+
+    def get_evaluations_on_domain(self, data, i, log_size):
+        """Pcs::get_evaluations_on_domain for the disjoint coset GENERATOR * <g_(2^log_size)>: a torch VIEW of the stored LDE's first
+        2^log_size rows (no copy); natural index k sits at row bitrev(k, log_size)."""
+        import torch
+        p, hh, ww = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.lib().p3hip_pcs_lde_dev(data._h, i, C.byref(p), C.byref(hh), C.byref(ww)))
+        m = 1 << log_size
+        if m < data.dims[i][0] or m > hh.value:
+            raise ValueError("get_evaluations_on_domain: 2^log_size must lie between the matrix height and the LDE height")
+
+        class _View:  # the CUDA array interface: torch wraps the memory without copying; `owner` keeps the LDE alive
+            def __init__(self, owner):
+                self.owner = owner
+                self.__cuda_array_interface__ = {"shape": (m, ww.value), "typestr": "<i4", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(_View(data), device="cuda")
+
+    def open(self, rounds, challenger):
+        """Pcs::open.  rounds = [(PcsProverData, [points of matrix 0, ...])], a point = 4 Montgomery words.  The challenger is
+        advanced to the state after the last query index.  Returns (opened values as numpy uint32 (n, 4) in observation order
+        round -> matrix -> point -> column, proof bytes: the FriProof section of the wire format)."""
+        L = _lib.lib()
+        n = len(rounds)
+        for d, mp in rounds:
+            if len(mp) != len(d.dims):
+                raise ValueError("open: one list of points per committed matrix")
+        handles = (C.c_void_p * max(n, 1))(*[d._h for d, _ in rounds])
+        counts, points, cl = _flatten(rounds)
+        total = sum(len(ps) * d.dims[i][1] for d, mp in rounds for i, ps in enumerate(mp))
+        opened = np.zeros((max(total, 1), 4), dtype=np.uint32)
+        out, ln = C.POINTER(C.c_uint8)(), C.c_size_t()
+        _lib.check(L.p3hip_pcs_open(self._h, handles, n, counts, points.ctypes.data_as(C.c_void_p), challenger._h,
+                                    opened.ctypes.data_as(C.c_void_p), opened.size, C.byref(out), C.byref(ln)))
+        return opened[:total], C.string_at(out, ln.value)
+
+    def verify(self, rounds, log_h, opened, proof, challenger):
+        """Pcs::verify (see verify)."""
+        return verify(self.params, self.hash, rounds, log_h, opened, proof, challenger)
+
+    def free(self):
+        if self._h:
+            _lib.lib().p3hip_pcs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def verify(params, hash, rounds, log_h, opened, proof, challenger):
+    """Pcs::verify on the host.  rounds = [((root, [width of matrix 0, ...]), [points of matrix 0, ...])]; opened as open returns
+    it.  Returns None on accept; raises PcsRejected (code = the failed check) on a rejection and P3HipError(-1) for a refused
+    argument.  The challenger is advanced as the verifier advances it."""
+    L = _lib.lib()
+    n = len(rounds)
+    roots = np.concatenate([_words(r, 8) for (r, _), _ in rounds]) if n else np.zeros(8, np.uint32)
+    mats = [len(ws) for (_, ws), _ in rounds]
+    widths = [int(w) for (_, ws), _ in rounds for w in ws]
+    for (_, ws), mp in rounds:
+        if len(mp) != len(ws):
+            raise ValueError("verify: one list of points per matrix")
+    counts, points, _ = _flatten(rounds)
+    opened = _words(opened, 4 * sum(len(ps) * int(ws[i]) for (_, ws), mp in rounds for i, ps in enumerate(mp)))
+    buf = (C.c_uint8 * max(len(proof), 1)).from_buffer_copy(bytes(proof) or b"\0")
+    code = C.c_int()
+    _lib.check(L.p3hip_pcs_verify(_hash_kind(hash), C.cast(params._c(), C.c_void_p), log_h, roots.ctypes.data_as(C.c_void_p),
+                                  (C.c_size_t * max(n, 1))(*mats), (C.c_size_t * max(len(widths), 1))(*widths), n, counts,
+                                  points.ctypes.data_as(C.c_void_p), opened.ctypes.data_as(C.c_void_p), buf, len(proof), challenger._h,
+                                  C.byref(code)))
+    if code.value:
+        raise PcsRejected(code.value, _lib.take_last_error() or "")
