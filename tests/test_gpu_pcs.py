@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pcs_ref as R
+from pcs_ref import fib_quotient as _fib_quotient
 
 pytestmark = pytest.mark.gpu
 P = R.P
@@ -18,55 +19,6 @@ HASHES = [("poseidon2", 0), ("keccak", 1)]
 # the eight FRI parameter sets of tests/test_gpu_prover.py
 FRI_SETS = [(1, 0, 100, 16), (2, 0, 10, 4), (2, 2, 6, 5), (1, 3, 9, 0), (3, 1, 4, 10), (1, 0, 0, 0), (1, 8, 3, 2), (4, 0, 2, 1)]
 FIRST_ROWS = [(0, 1), (7, 11), (P - 1, 1)]
-
-
-def _npow(a, e):
-    r, a = np.ones_like(a), a.copy()
-    while e:
-        if e & 1:
-            r = (r * a) % P
-        a = (a * a) % P
-        e >>= 1
-    return r
-
-
-def _bitrev(log_n):
-    i = np.arange(1 << log_n)
-    r = np.zeros_like(i)
-    for b in range(log_n):
-        r |= ((i >> b) & 1) << (log_n - 1 - b)
-    return r
-
-
-def _fib_quotient(lde_low, log_n, pis, alpha):
-    """quotient_values on GENERATOR * <g_n> (stark.c:44-60) in canonical numpy integers -> n x 4 Montgomery words, natural order"""
-    n = 1 << log_n
-    t = R.O.from_monty(lde_low).astype(np.uint64)[_bitrev(log_n)]  # natural order
-    loc, nxt = t, np.roll(t, -1, axis=0)
-    pc = [int(v) for v in R.O.from_monty(pis)]
-    g = int(R.O.from_monty(R.two_adic_generator(log_n)))
-    ginv = pow(g, P - 2, P)
-    x = np.zeros(n, dtype=np.uint64)
-    acc = 31
-    for i in range(n):
-        x[i] = acc
-        acc = acc * g % P
-    zh = (pow(31, n, P) - 1) % P
-    zh_inv = pow(zh, P - 2, P)
-    first = zh * _npow((x + P - 1) % P, P - 2) % P
-    last = zh * _npow((x + P - ginv) % P, P - 2) % P
-    trans = (x + P - ginv) % P
-    c = [first * ((loc[:, 0] + P - pc[0]) % P) % P, first * ((loc[:, 1] + P - pc[1]) % P) % P,
-         trans * ((loc[:, 1] + P - nxt[:, 0]) % P) % P, trans * ((loc[:, 0] + loc[:, 1] + P - nxt[:, 1]) % P) % P,
-         last * ((loc[:, 1] + P - pc[2]) % P) % P]
-    apow = [R.ext_from_base(R.ONE)]
-    for _ in range(4):
-        apow.append(R.ext_mul(apow[-1], alpha))
-    ap = [R.O.from_monty(a).astype(np.uint64) for a in apow]
-    q = np.zeros((n, 4), dtype=np.uint64)
-    for k in range(5):  # the first constraint takes the highest power (stark_common.h fib_fold_base)
-        q = (q + c[k][:, None] * ap[4 - k][None, :]) % P
-    return R.O.to_monty(q * zh_inv % P)
 
 
 def _fib_through_pcs(p3, pcs, hash, log_n, a, b):
