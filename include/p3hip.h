@@ -461,7 +461,7 @@ void p3hip_challenger_destroy(p3hip_challenger_t *c);
  *      over every (matrix, point) pair; also the widest single matrix).  The FRI parameter gates are the fib prover's with log_h for
  *      the trace's log height.  An opening point on the LDE coset GENERATOR * <g_big> (a base-field z with (z / GENERATOR)^big = 1:
  *      upstream panics on the zero denominator) is refused on the host before anything is launched, naming round, matrix and point.
- *      Not covered: HidingFriPcs, mixed heights, a device batch verifier. ---- */
+ *      Not covered: mixed heights, a device batch verifier.  HidingFriPcs: the section after this one. ---- */
 typedef struct p3hip_pcs p3hip_pcs_t;
 typedef struct p3hip_pcs_data p3hip_pcs_data_t;
 /* TwoAdicFriPcs::new(dft, mmcs, fri_params); stream / own_stream as p3hip_fib_prover_create */
@@ -495,6 +495,46 @@ int p3hip_pcs_verify(int hash, const p3hip_fri_params_t *params, unsigned log_h,
                      p3hip_challenger_t *challenger, int *reject_code);
 void p3hip_pcs_data_free(p3hip_pcs_data_t *d);
 void p3hip_pcs_destroy(p3hip_pcs_t *pcs);
+
+/* ---- HidingFriPcs<BabyBear, GpuDft, MerkleTreeHidingMmcs, ExtensionMmcs over it, SmallRng> over CALLER-SUPPLIED matrices: the PCS the
+ *      reference builds (native/src/fib_air.rs:63-65), for either hash configuration and either profile.  DESIGN.md section 5.2.
+ *      A hiding object is a p3hip_pcs_t; p3hip_pcs_commit_dev, p3hip_pcs_lde_dev, p3hip_pcs_open, p3hip_pcs_data_free and
+ *      p3hip_pcs_destroy serve it.  It owns three SmallRng streams in HBM — `mmcs` (salts of the input commitments), `fri` (salts of
+ *      the commit-phase layers; the FRI MMCS is a clone of the input MMCS taken at construction, so it starts from the same seed) and
+ *      `pcs` — which advance from call to call for the object's lifetime; a call refused for its arguments draws nothing.
+ *      With h = 2^log_h the caller's height, every committed matrix is a polynomial of degree < 2h: log_h >= 1 and log_h + 1 +
+ *      log_blowup <= 24, log_final_poly_len < log_h + 1.  Capacities as above except 4 matrices per hiding commitment (a query lists
+ *      every matrix and its salt); the 8192 batched columns count the random columns.  The rounds of one open are all hiding and of
+ *      one configuration (hash, blowup, number of random codewords).  Opened values include the random columns.
+ *      Not covered: mixed heights, a device batch verifier, more than 4 matrices per hiding commitment. ---- */
+/* HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over MerkleTreeHidingMmcs::new(..,
+ * SmallRng::seed_from_u64(mmcs_seed)) (fib_air.rs:40-65: 4, 1, 1); num_random_codewords in 1..8 */
+int p3hip_pcs_create_hiding(int profile, int hash, const p3hip_fri_params_t *params, unsigned num_random_codewords, uint64_t mmcs_seed,
+                            uint64_t pcs_seed, void *stream, int own_stream, p3hip_pcs_t **out);
+/* HidingFriPcs::commit is p3hip_pcs_commit_dev on a hiding object: matrix m (h x w, at most 4 of them, w <= 8192 - num_random_codewords)
+ * takes h (w + 2 NRC) draws of `pcs` row by row, in input order, and becomes the 2h x (w + NRC) matrix with rows 2i = evals[i] ||
+ * d[0..NRC) and 2i+1 = d[NRC..w+2NRC) over the size-2h domain with the caller's shift; then every matrix, in input order, takes a
+ * (2h << log_blowup) x 4 salt matrix of `mmcs` draws; leaf rows m0 || s0 || m1 || s1 ...  p3hip_pcs_lde_dev returns the stored LDE:
+ * 2h << log_blowup rows of width w + NRC, the caller's own columns first.  One synchronisation. */
+/* HidingFriPcs::commit_quotient: d_chunks[c], c < n_chunks in {2, 4}: h x width (<= 2048) evaluations in natural order on the coset
+ * GENERATOR g_(n_chunks h)^c <g_h>.  Chunk c is blinded to q_c + (X^h - s_c^h) t_c with t_c (c < n_chunks - 1) h x width draws of
+ * `pcs`, in chunk order, and the last t cancelling them in the verifier's recomposition; the n_chunks matrices of degree < 2h go
+ * into one salted tree.  One synchronisation. */
+int p3hip_pcs_commit_quotient_dev(p3hip_pcs_t *pcs, const uint32_t *const *d_chunks, size_t h, size_t width, size_t n_chunks,
+                                  uint32_t root_out[8], p3hip_pcs_data_t **data_out);
+/* HidingFriPcs::get_opt_randomization_poly_commitment for traces of 2^log_h rows: a 2h x (NRC + 4) matrix of `pcs` draws over the
+ * size-2h domain (shift 1), committed like a trace.  One synchronisation. */
+int p3hip_pcs_commit_randomization(p3hip_pcs_t *pcs, unsigned log_h, uint32_t root_out[8], p3hip_pcs_data_t **data_out);
+/* HidingFriPcs::open is p3hip_pcs_open: hiding prover data on a hiding object (plain data on a hiding object and hiding data on a
+ * plain object are refused by name).  Every committed column is opened, the random ones included; every commit-phase layer takes a
+ * salt of `fri` draws; each BatchOpening carries the values per matrix, then one salt per matrix, then the path; each commit-phase
+ * opening the sibling, the salt, the path. */
+/* HidingFriPcs::verify, host code: p3hip_pcs_verify over salted openings.  log_h is the CALLER's log height; widths are the committed
+ * widths (the caller's + NRC; NRC + 4 for the randomization matrix); at most 4 matrices per round.  Reject codes as p3hip_pcs_verify. */
+int p3hip_pcs_verify_hiding(int hash, const p3hip_fri_params_t *params, unsigned log_h, const uint32_t *roots /* 8 per round */,
+                            const size_t *mats_per_round, const size_t *widths, size_t n_rounds, const size_t *points_per_mat,
+                            const uint32_t *points, const uint32_t *opened, const uint8_t *proof, size_t len,
+                            p3hip_challenger_t *challenger, int *reject_code);
 
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */

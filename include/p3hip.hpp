@@ -388,10 +388,48 @@ class TwoAdicFriPcs {
         return code;
     }
 
-  private:
+  protected:
+    struct Adopt {};  // HidingFriPcs creates the object itself
+    TwoAdicFriPcs(Adopt, FriParameters fp, int hash) : fp_(fp), hash_(hash) {}
     p3hip_pcs_t* h_ = nullptr;
     FriParameters fp_;
     int hash_;
+};
+// HidingFriPcs<BabyBear, GpuDft, MerkleTreeHidingMmcs, ExtensionMmcs over it, SmallRng> over caller matrices (p3hip.h "HidingFriPcs over
+// CALLER-SUPPLIED matrices": what the reference builds, fib_air.rs:63-65).  commit, lde and open are the base class's on a hiding object:
+// commit randomizes (the stored LDE has 2h << log_blowup rows of width w + num_random_codewords, the caller's columns first), open opens
+// every committed column.  The three random streams live in the object and advance from call to call.
+class HidingFriPcs : public TwoAdicFriPcs {
+  public:
+    explicit HidingFriPcs(FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2, int profile = P3HIP_PROFILE_LATENCY,
+                          unsigned num_random_codewords = 4, uint64_t mmcs_seed = 1, uint64_t pcs_seed = 1, void* stream = nullptr,
+                          bool own_stream = true)
+        : TwoAdicFriPcs(Adopt{}, fp, hash) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        check(p3hip_pcs_create_hiding(profile, hash, &c, num_random_codewords, mmcs_seed, pcs_seed, stream, own_stream ? 1 : 0, &h_));
+    }
+    // HidingFriPcs::commit_quotient: 2 or 4 chunk matrices of h x width, chunk c on GENERATOR g_(C h)^c <g_h>, natural row order
+    ProverData commit_quotient(const std::vector<const uint32_t*>& d_chunks, size_t h, size_t width) {
+        ProverData d;
+        check(p3hip_pcs_commit_quotient_dev(h_, d_chunks.data(), h, width, d_chunks.size(), d.root.data(), &d.h));
+        return d;
+    }
+    // HidingFriPcs::get_opt_randomization_poly_commitment for traces of 2^log_h rows
+    ProverData get_opt_randomization_poly_commitment(unsigned log_h) {
+        ProverData d;
+        check(p3hip_pcs_commit_randomization(h_, log_h, d.root.data(), &d.h));
+        return d;
+    }
+    // HidingFriPcs::verify (host): log_h the caller's log height, widths the committed ones; codes as TwoAdicFriPcs::verify
+    int verify(unsigned log_h, const std::vector<uint32_t>& roots, const std::vector<size_t>& mats_per_round, const std::vector<size_t>& widths,
+               const std::vector<size_t>& points_per_mat, const std::vector<uint32_t>& points, const std::vector<uint32_t>& opened,
+               const std::vector<uint8_t>& proof, Challenger& challenger) const {
+        p3hip_fri_params_t c{fp_.log_blowup, fp_.log_final_poly_len, fp_.num_queries, fp_.proof_of_work_bits};
+        int code = 0;
+        check(p3hip_pcs_verify_hiding(hash_, &c, log_h, roots.data(), mats_per_round.data(), widths.data(), mats_per_round.size(),
+                                      points_per_mat.data(), points.data(), opened.data(), proof.data(), proof.size(), challenger.handle(), &code));
+        return code;
+    }
 };
 
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"

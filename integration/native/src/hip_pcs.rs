@@ -2,11 +2,12 @@
 //
 // native/src/hip_pcs.rs — `HipPcs`: the `Pcs<Challenge, Challenger>` the reference builds at native/src/fib_air.rs:62-65, with
 // commit / get_evaluations_on_domain / open on the device (libp3hip's TwoAdicFriPcs over caller matrices: include/p3hip.h
-// "TwoAdicFriPcs over CALLER-SUPPLIED matrices") and verify on the host.  NON-HIDING (TwoAdicFriPcs, not HidingFriPcs); every matrix
+// "TwoAdicFriPcs over CALLER-SUPPLIED matrices" and "HidingFriPcs over CALLER-SUPPLIED matrices") and verify on the host.  Every matrix
 // of one open has the same height, which is what p3_uni_stark hands a PCS (trace, preprocessed trace, quotient chunks).
 //
-//     let pcs = HipPcs::keccak(fri_params);        // the reference's hashes (fib_air.rs:28-53)
-//     let pcs = HipPcs::poseidon2(fri_params);     // north_star's configuration
+//     let pcs = HipPcs::keccak(fri_params);        // the reference's hashes (fib_air.rs:28-53), non-hiding
+//     let pcs = HipPcs::poseidon2(fri_params);     // north_star's configuration, non-hiding
+//     let pcs = HipPcs::hiding(P3HIP_HASH_KECCAK, fri_params, 4, 1, 1);   // the PCS the reference builds (fib_air.rs:40-65)
 //
 // The Fiat-Shamir transcript lives in a `HipChallenger` (p3hip_challenger_*): the library hands it to the device for the open and
 // back, so it must be the library's own object; it implements the p3-challenger traits uni-stark uses by forwarding.
@@ -97,6 +98,43 @@ extern "C" {
         proof_len: *mut usize,
     ) -> i32;
     fn p3hip_pcs_verify(
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        log_h: u32,
+        roots: *const u32,
+        mats_per_round: *const usize,
+        widths: *const usize,
+        n_rounds: usize,
+        points_per_mat: *const usize,
+        points: *const u32,
+        opened: *const u32,
+        proof: *const u8,
+        len: usize,
+        challenger: *mut p3hip_challenger_t,
+        reject_code: *mut i32,
+    ) -> i32;
+    fn p3hip_pcs_create_hiding(
+        profile: i32,
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        num_random_codewords: u32,
+        mmcs_seed: u64,
+        pcs_seed: u64,
+        stream: *mut c_void,
+        own_stream: i32,
+        out: *mut *mut p3hip_pcs_t,
+    ) -> i32;
+    fn p3hip_pcs_commit_quotient_dev(
+        pcs: *mut p3hip_pcs_t,
+        d_chunks: *const *const u32,
+        h: usize,
+        width: usize,
+        n_chunks: usize,
+        root_out: *mut u32,
+        data_out: *mut *mut p3hip_pcs_data_t,
+    ) -> i32;
+    fn p3hip_pcs_commit_randomization(pcs: *mut p3hip_pcs_t, log_h: u32, root_out: *mut u32, data_out: *mut *mut p3hip_pcs_data_t) -> i32;
+    fn p3hip_pcs_verify_hiding(
         hash: i32,
         params: *const p3hip_fri_params_t,
         log_h: u32,
@@ -209,6 +247,8 @@ pub struct HipPcs {
     h: *mut p3hip_pcs_t,
     hash: i32,
     params: p3hip_fri_params_t,
+    /// 0: TwoAdicFriPcs; otherwise HidingFriPcs with this many random codewords (Pcs::ZK = true)
+    num_random_codewords: usize,
 }
 impl HipPcs {
     pub fn new<M>(hash: i32, fri: &FriParameters<M>) -> Result<Self, String> {
@@ -220,7 +260,23 @@ impl HipPcs {
         };
         let mut h = core::ptr::null_mut();
         let rc = unsafe { p3hip_pcs_create(P3HIP_PROFILE_LATENCY, hash, &params, core::ptr::null_mut(), 1, &mut h) };
-        if rc != 0 { Err(last_error(rc)) } else { Ok(Self { h, hash, params }) }
+        if rc != 0 { Err(last_error(rc)) } else { Ok(Self { h, hash, params, num_random_codewords: 0 }) }
+    }
+    /// HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over a MerkleTreeHidingMmcs
+    /// seeded with mmcs_seed (fib_air.rs:40-65: 4, 1, 1).  The three random streams live in the object and advance from call to call.
+    pub fn hiding<M>(hash: i32, fri: &FriParameters<M>, num_random_codewords: usize, mmcs_seed: u64, pcs_seed: u64) -> Result<Self, String> {
+        let params = p3hip_fri_params_t {
+            log_blowup: fri.log_blowup as u32,
+            log_final_poly_len: fri.log_final_poly_len as u32,
+            num_queries: fri.num_queries as u32,
+            proof_of_work_bits: fri.proof_of_work_bits as u32,
+        };
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe {
+            p3hip_pcs_create_hiding(P3HIP_PROFILE_LATENCY, hash, &params, num_random_codewords as u32, mmcs_seed, pcs_seed,
+                                    core::ptr::null_mut(), 1, &mut h)
+        };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(Self { h, hash, params, num_random_codewords }) }
     }
     pub fn keccak<M>(fri: &FriParameters<M>) -> Result<Self, String> {
         Self::new(P3HIP_HASH_KECCAK, fri)
@@ -245,7 +301,9 @@ impl HipPcs {
             hs.push(m.height());
             ws.push(m.width());
             shifts.push(domain.shift().to_unique_u32());
-            dims.push((m.height(), m.width()));
+            // a hiding commitment stores the randomized matrix: twice the rows, the random columns behind the caller's
+            let k = self.num_random_codewords;
+            dims.push(if k > 0 { (2 * m.height(), m.width() + k) } else { (m.height(), m.width()) });
         }
         let ptrs: Vec<*const u32> = dev.iter().map(|p| *p as *const u32).collect();
         let mut root = [0u32; 8];
@@ -255,6 +313,36 @@ impl HipPcs {
         };
         for p in dev { unsafe { p3hip_free(p) }; } // the prover data owns the LDEs, not the evaluations
         if rc != 0 { Err(last_error(rc)) } else { Ok(HipPcsData { h, root, dims }) }
+    }
+
+    /// HidingFriPcs::commit_quotient: the chunk matrices (chunk c on GENERATOR g_(C h)^c <g_h>, C in {2, 4}) are uploaded, blinded on
+    /// the device and committed in one salted tree.
+    pub fn commit_quotient_host(&self, chunks: &[RowMajorMatrix<Val>]) -> Result<HipPcsData, String> {
+        let mut dev: Vec<*mut c_void> = Vec::new();
+        let (h, w) = chunks.first().map(|m| (m.height(), m.width())).unwrap_or((0, 0));
+        for m in chunks {
+            let bytes = m.height() * m.width() * 4;
+            let mut p = core::ptr::null_mut();
+            let rc = unsafe { p3hip_malloc(&mut p, bytes) };
+            if rc != 0 { return Err(last_error(rc)); }
+            let rc = unsafe { p3hip_upload(p, m.values.as_ptr() as *const c_void, bytes) };
+            if rc != 0 { return Err(last_error(rc)); }
+            dev.push(p);
+        }
+        let ptrs: Vec<*const u32> = dev.iter().map(|p| *p as *const u32).collect();
+        let mut root = [0u32; 8];
+        let mut d = core::ptr::null_mut();
+        let rc = unsafe { p3hip_pcs_commit_quotient_dev(self.h, ptrs.as_ptr(), h, w, ptrs.len(), root.as_mut_ptr(), &mut d) };
+        for p in dev { unsafe { p3hip_free(p) }; }
+        if rc != 0 { Err(last_error(rc)) } else { Ok(HipPcsData { h: d, root, dims: vec![(2 * h, w); chunks.len()] }) }
+    }
+
+    /// HidingFriPcs::get_opt_randomization_poly_commitment for traces of 2^log_h rows.
+    pub fn randomization_commitment(&self, log_h: u32) -> Result<HipPcsData, String> {
+        let mut root = [0u32; 8];
+        let mut d = core::ptr::null_mut();
+        let rc = unsafe { p3hip_pcs_commit_randomization(self.h, log_h, root.as_mut_ptr(), &mut d) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(HipPcsData { h: d, root, dims: vec![(2usize << log_h, self.num_random_codewords + 4)] }) }
     }
 
     /// Pcs::get_evaluations_on_domain for GENERATOR * <g_m>: the first m rows of the stored LDE (natural index i at row bitrev(i)).
@@ -316,9 +404,11 @@ impl HipPcs {
         let counts: Vec<usize> = points.iter().flatten().map(|p| p.len()).collect();
         let flat_p: Vec<u32> = points.iter().flatten().flatten().flatten().copied().collect();
         let mut code = 0i32;
+        // a hiding PCS: log_h is still the caller's log height, the widths are the committed ones
+        let verify = if self.num_random_codewords > 0 { p3hip_pcs_verify_hiding } else { p3hip_pcs_verify };
         let rc = unsafe {
-            p3hip_pcs_verify(self.hash, &self.params, log_h, flat_roots.as_ptr(), mats.as_ptr(), flat_w.as_ptr(), mats.len(), counts.as_ptr(),
-                             flat_p.as_ptr(), opened.as_ptr(), proof.as_ptr(), proof.len(), challenger.h, &mut code)
+            verify(self.hash, &self.params, log_h, flat_roots.as_ptr(), mats.as_ptr(), flat_w.as_ptr(), mats.len(), counts.as_ptr(),
+                   flat_p.as_ptr(), opened.as_ptr(), proof.as_ptr(), proof.len(), challenger.h, &mut code)
         };
         if rc != 0 { return Err(last_error(rc)); }
         if code != 0 { return Err(last_error(code)); }

@@ -1248,6 +1248,51 @@ int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t* params, vo
         return OK;
     });
 }
+int p3hip_pcs_create_hiding(int profile, int hash, const p3hip_fri_params_t* params, unsigned num_random_codewords, uint64_t mmcs_seed,
+                            uint64_t pcs_seed, void* stream, int own_stream, p3hip_pcs_t** out) {
+    return guarded([&]() -> int {
+        if (!params || !out) return fail(ERR_BAD_ARG, "pcs_create_hiding: null argument");
+        if (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY) return fail(ERR_BAD_ARG, "pcs_create_hiding: unknown profile");
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        bool own = false;
+        if (own_stream) {
+            P3_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            own = true;
+        }
+        std::unique_ptr<p3hip_pcs> p(new p3hip_pcs());
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        // on failure the object's destructor destroys the owned stream
+        if ((rc = p->pcs.init_hiding(fp, st, own, hash, profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY,
+                                     num_random_codewords, mmcs_seed, pcs_seed)))
+            return rc;
+        *out = p.release();
+        return OK;
+    });
+}
+int p3hip_pcs_commit_quotient_dev(p3hip_pcs_t* pcs, const uint32_t* const* d_chunks, size_t h, size_t width, size_t n_chunks,
+                                  uint32_t root_out[8], p3hip_pcs_data_t** data_out) {
+    return guarded([&]() -> int {
+        if (!pcs || !data_out) return fail(ERR_BAD_ARG, "pcs_commit_quotient: null argument");
+        PcsData* d = nullptr;
+        int rc = pcs->pcs.commit_quotient(d_chunks, h, width, n_chunks, root_out, &d);
+        if (rc) return rc;
+        *data_out = new p3hip_pcs_data{std::unique_ptr<PcsData>(d)};
+        return OK;
+    });
+}
+int p3hip_pcs_commit_randomization(p3hip_pcs_t* pcs, unsigned log_h, uint32_t root_out[8], p3hip_pcs_data_t** data_out) {
+    return guarded([&]() -> int {
+        if (!pcs || !data_out) return fail(ERR_BAD_ARG, "pcs_commit_randomization: null argument");
+        PcsData* d = nullptr;
+        int rc = pcs->pcs.commit_randomization(log_h, root_out, &d);
+        if (rc) return rc;
+        *data_out = new p3hip_pcs_data{std::unique_ptr<PcsData>(d)};
+        return OK;
+    });
+}
 int p3hip_pcs_commit_dev(p3hip_pcs_t* pcs, const uint32_t* const* d_evals, const size_t* heights, const size_t* widths,
                          const uint32_t* domain_shifts, size_t n_mats, uint32_t root_out[8], p3hip_pcs_data_t** data_out) {
     return guarded([&]() -> int {
@@ -1300,6 +1345,22 @@ int p3hip_pcs_verify(int hash, const p3hip_fri_params_t* params, unsigned log_h,
         std::string why;
         Challenger ch = challenger->c;
         int rc = pcs_verify(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, &ch, &why);
+        if (rc < 0) return fail(rc, why);
+        challenger->c = ch;  // accepted or rejected, the transcript is where the verifier left it
+        if (rc > 0) { *reject_code = rc; set_error("pcs verification failed: " + why); }
+        return OK;
+    });
+}
+int p3hip_pcs_verify_hiding(int hash, const p3hip_fri_params_t* params, unsigned log_h, const uint32_t* roots, const size_t* mats_per_round,
+                            const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points,
+                            const uint32_t* opened, const uint8_t* proof, size_t len, p3hip_challenger_t* challenger, int* reject_code) {
+    return guarded([&]() -> int {
+        if (!params || !challenger || !reject_code) return fail(ERR_BAD_ARG, "pcs_verify_hiding: null argument");
+        *reject_code = 0;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::string why;
+        Challenger ch = challenger->c;
+        int rc = pcs_verify_hiding(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, &ch, &why);
         if (rc < 0) return fail(rc, why);
         challenger->c = ch;  // accepted or rejected, the transcript is where the verifier left it
         if (rc > 0) { *reject_code = rc; set_error("pcs verification failed: " + why); }

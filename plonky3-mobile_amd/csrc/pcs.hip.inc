@@ -1,6 +1,7 @@
 // TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over CALLER-SUPPLIED matrices: commit, open (prover.h Pcs).
 // Included by prover.hip (same namespace: ProverCore, QTree, the transcript kernels, the grind and query kernels are shared; the
-// fib kernels above are left as they are).  Non-hiding; every matrix of one open has the same height h.
+// fib kernels above are left as they are).  Every matrix of one open has the same height h.  On a hiding object (pcs_hiding.hip.inc, included at
+// the end: HidingFriPcs) commit randomizes and salts, and open runs here over the committed matrices with salts in every opening.
 //
 // Conventions are the test oracle's restatement of upstream (stark.c, cited by line):
 //   commit   LDE = coset_lde_batch(evals, log_blowup, GENERATOR / s), bit-reversed by row (stark.c:33,64), one mmcs_commit per call
@@ -323,6 +324,7 @@ __global__ void __launch_bounds__(64) pcs_export_kernel(const DevState* ds, uint
 // ------------------------------------------------------------------------------------------------
 PcsData::~PcsData() {
     for (uint32_t* p : lde) (void)hipFree(p);
+    if (salt_base) (void)hipFree(salt_base);
     delete tree;
 }
 
@@ -382,6 +384,27 @@ struct Pcs::Impl {
         }
         ~Buf() { if (p) (void)hipFree(p); }
     } d, xd, partials, sums, alp, ay, pairs;
+    // HidingFriPcs (pcs_hiding.hip.inc): the three streams ([0] input mmcs, [1] fri mmcs, [2] pcs), the scratch of a hiding commit
+    // (grown like the open scratch) and the nine words a hiding commit reads back: its root and the streams' shortage flag
+    bool hiding = false;
+    uint32_t nrc = 0;
+    DevRng* rngs = nullptr;
+    Buf rng_ws, draws, rt, co, ext, lde_scratch;
+    uint32_t *rootbuf = nullptr, *host_root = nullptr;
+    // the next n field elements of stream r (rng_fill_field, piece by piece beyond what one fill's workspace should take: 2^26 elements;
+    // P3HIP_PCS_FILL_PIECE_LOG (tests): log2 of the piece, to enter the multi-piece path on small shapes)
+    int fill(Context& cx, DevRng* r, uint32_t* out, uint64_t n, uint32_t* err) {
+        uint64_t PIECE = 1ull << 26;
+        if (const char* e = getenv("P3HIP_PCS_FILL_PIECE_LOG")) PIECE = 1ull << std::min(std::max(atoi(e), 4), 26);
+        size_t w = 0;
+        int rc;
+        if (!n) return OK;
+        if ((rc = rng_workspace_words(std::min<uint64_t>(n, PIECE), &w))) return rc;
+        if ((rc = rng_ws.reserve(w))) return rc;
+        for (uint64_t o = 0; o < n; o += PIECE)
+            if ((rc = rng_fill_field(cx, stream, r, out + o, std::min<uint64_t>(PIECE, n - o), rng_ws.p, err))) return rc;
+        return OK;
+    }
     // the FRI arena, the staging layout and the pinned landing buffer of ONE shape (log_h, widths, points per matrix): kept while
     // opens of that shape follow one another, rebuilt when another shape arrives
     std::vector<uint32_t> shape;
@@ -392,6 +415,9 @@ struct Pcs::Impl {
     ~Impl() {
         core.reset();
         if (host_stage) (void)hipHostFree(host_stage);
+        if (host_root) (void)hipHostFree(host_root);
+        if (rootbuf) (void)hipFree(rootbuf);
+        if (rngs) (void)hipFree(rngs);
         if (ds) (void)hipFree(ds);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
@@ -418,6 +444,7 @@ int Pcs::init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash
 int Pcs::commit(const uint32_t* const* d_evals, const size_t* heights, const size_t* widths, const uint32_t* shifts, size_t n_mats,
                 uint32_t root_out[8], PcsData** out) {
     Impl& s = *im;
+    if (s.hiding) return commit_hiding(d_evals, heights, widths, shifts, n_mats, root_out, out);
     if (!d_evals || !heights || !widths || !root_out || !out) return fail(ERR_BAD_ARG, "pcs commit: null argument");
     if (n_mats == 0) return fail(ERR_BAD_ARG, "pcs commit: zero matrices");
     if (n_mats > PCS_MAX_MATS)
@@ -486,7 +513,9 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     for (size_t r = 0; r < n_rounds; r++) {
         const PcsData* dt = rounds[r];
         if (!dt) return fail(ERR_BAD_ARG, "pcs open: round " + std::to_string(r) + " is null");
-        if (dt->hash != s.hash || dt->device != s.device || dt->log_big - dt->log_h != s.fp.log_blowup)
+        if (dt->hiding != s.hiding)
+            return fail(ERR_BAD_ARG, "pcs open: round " + std::to_string(r) + (s.hiding ? " holds plain prover data, this PCS is hiding" : " holds hiding prover data, this PCS is not hiding"));
+        if (dt->hash != s.hash || dt->device != s.device || dt->log_big - dt->log_h != s.fp.log_blowup || dt->nrc != s.nrc)
             return fail(ERR_BAD_ARG, "pcs open: round " + std::to_string(r) + " was committed by another PCS configuration");
         shape.push_back((uint32_t)dt->lde.size());
         for (size_t m = 0; m < dt->lde.size(); m++, mi++) {
@@ -530,19 +559,24 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         s.shape.clear();
         std::unique_ptr<ProverCore> c(new ProverCore());
         if ((rc = c->begin("pcs open", st, false, s.hash, s.profile))) return rc;
+        c->salt_words = s.hiding ? PCS_SALT : 0;  // stark_hiding.c:230-247: every commit-phase layer with a salt
         if ((rc = c->set_fri("pcs open", s.fp, log_h))) return rc;
         if ((rc = c->alloc_fri())) return rc;
         for (size_t r = 0; r < n_rounds; r++) {
             QTree t{};
             t.n_mats = (uint32_t)rounds[r]->lde.size();
             for (uint32_t m = 0; m < t.n_mats; m++) { t.mat[m] = rounds[r]->lde[m]; t.width[m] = t.stride[m] = (uint32_t)rounds[r]->widths[m]; }
+            if (s.hiding) {  // stark_hiding.c:70-73: the values of every matrix, then one salt per matrix
+                for (uint32_t m = 0; m < t.n_mats; m++) { t.mat[t.n_mats + m] = rounds[r]->salts[m]; t.width[t.n_mats + m] = t.stride[t.n_mats + m] = PCS_SALT; }
+                t.n_mats *= 2;
+            }
             t.layers = rounds[r]->tree->layers; t.log_height = log_big; t.shift = 0;
             c->trees.push_back(t);
         }
         c->lay.root_t = c->lay.root_q = c->lay.opened = 0;  // the staging buffer starts with the opened values
         c->lay.froots = 4 * total;
-        if ((rc = c->layout("pcs open", PCS_STATE_WORDS))) return rc;
-        P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.host_stage), ((size_t)c->lay.words + PCS_STATE_WORDS) * 4 + 64));
+        if ((rc = c->layout("pcs open", PCS_STATE_WORDS + 1))) return rc;  // + the random streams' shortage flag
+        P3_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.host_stage), ((size_t)c->lay.words + PCS_STATE_WORDS + 1) * 4 + 64));
         s.core = std::move(c);
         s.shape = shape;
     }
@@ -572,7 +606,9 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     P3_HIP(hipMemcpyAsync(s.pairs.p, s.host_pairs.data(), (size_t)n_pairs * sizeof(PcsPair), hipMemcpyHostToDevice, st));
     for (size_t r = 0; r < n_rounds; r++) {
         QTree& t = core.trees[r];
-        for (uint32_t m = 0; m < t.n_mats; m++) t.mat[m] = rounds[r]->lde[m];
+        const uint32_t nm = (uint32_t)rounds[r]->lde.size();
+        for (uint32_t m = 0; m < nm; m++) t.mat[m] = rounds[r]->lde[m];
+        if (s.hiding) for (uint32_t m = 0; m < nm; m++) t.mat[nm + m] = rounds[r]->salts[m];
         t.layers = rounds[r]->tree->layers;
     }
     P3_HIP(hipMemcpyAsync(core.qtrees, core.trees.data(), n_rounds * sizeof(QTree), hipMemcpyHostToDevice, st));
@@ -643,6 +679,13 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         }
     }
     // ---- FRI commit phase, final polynomial, grind, queries: ProverCore, as a fib proof runs them ----
+    // hiding: the salts of every layer first, (big >> (r + 1)) x 4 draws of the `fri` stream in round order (stark_hiding.c:241); the
+    // shortage flag sits behind the exported state and travels with the open's one copy
+    uint32_t* const err = core.pstage + L.words + PCS_STATE_WORDS;
+    if (s.hiding) {
+        P3_HIP(hipMemsetAsync(err, 0, 4, st));
+        if ((rc = s.fill(cx, s.rngs + 1, core.fri_salts, core.fri_salt_words, err))) return rc;
+    }
     if ((rc = core.fri_rounds(cx, ts, core.n_rounds))) return rc;
     if ((rc = core.fri_final(cx, ts))) return rc;
     if ((rc = core.grind_start(ts))) return rc;
@@ -654,7 +697,7 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
                            (uint32_t)core.slot_words, core.pstage + L.slots);
         P3_HIP(hipGetLastError());
     }
-    const size_t words = (size_t)L.words + PCS_STATE_WORDS;
+    const size_t words = (size_t)L.words + PCS_STATE_WORDS + (s.hiding ? 1 : 0);
     hipLaunchKernelGGL(pcs_export_kernel, dim3(1), dim3(64), 0, st, s.ds, core.pstage + L.words);
     P3_HIP(hipGetLastError());
     P3_HIP(hipMemcpyAsync(s.host_stage, core.pstage, words * 4, hipMemcpyDeviceToHost, st));
@@ -668,6 +711,7 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         P3_HIP(hipStreamSynchronize(st));
     }
     if (hp[L.status] != 0) return fail(ERR_INTERNAL, "pcs open: witness rejected by the device transcript");
+    if (s.hiding && hp[L.words + PCS_STATE_WORDS] != 0) return fail(ERR_INTERNAL, "pcs open: a random stream ran out of raw draws");
     opened->assign(hp + L.opened, hp + L.opened + 4 * (size_t)total);
     proof->clear();
     proof->reserve(64 + (size_t)nq * core.slot_words * 4 + 4096);
@@ -677,3 +721,5 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
 }
 
 }  // namespace p3
+
+#include "pcs_hiding.hip.inc"

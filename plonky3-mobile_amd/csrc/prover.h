@@ -103,13 +103,25 @@ constexpr size_t PCS_MAX_ROUNDS = 4;    // commitments per open
 constexpr size_t PCS_MAX_POINTS = 4;    // distinct opening points per open
 constexpr size_t PCS_MAX_COLS = 8192;   // batched columns: sum of width over every (matrix, point) pair; also the widest matrix
 
-// prover data of one commitment: the bit-reversed LDEs (owned, in HBM) and their tree
+// HidingFriPcs (pcs_hiding.hip.inc): a commitment lists every matrix and its salt in one QTree (QTREE_MAX_MATS entries)
+constexpr size_t PCS_HIDING_MAX_MATS = 4;
+constexpr uint32_t PCS_SALT = 4;               // MerkleTreeHidingMmcs SALT_ELEMS
+constexpr uint32_t PCS_MAX_RANDOM_CODEWORDS = 8;
+constexpr size_t PCS_MAX_QUOTIENT_WIDTH = 2048;
+
+// prover data of one commitment: the bit-reversed LDEs (owned, in HBM) and their tree.  Of a hiding commitment: log_h is the
+// COMMITTED log height (the caller's + 1), widths the committed widths (the caller's + the random columns), salts[m] the
+// 2^log_big x PCS_SALT salt matrix of matrix m (pieces of salt_base)
 struct PcsData {
     std::vector<uint32_t*> lde;
     std::vector<size_t> widths;
     uint32_t log_h = 0, log_big = 0;
     int hash = 0, device = -1;
     Tree* tree = nullptr;
+    bool hiding = false;
+    uint32_t nrc = 0;
+    uint32_t* salt_base = nullptr;
+    std::vector<uint32_t*> salts;
     PcsData() = default;
     PcsData(const PcsData&) = delete;
     ~PcsData();
@@ -121,10 +133,19 @@ class Pcs {
     ~Pcs();
     Pcs(const Pcs&) = delete;
     int init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile);
+    // HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over a MerkleTreeHidingMmcs
+    // seeded with mmcs_seed (the FRI MMCS a clone of it): the object owns the three streams, which advance over its lifetime
+    int init_hiding(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile, uint32_t num_random_codewords,
+                    uint64_t mmcs_seed, uint64_t pcs_seed);
+    bool hiding() const;
     // Pcs::commit: d_evals[m] = heights[m] x widths[m] evaluations over shifts[m] * <g_h> in natural row order (device memory; shifts
     // null: all 1); one synchronisation (the root)
     int commit(const uint32_t* const* d_evals, const size_t* heights, const size_t* widths, const uint32_t* shifts, size_t n_mats,
                uint32_t root_out[8], PcsData** out);
+    // hiding objects only.  HidingFriPcs::commit_quotient: n_chunks matrices of h x width, chunk c the evaluations (natural order)
+    // on GENERATOR g_(n_chunks h)^c <g_h>; get_opt_randomization_poly_commitment for matrices of 2^log_h rows
+    int commit_quotient(const uint32_t* const* d_chunks, size_t h, size_t width, size_t n_chunks, uint32_t root_out[8], PcsData** out);
+    int commit_randomization(uint32_t log_h, uint32_t root_out[8], PcsData** out);
     // Pcs::open: points_per_mat per matrix in round -> matrix order, points 4 words each in round -> matrix -> point order; chal: the
     // transcript before the open, on return the transcript after the last query index; opened: extension elements in observation
     // order; proof: the FriProof section of the wire format.  One synchronisation.
@@ -135,6 +156,9 @@ class Pcs {
   private:
     struct Impl;
     Impl* im;
+    int commit_hiding(const uint32_t* const* d_evals, const size_t* heights, const size_t* widths, const uint32_t* shifts, size_t n_mats,
+                      uint32_t root_out[8], PcsData** out);
+    int hiding_finish(PcsData* data, uint32_t root_out[8]);
 };
 
 bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big);
@@ -144,5 +168,10 @@ bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big);
 int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
                size_t len, Challenger* chal, std::string* why);
+// HidingFriPcs::verify: log_h the CALLER's log height (the committed polynomials have degree < 2^(log_h + 1)), widths the committed
+// widths, every input opening and FRI layer opening with a salt of PCS_SALT words; at most PCS_HIDING_MAX_MATS matrices a round
+int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round,
+                      const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
+                      const uint8_t* proof, size_t len, Challenger* chal, std::string* why);
 
 }  // namespace p3

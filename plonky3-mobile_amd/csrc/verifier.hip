@@ -389,9 +389,12 @@ int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint
 // round -> matrix -> point -> column, alpha sampled, and per query
 //   ro = sum over (matrix, point) pairs in that order, over columns c:  alpha^k (opened_k - row[c]) / (z - x),  k running on.
 // Every size of the query section follows from the arguments: no loop bound or offset is read from the proof.
-int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
-               size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
-               size_t len, Challenger* chal, std::string* why) {
+// salt_words > 0: HidingFriPcs::verify over the MerkleTreeHidingMmcs (the test oracle's hiding verifier, stark_hiding.c:380-457, generalised
+// likewise): log_h is the COMMITTED log height, each input BatchOpening carries one salt per matrix behind the values and hashes to the
+// leaf row m0 || s0 || m1 || s1 ... (stark_hiding.c:300-322), each commit-phase opening carries its salt (FriCheck).
+static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
+                          size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
+                          size_t len, Challenger* chal, std::string* why, uint32_t salt_words, size_t max_mats) {
     auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
     if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
     if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
@@ -410,7 +413,7 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
     size_t n_points = 0, total = 0, mi = 0, pi = 0, row_max = 0;
     for (size_t r = 0; r < n_rounds; r++) {
         if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
-        if (mats_per_round[r] > PCS_MAX_MATS) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(PCS_MAX_MATS) + " matrices");
+        if (mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
         size_t row = 0;
         for (size_t m = 0; m < mats_per_round[r]; m++, mi++) {
             const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
@@ -445,7 +448,7 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
     alp[0] = bb::ext_one();
     for (size_t k = 1; k < total; k++) alp[k] = bb::mul(alp[k - 1], al);
     Reader rd{proof, len};
-    FriCheck fri{hash, fp, log_big, 0, why};
+    FriCheck fri{hash, fp, log_big, salt_words, why};
     if (int rc = fri.commit_phase(rd, ch)) return rc;
     const size_t qstart = rd.pos;
     {   // the query section's length: per query the rounds' BatchOpenings, then the FRI walk
@@ -453,19 +456,19 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
         mi = 0;
         for (size_t r = 0; r < n_rounds; r++) {
             qbytes += 4;
-            for (size_t m = 0; m < mats_per_round[r]; m++, mi++) qbytes += 4 + 4 * widths[mi];
+            for (size_t m = 0; m < mats_per_round[r]; m++, mi++) qbytes += 4 + 4 * widths[mi] + (salt_words ? 4 + 4 * (size_t)salt_words : 0);
             qbytes += 4 + 32 * (size_t)log_big;
         }
         qbytes += 4;
-        for (uint32_t r = 0; r < fri.n_rounds; r++) qbytes += 16 + 4 + 32 * (size_t)(log_big - 1 - r);
+        for (uint32_t r = 0; r < fri.n_rounds; r++) qbytes += 16 + (salt_words ? 4 + 4 * (size_t)salt_words : 0) + 4 + 32 * (size_t)(log_big - 1 - r);
         const size_t all = qbytes * fp.num_queries;
         if (all > len - rd.pos) return reject(why, 9, "truncated proof");
         rd.pos += all;
     }
     if (int rc = fri.final_poly(rd, ch)) return rc;
     rd.pos = qstart;
-    std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(row_max);
-    std::vector<size_t> hh(PCS_MAX_MATS, (size_t)1 << log_big);
+    std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(row_max), leaf(row_max + PCS_MAX_MATS * salt_words), salts(PCS_MAX_MATS * salt_words);
+    std::vector<size_t> hh(2 * PCS_MAX_MATS, (size_t)1 << log_big), lw(2 * PCS_MAX_MATS);
     const uint32_t gen = bb::to_monty(bb::GEN);
     for (uint32_t q = 0; q < fp.num_queries; q++) {
         const size_t index = ch.sample_bits(log_big);
@@ -483,10 +486,25 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
                 rd.felts(row.data() + off, widths[m0 + m]);
                 off += widths[m0 + m];
             }
+            for (size_t m = 0; salt_words && m < nm; m++) {
+                if (rd.u32() != salt_words) return reject(why, 12, "query shape");
+                rd.felts(salts.data() + m * salt_words, salt_words);
+            }
             if (rd.u32() != log_big) return reject(why, 12, "query shape");
             rd.digests(hash, path.data(), log_big);
             if (rd.bad) return reject(why, 9, "truncated proof");
-            if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index, row.data(), path.data(), log_big, nullptr, false) != 0)
+            if (salt_words) {  // the salts as width-4 matrices, each behind its matrix
+                size_t p = 0;
+                off = 0;
+                for (size_t m = 0; m < nm; m++) {
+                    const size_t w = widths[m0 + m];
+                    memcpy(leaf.data() + p, row.data() + off, w * 4); p += w; off += w;
+                    memcpy(leaf.data() + p, salts.data() + m * salt_words, (size_t)salt_words * 4); p += salt_words;
+                    lw[2 * m] = w; lw[2 * m + 1] = salt_words;
+                }
+                if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), 2 * nm, index, leaf.data(), path.data(), log_big, nullptr, false) != 0)
+                    return reject(why, 13, "input opening");
+            } else if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index, row.data(), path.data(), log_big, nullptr, false) != 0)
                 return reject(why, 13, "input opening");
             off = 0;
             for (size_t m = 0; m < nm; m++, mi++) {
@@ -502,6 +520,23 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
     }
     if (why) why->clear();
     return 0;
+}
+
+int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
+               size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
+               size_t len, Challenger* chal, std::string* why) {
+    return pcs_verify_any(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why, 0,
+                          PCS_MAX_MATS);
+}
+int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
+                      size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
+                      size_t len, Challenger* chal, std::string* why) {
+    if (log_h < 1 || log_h >= bb::TWO_ADICITY) {
+        if (why) *why = "pcs verify: log_h must be in [1, " + std::to_string(bb::TWO_ADICITY - 1) + "] (the caller's log height; the committed polynomials have degree < 2^(log_h + 1))";
+        return (int)ERR_BAD_ARG;
+    }
+    return pcs_verify_any(hash, fp, log_h + 1, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why,
+                          PCS_SALT, PCS_HIDING_MAX_MATS);
 }
 
 }  // namespace p3

@@ -1,7 +1,8 @@
 """Host-side mirror of Plonky3's Pcs contract for TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over
 caller-supplied matrices (include/p3hip.h "TwoAdicFriPcs over CALLER-SUPPLIED matrices"), and of the challengers a caller
-drives between its calls.  Non-hiding; every matrix of one open / verify has the same height.  commit / open keep everything
-device-resident (one synchronisation each); verify is host code of the library."""
+drives between its calls; HidingFriPcs mirrors the hiding PCS the reference builds ("HidingFriPcs over CALLER-SUPPLIED matrices").
+Every matrix of one open / verify has the same height.  commit / open keep everything device-resident (one synchronisation each);
+verify is host code of the library."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ from .fib_air import FriParameters, _hash_kind, profile_kind
 from .gpu_dft import MONTY_ONE, P, _is_torch, _stream_ptr, dev_u32
 
 MAX_MATS, MAX_ROUNDS, MAX_POINTS, MAX_COLS = 8, 4, 4, 8192  # csrc/prover.h PCS_MAX_*
+HIDING_MAX_MATS, SALT, MAX_RANDOM_CODEWORDS, MAX_QUOTIENT_WIDTH = 4, 4, 8, 2048  # csrc/prover.h PCS_HIDING_MAX_MATS ...
 
 
 def _words(a, n=None):
@@ -101,6 +103,8 @@ def _flatten(rounds):
 
 
 class TwoAdicFriPcs:
+    _hiding = False
+
     def __init__(self, params=None, hash="poseidon2", profile="latency", own_stream=False):
         import torch
         self.params = params or FriParameters()
@@ -166,7 +170,7 @@ class TwoAdicFriPcs:
 
     def verify(self, rounds, log_h, opened, proof, challenger):
         """Pcs::verify (see verify)."""
-        return verify(self.params, self.hash, rounds, log_h, opened, proof, challenger)
+        return verify(self.params, self.hash, rounds, log_h, opened, proof, challenger, hiding=self._hiding)
 
     def free(self):
         if self._h:
@@ -180,10 +184,57 @@ class TwoAdicFriPcs:
             pass
 
 
-def verify(params, hash, rounds, log_h, opened, proof, challenger):
+class HidingFriPcs(TwoAdicFriPcs):
+    """HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over a MerkleTreeHidingMmcs
+    seeded with mmcs_seed (native/src/fib_air.rs:40-65: 4, 1, 1).  The object owns the three random streams, which advance from call
+    to call.  commit (inherited) randomizes: the prover data's dims are those of the committed matrices, (2h, w +
+    num_random_codewords), and get_evaluations_on_domain returns all of those columns, the caller's own first."""
+    _hiding = True
+
+    def __init__(self, params=None, hash="poseidon2", profile="latency", num_random_codewords=4, mmcs_seed=1, pcs_seed=1, own_stream=False):
+        import torch
+        self.params = params or FriParameters()
+        self.hash, self._kind = hash, _hash_kind(hash)
+        self.num_random_codewords = num_random_codewords
+        self._h = C.c_void_p()
+        torch.cuda.current_stream()  # make sure a context exists
+        _lib.check(_lib.lib().p3hip_pcs_create_hiding(profile_kind(profile), self._kind, C.cast(self.params._c(), C.c_void_p),
+                                                      num_random_codewords, mmcs_seed, pcs_seed, None if own_stream else _stream_ptr(),
+                                                      1 if own_stream else 0, C.byref(self._h)))
+
+    def commit(self, evaluations):
+        """HidingFriPcs::commit: as TwoAdicFriPcs.commit, at most 4 matrices."""
+        root, data = super().commit(evaluations)
+        data.dims = [(2 * h, w + self.num_random_codewords) for h, w in data.dims]
+        return root, data
+
+    def commit_quotient(self, chunks):
+        """HidingFriPcs::commit_quotient.  chunks: 2 or 4 (h, w) matrices, chunk c the evaluations in natural order on the coset
+        GENERATOR * g_(len(chunks) h)^c * <g_h>.  Returns (root, PcsProverData) of the blinded chunk matrices, (2h, w) each."""
+        mats = [m.contiguous() if _is_torch(m) else dev_u32(m) for m in chunks]
+        for m in mats:
+            if m.dim() != 2 or m.element_size() != 4 or not m.is_cuda or m.shape != mats[0].shape:
+                raise ValueError("commit_quotient: (h, w) device matrices of 32-bit words, all of one shape")
+        n = len(mats)
+        h, w = (int(v) for v in mats[0].shape) if n else (0, 0)
+        ptrs = (C.c_void_p * max(n, 1))(*[m.data_ptr() for m in mats])
+        root, hd = np.zeros(8, dtype=np.uint32), C.c_void_p()
+        _lib.check(_lib.lib().p3hip_pcs_commit_quotient_dev(self._h, ptrs, h, w, n, root.ctypes.data_as(C.c_void_p), C.byref(hd)))
+        return root, PcsProverData(hd, root, [(2 * h, w)] * n, mats)
+
+    def get_opt_randomization_poly_commitment(self, log_h):
+        """HidingFriPcs::get_opt_randomization_poly_commitment for traces of 2^log_h rows -> (root, PcsProverData) of the (2h,
+        num_random_codewords + 4) random matrix."""
+        root, hd = np.zeros(8, dtype=np.uint32), C.c_void_p()
+        _lib.check(_lib.lib().p3hip_pcs_commit_randomization(self._h, log_h, root.ctypes.data_as(C.c_void_p), C.byref(hd)))
+        return root, PcsProverData(hd, root, [(2 << log_h, self.num_random_codewords + 4)], [])
+
+
+def verify(params, hash, rounds, log_h, opened, proof, challenger, hiding=False):
     """Pcs::verify on the host.  rounds = [((root, [width of matrix 0, ...]), [points of matrix 0, ...])]; opened as open returns
     it.  Returns None on accept; raises PcsRejected (code = the failed check) on a rejection and P3HipError(-1) for a refused
-    argument.  The challenger is advanced as the verifier advances it."""
+    argument.  The challenger is advanced as the verifier advances it.  hiding: HidingFriPcs::verify — log_h the caller's log
+    height, the widths the committed ones."""
     L = _lib.lib()
     n = len(rounds)
     roots = np.concatenate([_words(r, 8) for (r, _), _ in rounds]) if n else np.zeros(8, np.uint32)
@@ -196,9 +247,9 @@ def verify(params, hash, rounds, log_h, opened, proof, challenger):
     opened = _words(opened, 4 * sum(len(ps) * int(ws[i]) for (_, ws), mp in rounds for i, ps in enumerate(mp)))
     buf = (C.c_uint8 * max(len(proof), 1)).from_buffer_copy(bytes(proof) or b"\0")
     code = C.c_int()
-    _lib.check(L.p3hip_pcs_verify(_hash_kind(hash), C.cast(params._c(), C.c_void_p), log_h, roots.ctypes.data_as(C.c_void_p),
-                                  (C.c_size_t * max(n, 1))(*mats), (C.c_size_t * max(len(widths), 1))(*widths), n, counts,
-                                  points.ctypes.data_as(C.c_void_p), opened.ctypes.data_as(C.c_void_p), buf, len(proof), challenger._h,
-                                  C.byref(code)))
+    fn = L.p3hip_pcs_verify_hiding if hiding else L.p3hip_pcs_verify
+    _lib.check(fn(
+        _hash_kind(hash), C.cast(params._c(), C.c_void_p), log_h, roots.ctypes.data_as(C.c_void_p), (C.c_size_t * max(n, 1))(*mats), (C.c_size_t * max(len(widths), 1))(*widths), n, counts, points.ctypes.data_as(C.c_void_p),
+        opened.ctypes.data_as(C.c_void_p), buf, len(proof), challenger._h, C.byref(code)))
     if code.value:
         raise PcsRejected(code.value, _lib.take_last_error() or "")

@@ -7,6 +7,10 @@ device timestamps (events on the stream the PCS enqueues on), warm-up, repetitio
                                                    `rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python ...`
   python tools/pcs_bench.py --merge DIR ...        adds the per-kernel split of such runs (DIR/NAME/**/*kernel_trace.csv)
   -o FILE                                          where the report goes (default profiles/pcs_open_bench.txt)
+  python tools/pcs_bench.py --hiding               the device HidingFriPcs: commit / commit_quotient times, the copy yardstick of the two
+                                                   streaming kernels, the hiding fib comparison (default profiles/pcs_hiding_open_bench.txt)
+  python tools/pcs_bench.py --hiding --plain       the hiding commits only: the run to put under rocprofv3 --kernel-trace
+  python tools/pcs_bench.py --hiding --merge DIR   adds the device times of pcs_randomize_kernel / pcs_blind_kernel from DIR/**/*kernel_trace.csv
 
 Algorithmic bytes of the streaming kernels: reduced openings 4*big*w (every LDE word once), opened values 4*h*w (the low coset
 once), inverse denominators and ro 16*big*(K + 1).  The yardstick is a device-to-device copy of the same byte count timed in the
@@ -148,6 +152,89 @@ def merge(prof_dir, out):
         out.append("%-14s   %-34s %10.1f us" % (name, "all kernels", tot))
 
 
+# ---- HidingFriPcs ----
+HIDING_SHAPES = [(20, 2), (20, 64), (16, 2633)]  # (log_h, w) of a committed matrix
+NRC, CHUNKS, MAX_WQ = 4, 4, 2048
+
+
+def _blind_width(w):
+    return min(w, MAX_WQ)  # commit_quotient takes chunks of at most 2048 columns: the widest shape is timed at that width
+
+
+def hiding_bytes(log_h, w):
+    """algorithmic bytes (read + written, each word once) of the two streaming kernels"""
+    h, wq = 1 << log_h, _blind_width(w)
+    randomize = 4 * (h * w + h * (w + 2 * NRC)) + 4 * 2 * h * (w + NRC)
+    blind = 4 * (CHUNKS * h * wq + (CHUNKS - 1) * h * wq) + 4 * CHUNKS * 2 * h * wq
+    return randomize, blind
+
+
+def run_hiding(p3, warmup, reps, plain, out):
+    import torch
+    for log_h, w in HIDING_SHAPES:
+        h, name = 1 << log_h, "2^%dx%d" % (log_h, w)
+        pcs = p3.HidingFriPcs(p3.FriParameters(*FRI), "poseidon2")
+        m = torch.randint(0, P, (h, w), dtype=torch.int32, device="cuda")
+        chunks = [torch.randint(0, P, (h, _blind_width(w)), dtype=torch.int32, device="cuda") for _ in range(CHUNKS)]
+        a = _timed(lambda: pcs.commit([(m, None)])[1].free(), warmup, reps)
+        b = _timed(lambda: pcs.commit_quotient(chunks)[1].free(), warmup, reps)
+        out.append("%-12s hiding commit (fill, randomize, LDE, salts, tree): %s" % (name, _fmt(a)))
+        out.append("%-12s commit_quotient of %d chunks x %d (fill, inverse DFT, blind, LDE, salts, tree): %s" % (name, CHUNKS, _blind_width(w), _fmt(b)))
+        if not plain:
+            for what, nbytes in zip(("pcs_randomize_kernel", "pcs_blind_kernel"), hiding_bytes(log_h, w)):
+                out.append("%-12s   %-22s %12d bytes read + written; a device-to-device copy of as many bytes (half read, half written) runs at %.0f GB/s"
+                           % (name, what, nbytes, 2 * _copy_rate(nbytes // 2, warmup, reps)))
+        pcs.free()
+        del m, chunks
+
+
+def fib_hiding_comparison(p3, warmup, reps, out):
+    """the PCS calls of a hiding fib proof in the reference's configuration (Keccak, 2^19 rows; the quotient's values are given) beside
+    FibAirProver(hiding=True).prove in the same process"""
+    import torch
+    log_n = 19
+    pcs = p3.HidingFriPcs(p3.FriParameters(*FRI), "keccak")
+    trace = p3.generate_trace_rows(0, 1, 1 << log_n)
+    chunks = [torch.randint(0, P, (1 << log_n, 4), dtype=torch.int32, device="cuda") for _ in range(4)]
+    rng = np.random.default_rng(2)
+    z = [((rng.integers(0, P, 4, dtype=np.uint64) << 32) % P).astype(np.uint32) for _ in range(2)]
+
+    def through():
+        _, dt = pcs.commit([(trace, None)])
+        _, dq = pcs.commit_quotient(chunks)
+        _, dr = pcs.get_opt_randomization_poly_commitment(log_n)
+        pcs.open([(dr, [[z[0]]]), (dt, [[z[0], z[1]]]), (dq, [[z[0]]] * 4)], p3.Challenger("keccak"))
+        for d in (dt, dq, dr):
+            d.free()
+    a = _timed(through, warmup, reps)
+    pr = p3.FibAirProver(log_n, params=p3.FriParameters(*FRI), hash="keccak", hiding=True)
+    b = _timed(lambda: pr.prove(0, 1), warmup, reps)
+    pr.close()
+    out.append("hiding fib 2^19 Keccak through the PCS (3 commits + open, quotient values given): %s" % _fmt(a))
+    out.append("hiding fib 2^19 Keccak FibAirProver(hiding=True).prove:                          %s" % _fmt(b))
+    out.append("ratio of the medians (general path / hiding fib prover): %.2f" % (statistics.median(a) / statistics.median(b)))
+
+
+def merge_hiding(prof_dir, out):
+    """device times of the two kernels from a profiled --hiding --plain run: the dispatches in launch order are the shapes in
+    HIDING_SHAPES order, (warm-up + reps) of each; the median per shape"""
+    files = glob.glob(os.path.join(prof_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        out.append("no kernel trace under %s" % prof_dir)
+        return
+    rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Start_Timestamp"]))
+    for kernel, which in (("pcs_randomize_kernel", 0), ("pcs_blind_kernel", 1)):
+        ns = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if kernel in r["Kernel_Name"]]
+        per = len(ns) // len(HIDING_SHAPES)
+        for i, (log_h, w) in enumerate(HIDING_SHAPES):
+            mine = ns[i * per:(i + 1) * per]
+            if not mine:
+                continue
+            us, nbytes = statistics.median(mine) / 1e3, hiding_bytes(log_h, w)[which]
+            out.append("2^%dx%-6d %-22s median %8.1f us of %d dispatches under rocprofv3 --kernel-trace; %d bytes -> %.0f GB/s"
+                       % (log_h, _blind_width(w) if which else w, kernel, us, len(mine), nbytes, nbytes / (us * 1e3)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=sorted(SHAPES))
@@ -155,9 +242,25 @@ def main():
     ap.add_argument("--merge")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("-o", "--output", default=os.path.join(ROOT, "profiles", "pcs_open_bench.txt"))
+    ap.add_argument("--hiding", action="store_true")
+    ap.add_argument("-o", "--output")
     a = ap.parse_args()
+    a.output = a.output or os.path.join(ROOT, "profiles", "pcs_hiding_open_bench.txt" if a.hiding else "pcs_open_bench.txt")
     p3 = load_package()
+    if a.hiding:
+        out = ["# tools/pcs_bench.py --hiding: FRI parameters %s, %d random codewords, latency profile; device timestamps, %d warm-up and %d timed"
+               % (FRI, NRC, a.warmup, a.reps), "# repetitions per figure"]
+        run_hiding(p3, a.warmup, a.reps, a.plain, out)
+        if not a.plain:
+            fib_hiding_comparison(p3, a.warmup, a.reps, out)
+        if a.merge:
+            merge_hiding(a.merge, out)
+        text = "\n".join(out) + "\n"
+        sys.stdout.write(text)
+        if not a.plain:
+            with open(a.output, "w") as f:
+                f.write(text)
+        return
     out = ["# tools/pcs_bench.py: FRI parameters %s, Poseidon2 hashes, latency profile, 2 opening points; device timestamps,"
            % (FRI,), "# %d warm-up and %d timed repetitions per figure" % (a.warmup, a.reps)]
     for name in ([a.shape] if a.shape else list(SHAPES)):
