@@ -450,6 +450,15 @@ int p3hip_challenger_sample_ext(p3hip_challenger_t *c, uint32_t out[4]);        
 int p3hip_challenger_sample_bits(p3hip_challenger_t *c, unsigned bits, uint32_t *out);               /* CanSampleBits::sample_bits, bits <= 30 */
 int p3hip_challenger_clone(const p3hip_challenger_t *c, p3hip_challenger_t **out);                   /* Clone */
 void p3hip_challenger_destroy(p3hip_challenger_t *c);
+/* A challenger as the words a device transcript reads and writes (p3hip_pcs_verifier_verify_dev's d_chal_in / d_chal_out): the duplex
+ * state [16], input buffer [8], output buffer [8], pending inputs, outputs left, then the Keccak-256 hash challenger as a streaming
+ * sponge (state [25 x u64], pending bytes, output bytes left, pending block [136 bytes], output [32 bytes]).  export writes the half
+ * of the challenger's own configuration and zeroes the other; import reads that half, refuses (P3HIP_ERR_BAD_ARG, challenger
+ * unchanged) a counter no challenger can hold — 8 or more pending inputs, more than 8 outputs left; a pending block of 136 bytes or
+ * more, more than 32 output bytes left — and is otherwise the inverse of export: the next samples are the same. */
+#define P3HIP_CHALLENGER_STATE_WORDS 128
+int p3hip_challenger_export(const p3hip_challenger_t *c, uint32_t words[P3HIP_CHALLENGER_STATE_WORDS]);
+int p3hip_challenger_import(p3hip_challenger_t *c, const uint32_t words[P3HIP_CHALLENGER_STATE_WORDS]);
 
 /* ---- TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over CALLER-SUPPLIED matrices: the Pcs contract the reference
  *      hands to prove (HidingFriPcs::new(dft, val_mmcs, fri_params, ..), native/src/fib_air.rs:62-65), NON-HIDING, for either hash
@@ -461,7 +470,8 @@ void p3hip_challenger_destroy(p3hip_challenger_t *c);
  *      over every (matrix, point) pair; also the widest single matrix).  The FRI parameter gates are the fib prover's with log_h for
  *      the trace's log height.  An opening point on the LDE coset GENERATOR * <g_big> (a base-field z with (z / GENERATOR)^big = 1:
  *      upstream panics on the zero denominator) is refused on the host before anything is launched, naming round, matrix and point.
- *      Not covered: mixed heights, a device batch verifier.  HidingFriPcs: the section after this one. ---- */
+ *      Batches of proofs of one shape are verified on the device by p3hip_pcs_verifier_* (the section after the hiding PCS).
+ *      Not covered: mixed heights.  HidingFriPcs: the section after this one. ---- */
 typedef struct p3hip_pcs p3hip_pcs_t;
 typedef struct p3hip_pcs_data p3hip_pcs_data_t;
 /* TwoAdicFriPcs::new(dft, mmcs, fri_params); stream / own_stream as p3hip_fib_prover_create */
@@ -506,7 +516,8 @@ void p3hip_pcs_destroy(p3hip_pcs_t *pcs);
  *      log_blowup <= 24, log_final_poly_len < log_h + 1.  Capacities as above except 4 matrices per hiding commitment (a query lists
  *      every matrix and its salt); the 8192 batched columns count the random columns.  The rounds of one open are all hiding and of
  *      one configuration (hash, blowup, number of random codewords).  Opened values include the random columns.
- *      Not covered: mixed heights, a device batch verifier, more than 4 matrices per hiding commitment. ---- */
+ *      Batches of hiding proofs of one shape are verified on the device by p3hip_pcs_verifier_* (the next section).
+ *      Not covered: mixed heights, more than 4 matrices per hiding commitment. ---- */
 /* HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over MerkleTreeHidingMmcs::new(..,
  * SmallRng::seed_from_u64(mmcs_seed)) (fib_air.rs:40-65: 4, 1, 1); num_random_codewords in 1..8 */
 int p3hip_pcs_create_hiding(int profile, int hash, const p3hip_fri_params_t *params, unsigned num_random_codewords, uint64_t mmcs_seed,
@@ -535,6 +546,67 @@ int p3hip_pcs_verify_hiding(int hash, const p3hip_fri_params_t *params, unsigned
                             const size_t *mats_per_round, const size_t *widths, size_t n_rounds, const size_t *points_per_mat,
                             const uint32_t *points, const uint32_t *opened, const uint8_t *proof, size_t len,
                             p3hip_challenger_t *challenger, int *reject_code);
+
+/* ---- batches of PCS proofs verified ON THE DEVICE: Pcs::verify of TwoAdicFriPcs (hiding = 0) or HidingFriPcs (hiding = 1) for many
+ *      MEMBERS of ONE SHAPE at once — the proofs of any AIR a pool's caller, a rank that gathers proofs or an aggregator holds.
+ *      p3hip_pcs_verify / p3hip_pcs_verify_hiding (host, one proof) are the specification; DESIGN.md section 5.2.
+ *      A shape fixes the layout of every proof: log_h, the caller's log height as for the host verifiers; n_rounds <= 4; per round
+ *      mats_per_round <= 8 (<= 4 when hiding); per matrix its committed width (random columns included when hiding) and
+ *      points_per_mat <= 4 (zero allowed); n_slots <= 4 point slots; per (matrix, point) pair, round -> matrix -> point, one slot <
+ *      n_slots.  A member supplies n_slots points; the host verifier's form is those points expanded pair by pair.  Slots take the
+ *      place of the host's "at most 4 distinct values" rule: a slot may repeat and two slots may hold equal values.  Every other gate
+ *      (8192 batched columns included) and its message are the host verifiers', refused when the verifier is created.
+ *      REJECT CODES.  With H the host verifier's result for the member's expanded arguments: status 0 = accept, exactly when H
+ *      accepts.  status = H whenever H is 11 (InvalidPowWitness), 13 (input opening), 14 (FRI layer opening) or 15
+ *      (FinalPolyMismatch) and every field word of the proof, the opened values and the points is canonical: the first failure in the
+ *      host's order.  Everything else is P3HIP_VERIFY_MALFORMED: the host's 5..9 and 12, a wrong length, a field word >= P, and a
+ *      member whose VALUES the host refuses with P3HIP_ERR_BAD_ARG (an opened value or point >= P, a point on the LDE coset, a state
+ *      counter out of range).  The field words OUTSIDE the queries, the opened values, the points, the roots and the state counters are
+ *      checked before any arithmetic; the field words INSIDE the queries (rows, salts, siblings, Poseidon2 path words) are checked by
+ *      the opening kernel, after the fold arithmetic has consumed them — they never reach an address or a loop bound, and the
+ *      malformed status wins over whatever that arithmetic reported.  Batch-level arguments (n > max_proofs on the device entry, a misaligned pointer, a stride below the
+ *      proof length) are refused with P3HIP_ERR_BAD_ARG before anything is launched. ---- */
+typedef struct p3hip_pcs_verifier p3hip_pcs_verifier_t;
+typedef struct {
+    unsigned log_h;
+    size_t n_rounds;
+    const size_t *mats_per_round; /* n_rounds */
+    const size_t *widths;         /* one per matrix, round -> matrix */
+    const size_t *points_per_mat; /* one per matrix */
+    size_t n_slots;
+    const uint32_t *slots;        /* one per (matrix, point) pair, round -> matrix -> point */
+} p3hip_pcs_shape_t;
+/* Pcs::verify: the byte length every proof of the shape has (the FriProof section p3hip_pcs_open returns); host only, no GPU touched */
+int p3hip_pcs_proof_len(int hash, int hiding, const p3hip_fri_params_t *params, const p3hip_pcs_shape_t *shape, size_t *len_out);
+/* Pcs::verify: a verifier of up to max_proofs members per call on the calling thread's current device, which it remembers: a later
+ * call from a thread whose current device is another one is NOT refused, it is redirected — the call makes the verifier's device
+ * current for its duration and restores the caller's (the pointers must belong to the verifier's device).  p3hip_fib_verifier_* does
+ * the same.  Owns all scratch of the device entry, allocated here; the HOST entry's staging (eight buffers and a stream) is allocated
+ * by the first p3hip_pcs_verifier_verify call, which can therefore fail for lack of memory after creation succeeded. */
+int p3hip_pcs_verifier_create(int hash, int hiding, const p3hip_fri_params_t *params, const p3hip_pcs_shape_t *shape, size_t max_proofs,
+                              p3hip_pcs_verifier_t **out);
+/* Pcs::verify: n <= max_proofs members in device memory.  Proof i at d_proofs + i * stride_bytes (stride a multiple of 4, >=
+ * p3hip_pcs_proof_len); d_lens: n u32 byte lengths, or NULL = every proof has p3hip_pcs_proof_len bytes (a proof of another length
+ * is rejected without being read); d_roots: n x n_rounds x 8 words; d_points: n x n_slots x 4 Montgomery words; d_opened: n x total
+ * x 4 words in observation order (total = sum of width over the pairs); d_chal_in: n x P3HIP_CHALLENGER_STATE_WORDS, each member's
+ * transcript before verification (8-byte aligned, as d_chal_out; everything else 4-byte aligned); d_status: n codes; *d_rejected (may
+ * be NULL) = count of nonzero codes; d_chal_out (may be NULL): of an ACCEPTED member the transcript as the host verifier leaves it
+ * (of any other member undefined).  Enqueues only (four launches and one 4-byte memset on `stream`): no allocation, no host copy,
+ * no synchronise; can be captured.  One call at a time per verifier: the scratch is reused in stream order. */
+int p3hip_pcs_verifier_verify_dev(p3hip_pcs_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,
+                                  const uint32_t *d_roots, const uint32_t *d_points, const uint32_t *d_opened, const uint32_t *d_chal_in,
+                                  size_t n, uint32_t *d_status, uint32_t *d_rejected, uint32_t *d_chal_out, void *stream);
+/* Pcs::verify: host convenience.  proofs[i] / lens[i], roots, points, opened: host memory, laid out as above; challengers[i]: in, the
+ * member's transcript before verification; out, of an accepted member the transcript as the host verifier leaves it, of a rejected
+ * member unchanged.  Uploads on a stream of the verifier's own (staging allocated by the first call), verifies, downloads
+ * status_out[n]; synchronises.  Splits n > max_proofs into several rounds itself. */
+int p3hip_pcs_verifier_verify(p3hip_pcs_verifier_t *v, size_t n, const uint8_t *const *proofs, const size_t *lens, const uint32_t *roots,
+                              const uint32_t *points, const uint32_t *opened, p3hip_challenger_t *const *challengers, uint32_t *status_out);
+/* DIAGNOSTIC, not part of the stable ABI: 1 when the shape's reduced opening runs one wavefront per query, 0: one lane per query.  Which
+ * form a shape gets is a tuning detail (today: 256 or more row words per query) and will move with measurements; the tests use this
+ * entry to show that they run both forms.  Results never depend on the form. */
+int p3hip_pcs_verifier_wave_form(const p3hip_pcs_verifier_t *v);
+void p3hip_pcs_verifier_destroy(p3hip_pcs_verifier_t *v);
 
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */

@@ -317,6 +317,13 @@ class Challenger {
     std::array<uint32_t, 4> sample_ext() { std::array<uint32_t, 4> e{}; check(p3hip_challenger_sample_ext(h_, e.data())); return e; }
     uint32_t sample_bits(unsigned bits) { uint32_t v = 0; check(p3hip_challenger_sample_bits(h_, bits, &v)); return v; }
     p3hip_challenger_t* handle() const { return h_; }
+    // the transcript as the words a device verifier imports, and back (p3hip.h p3hip_challenger_export / _import)
+    std::array<uint32_t, P3HIP_CHALLENGER_STATE_WORDS> export_state() const {
+        std::array<uint32_t, P3HIP_CHALLENGER_STATE_WORDS> w{};
+        check(p3hip_challenger_export(h_, w.data()));
+        return w;
+    }
+    void import_state(const std::array<uint32_t, P3HIP_CHALLENGER_STATE_WORDS>& w) { check(p3hip_challenger_import(h_, w.data())); }
 
   private:
     p3hip_challenger_t* h_ = nullptr;
@@ -430,6 +437,53 @@ class HidingFriPcs : public TwoAdicFriPcs {
                                       points_per_mat.data(), points.data(), opened.data(), proof.data(), proof.size(), challenger.handle(), &code));
         return code;
     }
+};
+
+// Pcs::verify of TwoAdicFriPcs / HidingFriPcs for batches of members of ONE shape, on the device (p3hip.h "batches of PCS proofs verified
+// ON THE DEVICE").  widths: the committed widths, round -> matrix; slots: one per (matrix, point) pair, round -> matrix -> point.
+class PcsVerifier {
+  public:
+    PcsVerifier(int hash, bool hiding, FriParameters fp, unsigned log_h, const std::vector<size_t>& mats_per_round, const std::vector<size_t>& widths,
+                const std::vector<size_t>& points_per_mat, size_t n_slots, const std::vector<uint32_t>& slots, size_t max_proofs)
+        : n_rounds_(mats_per_round.size()), n_slots_(n_slots) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        p3hip_pcs_shape_t s{log_h, mats_per_round.size(), mats_per_round.data(), widths.data(), points_per_mat.data(), n_slots, slots.data()};
+        if (widths.size() != points_per_mat.size()) throw Error(P3HIP_ERR_BAD_ARG, "PcsVerifier: one point count per matrix");
+        for (size_t m = 0; m < widths.size(); m++) total_ += widths[m] * points_per_mat[m];
+        check(p3hip_pcs_proof_len(hash, hiding ? 1 : 0, &c, &s, &proof_len_));
+        check(p3hip_pcs_verifier_create(hash, hiding ? 1 : 0, &c, &s, max_proofs, &h_));
+    }
+    PcsVerifier(const PcsVerifier&) = delete;
+    PcsVerifier& operator=(const PcsVerifier&) = delete;
+    ~PcsVerifier() { p3hip_pcs_verifier_destroy(h_); }
+    size_t proof_len() const { return proof_len_; }
+    // per member: n_rounds x 8 root words, n_slots x 4 point words, total x 4 opened words and its challenger (advanced when the
+    // member is accepted, left alone otherwise); one status per member
+    std::vector<uint32_t> verify_many(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<uint32_t>& roots,
+                                      const std::vector<uint32_t>& points, const std::vector<uint32_t>& opened,
+                                      const std::vector<Challenger*>& challengers) {
+        const size_t n = proofs.size();
+        if (challengers.size() != n || roots.size() != n * n_rounds_ * 8 || points.size() != n * n_slots_ * 4 || opened.size() != n * total_ * 4)
+            throw Error(P3HIP_ERR_BAD_ARG, "PcsVerifier: one challenger, n_rounds roots, n_slots points and `total` opened values per proof");
+        std::vector<const uint8_t*> ptrs(n);
+        std::vector<size_t> lens(n);
+        std::vector<p3hip_challenger_t*> ch(n);
+        for (size_t i = 0; i < n; i++) { ptrs[i] = proofs[i].data(); lens[i] = proofs[i].size(); ch[i] = challengers[i]->handle(); }
+        std::vector<uint32_t> status(n);
+        check(p3hip_pcs_verifier_verify(h_, n, ptrs.data(), lens.data(), roots.data(), points.data(), opened.data(), ch.data(), status.data()));
+        return status;
+    }
+    // device-resident members: enqueues on `stream`, nothing is waited for
+    void verify_many_dev(const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens, const uint32_t* d_roots, const uint32_t* d_points,
+                         const uint32_t* d_opened, const uint32_t* d_chal_in, size_t n, uint32_t* d_status, uint32_t* d_rejected,
+                         uint32_t* d_chal_out, void* stream) {
+        check(p3hip_pcs_verifier_verify_dev(h_, d_proofs, stride_bytes, d_lens, d_roots, d_points, d_opened, d_chal_in, n, d_status, d_rejected,
+                                            d_chal_out, stream));
+    }
+
+  private:
+    p3hip_pcs_verifier_t* h_ = nullptr;
+    size_t n_rounds_ = 0, n_slots_ = 0, total_ = 0, proof_len_ = 0;
 };
 
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"

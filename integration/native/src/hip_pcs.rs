@@ -2,7 +2,7 @@
 //
 // native/src/hip_pcs.rs — `HipPcs`: the `Pcs<Challenge, Challenger>` the reference builds at native/src/fib_air.rs:62-65, with
 // commit / get_evaluations_on_domain / open on the device (libp3hip's TwoAdicFriPcs over caller matrices: include/p3hip.h
-// "TwoAdicFriPcs over CALLER-SUPPLIED matrices" and "HidingFriPcs over CALLER-SUPPLIED matrices") and verify on the host.  Every matrix
+// "TwoAdicFriPcs over CALLER-SUPPLIED matrices" and "HidingFriPcs over CALLER-SUPPLIED matrices") and verify on the host, or for batches of one shape on the device (HipPcsVerifier).  Every matrix
 // of one open has the same height, which is what p3_uni_stark hands a PCS (trace, preprocessed trace, quotient chunks).
 //
 //     let pcs = HipPcs::keccak(fri_params);        // the reference's hashes (fib_air.rs:28-53), non-hiding
@@ -49,6 +49,22 @@ pub struct p3hip_pcs_t {
 pub struct p3hip_pcs_data_t {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct p3hip_pcs_verifier_t {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct p3hip_pcs_shape_t {
+    pub log_h: u32,
+    pub n_rounds: usize,
+    pub mats_per_round: *const usize,
+    pub widths: *const usize,
+    pub points_per_mat: *const usize,
+    pub n_slots: usize,
+    pub slots: *const u32,
+}
+pub const P3HIP_CHALLENGER_STATE_WORDS: usize = 128;
+pub const P3HIP_VERIFY_MALFORMED: u32 = 16;
 
 // include/p3hip.h
 extern "C" {
@@ -152,6 +168,29 @@ extern "C" {
     ) -> i32;
     fn p3hip_pcs_data_free(d: *mut p3hip_pcs_data_t);
     fn p3hip_pcs_destroy(pcs: *mut p3hip_pcs_t);
+    fn p3hip_challenger_export(c: *const p3hip_challenger_t, words: *mut u32) -> i32;
+    fn p3hip_challenger_import(c: *mut p3hip_challenger_t, words: *const u32) -> i32;
+    fn p3hip_pcs_proof_len(hash: i32, hiding: i32, params: *const p3hip_fri_params_t, shape: *const p3hip_pcs_shape_t, len_out: *mut usize) -> i32;
+    fn p3hip_pcs_verifier_create(
+        hash: i32,
+        hiding: i32,
+        params: *const p3hip_fri_params_t,
+        shape: *const p3hip_pcs_shape_t,
+        max_proofs: usize,
+        out: *mut *mut p3hip_pcs_verifier_t,
+    ) -> i32;
+    fn p3hip_pcs_verifier_verify(
+        v: *mut p3hip_pcs_verifier_t,
+        n: usize,
+        proofs: *const *const u8,
+        lens: *const usize,
+        roots: *const u32,
+        points: *const u32,
+        opened: *const u32,
+        challengers: *const *mut p3hip_challenger_t,
+        status_out: *mut u32,
+    ) -> i32;
+    fn p3hip_pcs_verifier_destroy(v: *mut p3hip_pcs_verifier_t);
     fn p3hip_malloc(dev_ptr: *mut *mut c_void, bytes: usize) -> i32;
     fn p3hip_free(dev_ptr: *mut c_void) -> i32;
     fn p3hip_upload(dev_dst: *mut c_void, host_src: *const c_void, bytes: usize) -> i32;
@@ -418,6 +457,85 @@ impl HipPcs {
 impl Drop for HipPcs {
     fn drop(&mut self) {
         unsafe { p3hip_pcs_destroy(self.h) }
+    }
+}
+
+impl HipChallenger {
+    /// The transcript as the words a device verifier imports (include/p3hip.h p3hip_challenger_export).
+    pub fn export_state(&self) -> Result<[u32; P3HIP_CHALLENGER_STATE_WORDS], String> {
+        let mut w = [0u32; P3HIP_CHALLENGER_STATE_WORDS];
+        let rc = unsafe { p3hip_challenger_export(self.h, w.as_mut_ptr()) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(w) }
+    }
+    pub fn import_state(&mut self, w: &[u32; P3HIP_CHALLENGER_STATE_WORDS]) -> Result<(), String> {
+        let rc = unsafe { p3hip_challenger_import(self.h, w.as_ptr()) };
+        if rc != 0 { Err(last_error(rc)) } else { Ok(()) }
+    }
+}
+
+/// Pcs::verify for batches of members of ONE shape on the device (include/p3hip.h "batches of PCS proofs verified ON THE DEVICE").
+/// widths: the committed widths per round; slots: per matrix the slot (< n_slots) of each of its opening points.
+pub struct HipPcsVerifier {
+    h: *mut p3hip_pcs_verifier_t,
+    pub proof_len: usize,
+    n_rounds: usize,
+    n_slots: usize,
+    total: usize,
+}
+impl HipPcsVerifier {
+    pub fn new(pcs: &HipPcs, log_h: u32, widths: &[Vec<usize>], slots: &[Vec<Vec<u32>>], n_slots: usize, max_proofs: usize) -> Result<Self, String> {
+        let mats: Vec<usize> = widths.iter().map(|w| w.len()).collect();
+        let flat_w: Vec<usize> = widths.iter().flatten().copied().collect();
+        let counts: Vec<usize> = slots.iter().flatten().map(|s| s.len()).collect();
+        let flat_s: Vec<u32> = slots.iter().flatten().flatten().copied().collect();
+        let total = flat_w.iter().zip(counts.iter()).map(|(w, c)| w * c).sum();
+        let shape = p3hip_pcs_shape_t {
+            log_h,
+            n_rounds: mats.len(),
+            mats_per_round: mats.as_ptr(),
+            widths: flat_w.as_ptr(),
+            points_per_mat: counts.as_ptr(),
+            n_slots,
+            slots: flat_s.as_ptr(),
+        };
+        let hiding = (pcs.num_random_codewords > 0) as i32;
+        let (mut h, mut proof_len) = (core::ptr::null_mut(), 0usize);
+        let rc = unsafe { p3hip_pcs_proof_len(pcs.hash, hiding, &pcs.params, &shape, &mut proof_len) };
+        if rc != 0 { return Err(last_error(rc)); }
+        let rc = unsafe { p3hip_pcs_verifier_create(pcs.hash, hiding, &pcs.params, &shape, max_proofs, &mut h) };
+        if rc != 0 { return Err(last_error(rc)); }
+        Ok(Self { h, proof_len, n_rounds: mats.len(), n_slots, total })
+    }
+
+    /// One status per member: 0 = accept, 11 / 13 / 14 / 15 the host verifier's code, 16 malformed.  roots: n_rounds x 8 words per
+    /// member, points: n_slots x 4, opened: total x 4.  An accepted member's challenger is advanced, a rejected member's is left alone.
+    pub fn verify_many(
+        &mut self,
+        proofs: &[&[u8]],
+        roots: &[u32],
+        points: &[u32],
+        opened: &[u32],
+        challengers: &mut [HipChallenger],
+    ) -> Result<Vec<u32>, String> {
+        let n = proofs.len();
+        if challengers.len() != n || roots.len() != n * self.n_rounds * 8 || points.len() != n * self.n_slots * 4 || opened.len() != n * self.total * 4 {
+            return Err("verify_many: one challenger, n_rounds roots, n_slots points and `total` opened values per proof".into());
+        }
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let chals: Vec<*mut p3hip_challenger_t> = challengers.iter().map(|c| c.h).collect();
+        let mut status = vec![0u32; n];
+        let rc = unsafe {
+            p3hip_pcs_verifier_verify(self.h, n, ptrs.as_ptr(), lens.as_ptr(), roots.as_ptr(), points.as_ptr(), opened.as_ptr(), chals.as_ptr(),
+                                      status.as_mut_ptr())
+        };
+        if rc != 0 { return Err(last_error(rc)); }
+        Ok(status)
+    }
+}
+impl Drop for HipPcsVerifier {
+    fn drop(&mut self) {
+        unsafe { p3hip_pcs_verifier_destroy(self.h) }
     }
 }
 

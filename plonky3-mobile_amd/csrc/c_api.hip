@@ -18,6 +18,7 @@
 #include "common.h"
 #include "mmcs.h"
 #include "prover.h"
+#include "pcs_verifier_dev.h"
 #include "verifier_dev.h"
 #include "rng.h"
 
@@ -1370,4 +1371,73 @@ int p3hip_pcs_verify_hiding(int hash, const p3hip_fri_params_t* params, unsigned
 void p3hip_pcs_data_free(p3hip_pcs_data_t* d) { delete d; }
 void p3hip_pcs_destroy(p3hip_pcs_t* pcs) { delete pcs; }
 
+}  // extern "C"
+
+// ---- batches of PCS proofs verified on the device (pcs_verifier_dev.hip) ----
+struct p3hip_pcs_verifier {
+    PcsVerifierDev v;
+};
+static_assert(P3HIP_CHALLENGER_STATE_WORDS == CHALLENGER_STATE_WORDS, "include/p3hip.h and prover.h agree on the state's size");
+static int pcs_shape_of(const p3hip_pcs_shape_t* s, PcsShape* out, const char* who) {
+    if (!s) return fail(ERR_BAD_ARG, std::string(who) + ": null argument");
+    *out = PcsShape{s->log_h, s->n_rounds, s->mats_per_round, s->widths, s->points_per_mat, s->n_slots, s->slots};
+    return OK;
+}
+extern "C" {
+int p3hip_challenger_export(const p3hip_challenger_t* c, uint32_t* words) {
+    return guarded([&]() -> int {
+        if (!c || !words) return fail(ERR_BAD_ARG, "challenger_export: null argument");
+        challenger_export(c->c, words);
+        return OK;
+    });
+}
+int p3hip_challenger_import(p3hip_challenger_t* c, const uint32_t* words) {
+    return guarded([&]() -> int {
+        if (!c || !words) return fail(ERR_BAD_ARG, "challenger_import: null argument");
+        return challenger_import(words, &c->c);
+    });
+}
+int p3hip_pcs_proof_len(int hash, int hiding, const p3hip_fri_params_t* params, const p3hip_pcs_shape_t* shape, size_t* len_out) {
+    return guarded([&]() -> int {
+        if (!params || !len_out) return fail(ERR_BAD_ARG, "pcs_proof_len: null argument");
+        PcsShape sh;
+        if (int rc = pcs_shape_of(shape, &sh, "pcs_proof_len")) return rc;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        return pcs_proof_len(hash, hiding != 0, fp, sh, len_out);
+    });
+}
+int p3hip_pcs_verifier_create(int hash, int hiding, const p3hip_fri_params_t* params, const p3hip_pcs_shape_t* shape, size_t max_proofs,
+                              p3hip_pcs_verifier_t** out) {
+    return guarded([&]() -> int {
+        if (!params || !out) return fail(ERR_BAD_ARG, "pcs_verifier_create: null argument");
+        PcsShape sh;
+        if (int rc = pcs_shape_of(shape, &sh, "pcs_verifier_create")) return rc;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::unique_ptr<p3hip_pcs_verifier> h(new p3hip_pcs_verifier());
+        if (int rc = h->v.init(hash, hiding != 0, fp, sh, max_proofs)) return rc;
+        *out = h.release();
+        return OK;
+    });
+}
+int p3hip_pcs_verifier_verify_dev(p3hip_pcs_verifier_t* v, const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens,
+                                  const uint32_t* d_roots, const uint32_t* d_points, const uint32_t* d_opened, const uint32_t* d_chal_in,
+                                  size_t n, uint32_t* d_status, uint32_t* d_rejected, uint32_t* d_chal_out, void* stream) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: null verifier");
+        return v->v.verify_dev(d_proofs, stride_bytes, d_lens, d_roots, d_points, d_opened, d_chal_in, n, d_status, d_rejected, d_chal_out,
+                               static_cast<hipStream_t>(stream));
+    });
+}
+int p3hip_pcs_verifier_verify(p3hip_pcs_verifier_t* v, size_t n, const uint8_t* const* proofs, const size_t* lens, const uint32_t* roots,
+                              const uint32_t* points, const uint32_t* opened, p3hip_challenger_t* const* challengers, uint32_t* status_out) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null verifier");
+        if (n && !challengers) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null argument");
+        std::vector<Challenger*> ch(n);
+        for (size_t i = 0; i < n; i++) ch[i] = challengers[i] ? &challengers[i]->c : nullptr;
+        return v->v.verify_host(n, proofs, lens, roots, points, opened, ch.data(), status_out);
+    });
+}
+int p3hip_pcs_verifier_wave_form(const p3hip_pcs_verifier_t* v) { return v && v->v.wave_form() ? 1 : 0; }
+void p3hip_pcs_verifier_destroy(p3hip_pcs_verifier_t* v) { delete v; }
 }  // extern "C"

@@ -358,6 +358,27 @@ static void chal_from_dev(const uint32_t* words, Challenger* c) {
     c->n_obuf = (int)d.kc.n_obuf;
 }
 
+// the same two conversions for callers that hold transcripts in device memory (include/p3hip.h p3hip_challenger_export / _import)
+static_assert(CHALLENGER_STATE_WORDS == PCS_STATE_WORDS, "P3HIP_CHALLENGER_STATE_WORDS is the transcript part of DevState");
+void challenger_export(const Challenger& c, uint32_t* words) {
+    DevState d;
+    chal_to_dev(c, &d);
+    memcpy(words, &d, (size_t)PCS_STATE_WORDS * 4);
+}
+int challenger_import(const uint32_t* words, Challenger* c) {
+    DevState d;
+    memcpy(&d, words, (size_t)PCS_STATE_WORDS * 4);
+    if (c->kind == HASH_POSEIDON2) {
+        if (d.n_in >= 8) return fail(ERR_BAD_ARG, "challenger_import: " + std::to_string(d.n_in) + " pending inputs, a duplex challenger holds at most 7");
+        if (d.n_out > 8) return fail(ERR_BAD_ARG, "challenger_import: " + std::to_string(d.n_out) + " outputs left, a duplex challenger holds at most 8");
+    } else {
+        if (d.kc.blen >= 136) return fail(ERR_BAD_ARG, "challenger_import: a pending block of " + std::to_string(d.kc.blen) + " bytes, below the rate of 136 expected");
+        if (d.kc.n_obuf > 32) return fail(ERR_BAD_ARG, "challenger_import: " + std::to_string(d.kc.n_obuf) + " output bytes left, a digest has 32");
+    }
+    chal_from_dev(words, c);
+    return OK;
+}
+
 // a base-field point with (z / GENERATOR)^big = 1 lies on the LDE coset: 1/(z - x) has no value there (upstream panics)
 bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big) {
     if (z[1] || z[2] || z[3]) return false;

@@ -1,0 +1,53 @@
+// pcs_verifier_dev.hip: batches of TwoAdicFriPcs / HidingFriPcs proofs of ONE shape verified on the device (include/p3hip.h
+// p3hip_pcs_verifier_*).
+#pragma once
+#include "prover.h"
+#include "verifier_dev.h"
+
+namespace p3 {
+
+constexpr size_t PCS_MAX_SLOTS = 4;  // point slots of a shape: what PCS_MAX_POINTS distinct values are to the host verifier
+
+// What every proof of one configuration shares.  widths: the committed widths (random columns included when hiding); slots: one
+// slot < n_slots per (matrix, point) pair, round -> matrix -> point.
+struct PcsShape {
+    uint32_t log_h = 0;  // the caller's height, as for the host verifiers
+    size_t n_rounds = 0;
+    const size_t* mats_per_round = nullptr;
+    const size_t* widths = nullptr;
+    const size_t* points_per_mat = nullptr;
+    size_t n_slots = 0;
+    const uint32_t* slots = nullptr;
+};
+
+// host only: the byte length every proof of the shape has
+int pcs_proof_len(int hash, bool hiding, const FriParams& fp, const PcsShape& shape, size_t* len_out);
+
+class PcsVerifierDev {
+  public:
+    PcsVerifierDev();
+    ~PcsVerifierDev();
+    PcsVerifierDev(const PcsVerifierDev&) = delete;
+    // allocates every scratch buffer of the device entry for max_proofs members on the calling thread's current device
+    int init(int hash, bool hiding, const FriParams& fp, const PcsShape& shape, size_t max_proofs);
+    // enqueue only: no allocation, no host copy, no synchronise
+    int verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_roots, const uint32_t* d_points,
+                   const uint32_t* d_opened, const uint32_t* d_chal_in, size_t n, uint32_t* d_status, uint32_t* d_rejected,
+                   uint32_t* d_chal_out, hipStream_t stream);
+    // uploads (its staging is allocated by the first call), verifies in rounds of max_proofs, downloads; synchronises.  An accepted
+    // member's challenger comes out as the host verifier leaves it, a rejected member's is unchanged.
+    int verify_host(size_t n, const uint8_t* const* proofs, const size_t* lens, const uint32_t* roots, const uint32_t* points,
+                    const uint32_t* opened, Challenger* const* chals, uint32_t* status_out);
+    size_t proof_len() const;
+    size_t max_proofs() const;
+    size_t total_columns() const;  // opened values of one member
+    bool wave_form() const;        // the reduced opening runs one wavefront per query
+    int hash() const;
+    int device() const;
+
+  private:
+    struct Impl;
+    Impl* im;
+};
+
+}  // namespace p3

@@ -1,0 +1,735 @@
+// Batch verifier of PCS proofs on the device: TwoAdicFriPcs::verify / HidingFriPcs::verify + p3_fri::verifier over caller matrices for
+// MANY members of one shape at once.  verifier.hip's pcs_verify_any (host, one proof) is the specification: every phase below restates
+// it and FriCheck, and the reject codes are the host's.  The structure is verifier_dev.hip's (the fib_air batch verifier).
+//
+// A SHAPE fixes the layout of every proof: the FRI parameters, the committed log height, per round the matrices' widths, per matrix
+// its opening points as SLOTS (a member supplies n_slots points; pair (matrix, point) -> slot).  Every offset is then a function of
+// the shape: PLayout is computed on the host when the verifier is created and passed to the kernels by value (1.7 kB: it fits).
+//
+// SAFETY RULE.  NO LOAD ADDRESS AND NO LOOP BOUND DEPENDS ON A PROOF BYTE, AN OPENED VALUE, A POINT OR A CHALLENGER STATE WORD.  A
+// proof whose length differs from the shape's is rejected unread; every count / width / depth / salt-length word is compared with the
+// value the shape dictates and never followed; the imported state is loaded ONCE (registers, the sponge's copy in LDS) and the counters
+// of that copy are compared with their ranges before anything uses them (a Keccak fill level indexes the sponge's block in LDS);
+// the query indices are sample_bits(log_big), in range by construction, and select bits and exponents, never addresses.
+//
+//   pv_transcript_kernel  one wavefront per member.  First the checks, before any arithmetic: length, the three header count words,
+//                         canonicity of the proof's field words outside the queries (those of the queries are scanned by
+//                         pv_open_kernel, AFTER pv_query_kernel's arithmetic has consumed them: harmless, they never reach an
+//                         address, and key 0 wins), of the opened values, the points and (Poseidon2)
+//                         the roots, a base-field point on GENERATOR <g_big>, the state counters.  Then the transcript (DevChal,
+//                         transcript.hip.h) from the imported state: opened values, alpha, the commit-phase betas, the final
+//                         polynomial, the witness, the proof of work, the query indices; the state is exported.  Leaves in HBM per
+//                         member: alpha^c for c below the widest matrix, and per (matrix, point) pair alpha^off and
+//                         alpha^off Y, Y = sum_c alpha^c opened_c.
+//   pv_query_kernel       per (member, query): S_m = sum_c alpha^c row[c] ONCE per matrix, shared by its points;
+//                         ro = sum_pairs (alpha^off Y - alpha^off S_m) / (z - x) with the <= 4 slot denominators inverted together
+//                         (one inversion per query); then FriCheck::query's walk: writes every round's (ev0, ev1) leaf and compares
+//                         the final polynomial with the folded value.  Two forms:
+//                           <false>  one lane per query;
+//                           <true>   one wavefront per query, lanes along the columns, S_m summed across the wave.
+//                         THE SWITCH is PV_WAVE_MIN_COLS = 256 row words per query (sum of the widths of all matrices).  Instruction
+//                         counts, estimated from the source (not measured): the column loop is ~50 VALU instructions per column (an
+//                         extension element scaled by a base word is 4 Montgomery products of ~9 instructions, plus 4 modular additions
+//                         of 3 and the loads), everything behind it ~3k (the <= 4 denominators with ONE inversion, 31 squarings and
+//                         ~20 products of the norm, ~1.5k; two extension products per pair; ~150 per fold round).  A batch of 64 members
+//                         x 100 queries is 100 waves in the lane form and 6400 in the wave form on 1024 SIMDs; per SIMD the lane form
+//                         issues 50 W + 3k instructions, the wave form 6.25 x (0.8 W + 3k + 0.15k of cross-lane sums): equal near
+//                         W = 370, and a lone member's latency favours the wave form earlier still.  256 is the power of two below the
+//                         crossing.
+//   pv_open_kernel        one lane per (opening slot, member, query), slot-major so that the lanes of a wave walk paths of one depth:
+//                         an input round's leaf is m0 || m1 ... (with salts m0 || s0 || m1 || s1 ...), an FRI leaf the 8 words of
+//                         pv_query_kernel's pair plus its salt; hashed up the path in the proof (the per-lane sponge / compression
+//                         of mmcs_verify.hip) and compared with the member's root / the round's root in the proof.
+//   pv_finish_kernel      order key -> status, count of rejected members.
+// The first failure in the HOST's order decides the code: every check does atomicMin on a per-member word (order key << 8 | code).
+// Anything the host answers with 5..9 or 12, or refuses for a member's VALUES, is VERIFY_MALFORMED here (key 0 unless it is a shape
+// word inside a query, which keeps its place in the order so that an earlier query's 13 / 14 / 15 still wins).
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <memory>
+
+#include "bb31.hip.h"
+#include "challenger.h"
+#include "common.h"
+#include "keccak.hip.h"
+#include "mmcs.h"
+#include "pcs_verifier_dev.h"
+#include "poseidon2_f64.hip.h"
+#include "prover.h"
+#include "transcript.hip.h"
+
+namespace p3 {
+
+using bb::Ext;
+
+namespace {
+
+constexpr uint32_t PV_MAX_IN = (uint32_t)PCS_MAX_ROUNDS, PV_MAX_ALLMATS = (uint32_t)(PCS_MAX_ROUNDS * PCS_MAX_MATS);
+constexpr uint32_t PV_MAX_PAIRS = PV_MAX_ALLMATS * (uint32_t)PCS_MAX_POINTS, PV_MAX_FRI = 28;
+constexpr uint32_t PV_WAVE_MIN_COLS = 256;
+constexpr uint32_t CODE_POW = 11, CODE_INPUT_OPENING = 13, CODE_FRI_OPENING = 14, CODE_FINAL_POLY = 15;
+// order keys (smaller = earlier in the host verifier's order)
+constexpr uint64_t KEY_HEADER = 0, KEY_POW = 1, KEY_QUERY0 = 2, KEY_NONE = ~0ull;
+constexpr uint32_t STEPS_PER_QUERY = 64;  // 2 (n_in + n_fri) + 1 <= 2 (4 + 27) + 1
+static_assert(PV_MAX_PAIRS <= 128, "the transcript kernel keeps two pair powers per lane");
+// where the Keccak half of an exported challenger begins (transcript.hip.h DevState)
+constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;
+static_assert(offsetof(DevState, pis) == (size_t)CHALLENGER_STATE_WORDS * 4 && CHALLENGER_STATE_WORDS % 2 == 0, "state words");
+
+struct PLayout {
+    int hash;
+    uint32_t salt, log_big, lfinal, n_fri, nq, fpl, pow_bits;
+    uint32_t proof_words, nq_off, q_base, q_len, fpl_off, fpoly_off, witness_off;
+    uint32_t n_in, n_slots, n_pairs, total, wmax, row_words;
+    // input rounds; offsets are relative to a query's first word
+    uint32_t nm[PV_MAX_IN], mat0[PV_MAX_IN], open_off[PV_MAX_IN], depth_off[PV_MAX_IN], leaf_len[PV_MAX_IN];
+    // matrices, round -> matrix: width word at val_off - 1, salt length word at salt_off - 1; leaf_start: where the matrix begins in its leaf
+    uint32_t width[PV_MAX_ALLMATS], val_off[PV_MAX_ALLMATS], salt_off[PV_MAX_ALLMATS], leaf_start[PV_MAX_ALLMATS], np[PV_MAX_ALLMATS];
+    // (matrix, point) pairs, round -> matrix -> point: the first power of alpha the pair consumes, its slot, its matrix
+    uint16_t pair_off[PV_MAX_PAIRS];
+    uint8_t pair_slot[PV_MAX_PAIRS], pair_mat[PV_MAX_PAIRS];
+    uint32_t nr_off, fri_off[PV_MAX_FRI];
+    // constants of the field
+    uint32_t gen, gen_inv, neg_half, gens[PV_MAX_FRI], gens_inv[PV_MAX_FRI];
+};
+static_assert(sizeof(PLayout) <= 3072, "passed by value in the kernel arguments");
+
+struct PState {
+    Ext beta[PV_MAX_FRI];
+};
+
+struct PArgs {
+    const uint8_t* proofs;
+    size_t stride;
+    const uint32_t* lens;
+    const uint32_t* roots;    // n x n_in x 8
+    const uint32_t* points;   // n x n_slots x 4
+    const uint32_t* opened;   // n x total x 4
+    const uint32_t* chal_in;  // n x CHALLENGER_STATE_WORDS
+    uint32_t* chal_out;       // the same, or null
+    uint32_t n;
+    PState* st;
+    uint32_t* idx;            // n x nq
+    uint32_t* evs;            // n x nq x n_fri x 8
+    uint32_t* alp;            // n x wmax x 4
+    uint32_t* pa;             // n x n_pairs x 4: alpha^off
+    uint32_t* pb;             // n x n_pairs x 4: alpha^off Y
+    unsigned long long* key;  // n
+};
+
+__device__ __forceinline__ uint64_t make_key(uint64_t order, uint32_t code) { return (order << 8) | code; }
+__device__ __forceinline__ void report(const PArgs& a, uint32_t i, uint64_t order, uint32_t code) {
+    atomicMin(a.key + i, (unsigned long long)make_key(order, code));
+}
+__device__ __forceinline__ bool length_ok(const PArgs& a, const PLayout& L, uint32_t i) { return !a.lens || a.lens[i] == 4u * L.proof_words; }
+// the transcript kernel rejected the member before it produced anything the later kernels read
+__device__ __forceinline__ bool header_rejected(const PArgs& a, uint32_t i) { return (a.key[i] >> 8) == KEY_HEADER; }
+__device__ __forceinline__ const uint32_t* proof_words(const PArgs& a, uint32_t i) {
+    return reinterpret_cast<const uint32_t*>(a.proofs + (size_t)i * a.stride);
+}
+__device__ __forceinline__ Ext ldx(const uint32_t* w, size_t off) { return Ext{{w[off], w[off + 1], w[off + 2], w[off + 3]}}; }
+__device__ __forceinline__ void stx(uint32_t* w, size_t off, const Ext& e) { for (int c = 0; c < 4; c++) w[off + c] = e.c[c]; }
+__device__ __forceinline__ uint32_t rev_bits_dev(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32u - bits) : 0u; }
+__device__ __forceinline__ Ext wave_sum(Ext v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < 4; c++) v.c[c] = bb::add(v.c[c], (uint32_t)__shfl_xor((int)v.c[c], o, 64));
+    return v;
+}
+
+// ---- 1. transcript: one wavefront per member --------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
+    P3_LATENCY_BOUND_KERNEL();
+    __shared__ KState ks;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (!length_ok(a, L, i)) {  // rejected without being read
+        if (lane == 0) a.key[i] = make_key(KEY_HEADER, VERIFY_MALFORMED);
+        return;
+    }
+    const uint32_t* w = proof_words(a, i);
+    const uint32_t* op = a.opened + (size_t)i * L.total * 4;
+    const uint32_t* pts = a.points + (size_t)i * L.n_slots * 4;
+    const uint32_t* roots = a.roots + (size_t)i * L.n_in * 8;
+    const uint32_t* cs = a.chal_in + (size_t)i * CHALLENGER_STATE_WORDS;
+    const uint32_t nw = 4 * L.total;
+    DevChal ch;  // a copy of fixed size and no arithmetic: the counters are not followed before the check below
+    ch.begin(L.hash, reinterpret_cast<DevState*>(const_cast<uint32_t*>(cs)), &ks, false);
+    {   // every check that needs no challenge, the lanes side by side
+        bool bad = false;
+        uint32_t hi = 0;
+        if (lane == 0) bad = w[0] != L.n_fri || w[L.nq_off] != L.nq || w[L.fpl_off] != L.fpl;
+        if (L.hash == HASH_POSEIDON2) {
+            for (uint32_t j = 1 + lane; j < 1 + 8 * L.n_fri; j += 64) hi = max(hi, w[j]);
+            if (lane < 8 * L.n_in) hi = max(hi, roots[lane]);
+        }
+        for (uint32_t j = L.fpoly_off + lane; j <= L.witness_off; j += 64) hi = max(hi, w[j]);  // the witness follows the final polynomial
+        for (uint32_t j = lane; j < nw; j += 64) hi = max(hi, op[j]);
+        if (lane < 4 * L.n_slots) hi = max(hi, pts[lane]);
+        if (lane < L.n_slots) {  // a base-field point with (z / GENERATOR)^big = 1: 1 / (z - x) has no value on the LDE coset
+            const uint32_t* z = pts + 4 * lane;
+            if (!(z[1] | z[2] | z[3])) {
+                uint32_t q = bb::mul(z[0], L.gen_inv);
+                for (uint32_t k = 0; k < L.log_big; k++) q = bb::sqr(q);
+                bad |= q == bb::ONE;
+            }
+        }
+        // the state's counters, as the challenger holds them after its ONE load of the state (registers; the LDS copy of the sponge):
+        // what is compared here is what is used below, whatever becomes of d_chal_in during the call
+        if (L.hash == HASH_POSEIDON2) bad |= ch.n_in >= 8u || ch.n_out > 8u;
+        else bad |= ks.blen >= 136u || ks.n_obuf > 32u;
+        if (__builtin_amdgcn_ballot_w64(bad || hi >= bb::P)) {
+            if (lane == 0) a.key[i] = make_key(KEY_HEADER, VERIFY_MALFORMED);
+            return;
+        }
+    }
+    uint64_t key = KEY_NONE;
+    for (uint32_t base = 0; base < nw; base += 64) {  // 64 words per load, observed one by one
+        const uint32_t v = base + lane < nw ? op[base + lane] : 0u;
+        const uint32_t cnt = min(64u, nw - base);
+        for (uint32_t k = 0; k < cnt; k++) ch.observe((uint32_t)__shfl((int)v, (int)k, 64));
+    }
+    const Ext al = ch.sample_ext();
+    {   // alpha^c for c < wmax, and per pair alpha^off and alpha^off Y: lane l walks the columns l, l + 64, ...
+        Ext a64 = al;
+        for (int k = 0; k < 6; k++) a64 = bb::sqr(a64);
+        const Ext pl = bb::pow(al, (uint64_t)lane);
+        {
+            Ext p = pl;
+            uint32_t* t = a.alp + (size_t)i * L.wmax * 4;
+            for (uint32_t c = lane; c < L.wmax; c += 64) { stx(t, 4 * (size_t)c, p); p = bb::mul(p, a64); }
+        }
+        Ext mine[2];
+        for (uint32_t h = 0; h < 2; h++) {
+            const uint32_t pr = lane + 64 * h;
+            mine[h] = pr < L.n_pairs ? bb::pow(al, (uint64_t)L.pair_off[pr]) : bb::ext_one();
+        }
+        for (uint32_t pr = 0; pr < L.n_pairs; pr++) {
+            const uint32_t off = L.pair_off[pr], wd = L.width[L.pair_mat[pr]];
+            Ext p = pl, y = bb::ext_zero();
+            for (uint32_t c = lane; c < wd; c += 64) { y = bb::add(y, bb::mul(p, ldx(op, 4 * (size_t)(off + c)))); p = bb::mul(p, a64); }
+            y = wave_sum(y);
+            Ext ao;
+            for (int c = 0; c < 4; c++) ao.c[c] = (uint32_t)__shfl((int)(pr < 64 ? mine[0].c[c] : mine[1].c[c]), (int)(pr & 63u), 64);
+            if (lane == 0) {
+                stx(a.pa, 4 * ((size_t)i * L.n_pairs + pr), ao);
+                stx(a.pb, 4 * ((size_t)i * L.n_pairs + pr), bb::mul(ao, y));
+            }
+        }
+    }
+    PState* st = a.st + i;
+    for (uint32_t r = 0; r < L.n_fri; r++) {
+        ch.observe_n(w + 1 + 8 * r, 8);
+        const Ext beta = ch.sample_ext();
+        if (lane == 0) st->beta[r] = beta;
+    }
+    for (uint32_t k = 0; k < 4 * L.fpl; k++) ch.observe(w[L.fpoly_off + k]);
+    ch.observe(w[L.witness_off]);
+    if (ch.sample_bits(L.pow_bits) != 0) key = make_key(KEY_POW, CODE_POW);
+    for (uint32_t q = 0; q < L.nq; q++) {
+        const uint32_t index = ch.sample_bits(L.log_big);
+        if (lane == 0) a.idx[(size_t)i * L.nq + q] = index;
+    }
+    if (a.chal_out) {  // the other configuration's half of the state is zero, as challenger_export leaves it
+        uint32_t* out = a.chal_out + (size_t)i * CHALLENGER_STATE_WORDS;
+        const uint32_t lo = L.hash == HASH_POSEIDON2 ? SW_KC : 0u, hi = L.hash == HASH_POSEIDON2 ? CHALLENGER_STATE_WORDS : SW_KC;
+        for (uint32_t j = lo + lane; j < hi; j += 64) out[j] = 0u;
+        ch.ds = reinterpret_cast<DevState*>(out);
+        ch.end();
+    }
+    if (lane == 0) a.key[i] = key;
+}
+
+// ---- 2. reduced opening and fold walk: per (member, query) ------------------------------------------------------------------
+__device__ __forceinline__ Ext pick4(const Ext d[4], uint32_t s) { return s == 0 ? d[0] : s == 1 ? d[1] : s == 2 ? d[2] : d[3]; }
+
+template <bool WAVE>
+__global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
+    const uint64_t gt = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t = WAVE ? gt >> 6 : gt;  // WAVE: the same for every lane of a wave, so every branch below is wave-uniform
+    const uint32_t lane = WAVE ? (threadIdx.x & 63u) : 0u, step = WAVE ? 64u : 1u;
+    if (t >= (uint64_t)a.n * L.nq) return;
+    const uint32_t i = (uint32_t)(t / L.nq), q = (uint32_t)(t % L.nq);
+    if (!length_ok(a, L, i) || header_rejected(a, i)) return;
+    const uint32_t* w = proof_words(a, i);
+    const uint32_t* qw = w + L.q_base + (size_t)q * L.q_len;
+    const uint32_t* pts = a.points + (size_t)i * L.n_slots * 4;
+    const uint32_t* alp = a.alp + (size_t)i * L.wmax * 4;
+    const PState* st = a.st + i;
+    const uint32_t index = a.idx[t];
+    const uint32_t xi = bb::mul(L.gen, bb::pow(L.gens[L.log_big], rev_bits_dev(index, L.log_big)));
+    Ext dz[4];
+    {   // 1 / (z_s - x) for the slots, one inversion
+        Ext d[4], pre[4], acc = bb::ext_one();
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            d[s] = s < L.n_slots ? bb::sub(ldx(pts, 4 * s), bb::ext_from_base(xi)) : bb::ext_one();
+            pre[s] = acc;
+            acc = bb::mul(acc, d[s]);
+        }
+        Ext inv = bb::inv(acc);
+#pragma unroll
+        for (int s = 3; s >= 0; s--) { dz[s] = bb::mul(inv, pre[s]); inv = bb::mul(inv, d[s]); }
+    }
+    Ext folded = bb::ext_zero();
+    uint32_t pair = 0;
+    for (uint32_t r = 0; r < L.n_in; r++)
+        for (uint32_t m = L.mat0[r]; m < L.mat0[r] + L.nm[r]; m++) {
+            const uint32_t* vals = qw + L.val_off[m];
+            const uint32_t wd = L.width[m];
+            Ext s = bb::ext_zero();
+            for (uint32_t c = lane; c < wd; c += step) s = bb::add(s, bb::scale(ldx(alp, 4 * (size_t)c), vals[c]));
+            if (WAVE) s = wave_sum(s);
+            for (uint32_t p = 0; p < L.np[m]; p++, pair++) {
+                const size_t po = 4 * ((size_t)i * L.n_pairs + pair);
+                const Ext num = bb::sub(ldx(a.pb, po), bb::mul(ldx(a.pa, po), s));
+                folded = bb::add(folded, bb::mul(num, pick4(dz, L.pair_slot[pair])));
+            }
+        }
+    uint32_t idx = index;
+    uint32_t* evs = a.evs + t * L.n_fri * 8;
+    for (uint32_t r = 0; r < L.n_fri; r++) {
+        const uint32_t lfh = L.log_big - 1 - r;
+        const Ext sib = ldx(qw, L.fri_off[r]);
+        const bool odd = idx & 1u;
+        const Ext ev0 = odd ? sib : folded, ev1 = odd ? folded : sib;
+        const uint32_t pr = idx >> 1;
+        if (lane == 0)
+            for (int c = 0; c < 4; c++) { evs[8 * r + c] = ev0.c[c]; evs[8 * r + 4 + c] = ev1.c[c]; }
+        const uint32_t e = rev_bits_dev(pr, lfh);
+        const uint32_t sx = bb::pow(L.gens[lfh + 1], e), s_inv = bb::pow(L.gens_inv[lfh + 1], e);
+        const Ext num = bb::mul(bb::sub(st->beta[r], bb::ext_from_base(sx)), bb::sub(ev1, ev0));
+        folded = bb::add(ev0, bb::scale(num, bb::mul(L.neg_half, s_inv)));  // 1 / (-s - s)
+        idx = pr;
+    }
+    const uint32_t xf = bb::pow(L.gens[L.lfinal], rev_bits_dev(idx, L.lfinal));
+    Ext evf = bb::ext_zero();
+    for (uint32_t k = L.fpl; k-- > 0;) evf = bb::add(bb::scale(evf, xf), ldx(w, L.fpoly_off + 4 * (size_t)k));
+    if (lane == 0 && !bb::eq(evf, folded)) report(a, i, KEY_QUERY0 + (uint64_t)q * STEPS_PER_QUERY + 2 * (L.n_in + L.n_fri), CODE_FINAL_POLY);
+}
+
+// ---- 3. openings: one lane per (slot, member, query) ------------------------------------------------------------------------
+// What one lane opens.  n_ev = 8: an FRI leaf, evs[0..8) then `salt` words at tail.  n_ev = 0: an input round's leaf over the
+// matrices m0 .. m0 + nm of the layout, each followed by its salt, the words gathered from the query at qw.
+struct LaneOpening {
+    const uint32_t* evs;
+    const uint32_t* qw;
+    const uint32_t* tail;
+    const uint32_t* path;
+    const uint32_t* root;
+    uint32_t n_ev, m0, nm, leaf_len, depth, index;
+    __device__ __forceinline__ uint32_t leaf_word(const PLayout& L, uint32_t e) const {
+        if (n_ev) return e < n_ev ? evs[e] : tail[e - n_ev];
+        uint32_t m = m0;
+        for (uint32_t k = 1; k < nm; k++)
+            if (e >= L.leaf_start[m0 + k]) m = m0 + k;
+        const uint32_t c = e - L.leaf_start[m];
+        return c < L.width[m] ? qw[L.val_off[m] + c] : qw[L.salt_off[m] + (c - L.width[m])];
+    }
+};
+
+template <int HASH>
+__device__ __forceinline__ bool lane_open_mismatch(const PLayout& L, const LaneOpening& o, uint32_t& hi);
+
+// The two forms below restate mmcs_verify.hip's per-lane walks as verifier_dev.hip does (a fix there belongs here too): one height
+// class over words gathered from proof bytes and the fold pairs.
+// PaddingFreeSponge<Poseidon2-16, 16, 8, 8> over the leaf, TruncatedPermutation up the path
+template <>
+__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    const p2f::MagicRegs smk = p2f::magic_regs();
+    double s[16], cur[8];
+#pragma unroll
+    for (int k = 0; k < 16; k++) s[k] = 0.0;
+    for (uint32_t k = 0; k < o.leaf_len; k += 8) {
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            if (k + e < o.leaf_len) {
+                const uint32_t v = o.leaf_word(L, k + e);
+                hi = max(hi, v);
+                s[e] = p2f::load_elem(v);
+            }
+        p2f::permute(s);
+#pragma unroll
+        for (int e = 0; e < 16; e++) s[e] = p2f::reduce(s[e]);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) cur[k] = s[k];
+    for (uint32_t l = 0; l < o.depth; l++) {
+        const bool right = (o.index >> l) & 1u;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t sw = o.path[8 * l + k];
+            hi = max(hi, sw);
+            const double sd = p2f::load_elem(sw);
+            s[k] = right ? sd : cur[k];
+            s[8 + k] = right ? cur[k] : sd;
+        }
+        p2f::permute(s);
+#pragma unroll
+        for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
+    }
+    bool mismatch = false;
+#pragma unroll
+    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
+    return mismatch;
+}
+
+// SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the leaf, CompressionFunctionFromHasher up the path; digest words are
+// raw u64 halves: any value is hashed
+template <>
+__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    uint64_t st[25], cur[4];
+#pragma unroll
+    for (int k = 0; k < 25; k++) st[k] = 0;
+    const uint32_t n64 = (o.leaf_len + 1) / 2;
+    for (uint32_t b = 0; b < n64; b += 17) {
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            const uint32_t e = 2 * (b + k);
+            if (e < o.leaf_len) {
+                const uint32_t lo = o.leaf_word(L, e), hw = e + 1 < o.leaf_len ? o.leaf_word(L, e + 1) : 0u;
+                hi = max(hi, max(lo, hw));
+                st[k] = (uint64_t)lo | ((uint64_t)hw << 32);
+            }
+        }
+        if (b + 17 >= n64) kk::permute_digest(st);  // the last block: only the digest words are read
+        else kk::permute(st);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = st[k];
+    for (uint32_t l = 0; l < o.depth; l++) {
+        const bool right = (o.index >> l) & 1u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint64_t r = (uint64_t)o.path[8 * l + 2 * k] | ((uint64_t)o.path[8 * l + 2 * k + 1] << 32);
+            st[k] = right ? r : cur[k];
+            st[4 + k] = right ? cur[k] : r;
+        }
+#pragma unroll
+        for (int k = 8; k < 25; k++) st[k] = 0;
+        kk::permute_digest(st);
+#pragma unroll
+        for (int k = 0; k < 4; k++) cur[k] = st[k];
+    }
+    bool mismatch = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
+    return mismatch;
+}
+
+template <int HASH>
+__global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
+    const uint64_t per_slot = (uint64_t)a.n * L.nq, t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= per_slot * (L.n_in + L.n_fri)) return;
+    const uint32_t slot = (uint32_t)(t / per_slot);
+    const uint64_t pq = t % per_slot;
+    const uint32_t i = (uint32_t)(pq / L.nq), q = (uint32_t)(pq % L.nq);
+    if (!length_ok(a, L, i) || header_rejected(a, i)) return;
+    const uint32_t* w = proof_words(a, i);
+    const uint32_t* qw = w + L.q_base + (size_t)q * L.q_len;
+    const uint32_t index = a.idx[pq];
+    const uint64_t qkey = KEY_QUERY0 + (uint64_t)q * STEPS_PER_QUERY;
+    bool shape = false;  // a word of the query the shape dictates (the host's 12), met in query order
+    LaneOpening o{};
+    o.qw = qw;
+    uint32_t hi = 0, code;
+    if (slot < L.n_in) {
+        const uint32_t m0 = L.mat0[slot], nm = L.nm[slot];
+        if (slot == 0 && qw[0] != L.n_in) shape = true;
+        if (qw[L.open_off[slot]] != nm) shape = true;
+        for (uint32_t m = m0; m < m0 + nm; m++) {
+            if (qw[L.val_off[m] - 1] != L.width[m]) shape = true;
+            if (L.salt && qw[L.salt_off[m] - 1] != L.salt) shape = true;
+        }
+        o.depth = L.log_big;
+        if (qw[L.depth_off[slot]] != o.depth) shape = true;
+        o.path = qw + L.depth_off[slot] + 1;
+        o.m0 = m0; o.nm = nm;
+        o.leaf_len = L.leaf_len[slot];
+        o.index = index;
+        o.root = a.roots + ((size_t)i * L.n_in + slot) * 8;
+        code = CODE_INPUT_OPENING;
+    } else {
+        const uint32_t r = slot - L.n_in;
+        const uint32_t* p = qw + L.fri_off[r];
+        if (r == 0 && qw[L.nr_off] != L.n_fri) shape = true;
+        for (int c = 0; c < 4; c++) hi = max(hi, p[c]);  // the sibling: a field element of the proof
+        o.evs = a.evs + (pq * L.n_fri + r) * 8;
+        o.n_ev = 8;
+        o.tail = p + 5;
+        if (L.salt && p[4] != L.salt) shape = true;
+        const uint32_t* dp = p + 4 + (L.salt ? 1 + L.salt : 0u);
+        o.depth = L.log_big - 1 - r;
+        if (dp[0] != o.depth) shape = true;
+        o.path = dp + 1;
+        o.leaf_len = 8 + L.salt;
+        o.index = index >> (r + 1);
+        o.root = w + 1 + 8 * r;
+        code = CODE_FRI_OPENING;
+    }
+    const bool mismatch = lane_open_mismatch<HASH>(L, o, hi);
+    if (shape) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
+    if (hi >= bb::P) report(a, i, KEY_HEADER, VERIFY_MALFORMED);
+    if (mismatch) report(a, i, qkey + 2 * slot + 1, code);
+}
+
+// ---- 4. order key -> status -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) pv_finish_kernel(const unsigned long long* key, uint32_t n, uint32_t* status, uint32_t* d_rejected) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < n;
+    const uint32_t st = act && key[i] != KEY_NONE ? (uint32_t)(key[i] & 0xffu) : 0u;
+    if (act) status[i] = st;
+    const uint64_t b = __builtin_amdgcn_ballot_w64(st != 0u);
+    if (d_rejected && b && (threadIdx.x & 63u) == 0u) atomicAdd(d_rejected, (uint32_t)__builtin_popcountll(b));
+}
+
+// ---- host: the layout of one shape ------------------------------------------------------------------------------------------
+// The gates and their messages are pcs_verify_any's (verifier.hip), in its order; what it checks on a member's values (canonical
+// points, the LDE coset, canonical opened values) is the kernels' business.  Slots take the place of its "distinct points" rule.
+int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, PLayout* out) {
+    auto bad = [&](const std::string& msg) { return fail(ERR_BAD_ARG, msg); };
+    if (!sh.mats_per_round || !sh.widths || !sh.points_per_mat || !sh.slots) return bad("pcs verify: null argument");
+    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
+    uint32_t log_h = sh.log_h;
+    if (hiding) {
+        if (log_h < 1 || log_h >= bb::TWO_ADICITY)
+            return bad("pcs verify: log_h must be in [1, " + std::to_string(bb::TWO_ADICITY - 1) + "] (the caller's log height; the committed polynomials have degree < 2^(log_h + 1))");
+        log_h++;
+    }
+    if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
+    if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
+    if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
+    if (fp.num_queries == 0) return bad("pcs verify: num_queries must be positive");
+    const size_t n_rounds = sh.n_rounds, max_mats = hiding ? PCS_HIDING_MAX_MATS : PCS_MAX_MATS;
+    if (n_rounds == 0) return bad("pcs verify: zero rounds");
+    if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
+    if (sh.n_slots < 1 || sh.n_slots > PCS_MAX_SLOTS) return bad("pcs verifier: n_slots must be in [1, " + std::to_string(PCS_MAX_SLOTS) + "]");
+    PLayout& L = *out;
+    memset(&L, 0, sizeof(L));
+    L.hash = hash;
+    L.salt = hiding ? PCS_SALT : 0;
+    L.log_big = log_h + fp.log_blowup;
+    L.lfinal = fp.log_blowup + fp.log_final_poly_len;
+    L.n_fri = L.log_big - L.lfinal;
+    L.nq = fp.num_queries;
+    L.fpl = 1u << fp.log_final_poly_len;
+    L.pow_bits = fp.proof_of_work_bits;
+    L.n_in = (uint32_t)n_rounds;
+    L.n_slots = (uint32_t)sh.n_slots;
+    const uint32_t D = 8;
+    size_t mi = 0, pi = 0, total = 0;
+    uint64_t p = 1;  // within a query, behind the count of rounds
+    for (size_t r = 0; r < n_rounds; r++) {
+        const size_t nm = sh.mats_per_round[r];
+        if (nm == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
+        if (nm > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
+        L.nm[r] = (uint32_t)nm;
+        L.mat0[r] = (uint32_t)mi;
+        L.open_off[r] = (uint32_t)p++;
+        uint32_t leaf = 0;
+        for (size_t m = 0; m < nm; m++, mi++) {
+            const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
+            const size_t wd = sh.widths[mi], np = sh.points_per_mat[mi];
+            if (wd < 1 || wd > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
+            if (np > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
+            L.width[mi] = (uint32_t)wd;
+            L.np[mi] = (uint32_t)np;
+            L.val_off[mi] = (uint32_t)(p + 1);
+            p += 1 + wd;
+            L.leaf_start[mi] = leaf;
+            leaf += (uint32_t)wd + L.salt;
+            L.wmax = std::max(L.wmax, (uint32_t)wd);
+            L.row_words += (uint32_t)wd;
+            for (size_t k = 0; k < np; k++, pi++) {
+                const std::string pw = who + " point " + std::to_string(k);
+                if (sh.slots[pi] >= sh.n_slots) return bad(pw + ": slot " + std::to_string(sh.slots[pi]) + " of " + std::to_string(sh.n_slots));
+                L.pair_off[pi] = (uint16_t)total;
+                L.pair_slot[pi] = (uint8_t)sh.slots[pi];
+                L.pair_mat[pi] = (uint8_t)mi;
+                total += wd;
+                if (total > PCS_MAX_COLS) return bad(pw + ": more than " + std::to_string(PCS_MAX_COLS) + " batched columns");
+            }
+        }
+        if (L.salt)
+            for (size_t m = 0; m < nm; m++) { L.salt_off[L.mat0[r] + m] = (uint32_t)(p + 1); p += 1 + L.salt; }
+        L.leaf_len[r] = leaf;
+        L.depth_off[r] = (uint32_t)p;
+        p += 1 + (uint64_t)D * L.log_big;
+    }
+    if (total == 0) return bad("pcs verify: no opening point");
+    L.n_pairs = (uint32_t)pi;
+    L.total = (uint32_t)total;
+    L.nr_off = (uint32_t)p++;
+    for (uint32_t r = 0; r < L.n_fri; r++) {
+        L.fri_off[r] = (uint32_t)p;
+        p += 4 + (L.salt ? 1 + L.salt : 0) + 1 + (uint64_t)D * (L.log_big - 1 - r);
+    }
+    L.q_len = (uint32_t)p;
+    L.nq_off = 1 + D * L.n_fri;
+    L.q_base = L.nq_off + 1;
+    const uint64_t after = (uint64_t)L.q_base + p * L.nq;
+    if (after + 2 + 4ull * L.fpl > 0x3fffffffull) return bad("pcs verifier: a proof of this shape exceeds 2^32 bytes");
+    L.fpl_off = (uint32_t)after;
+    L.fpoly_off = L.fpl_off + 1;
+    L.witness_off = L.fpoly_off + 4 * L.fpl;
+    L.proof_words = L.witness_off + 1;
+    L.gen = bb::to_monty(bb::GEN);
+    L.gen_inv = bb::inv(L.gen);
+    L.neg_half = bb::inv(bb::neg(bb::dbl(bb::ONE)));
+    for (uint32_t b = 0; b < PV_MAX_FRI; b++) { L.gens[b] = bb::two_adic_generator(b); L.gens_inv[b] = bb::inv(L.gens[b]); }
+    return OK;
+}
+
+}  // namespace
+
+int pcs_proof_len(int hash, bool hiding, const FriParams& fp, const PcsShape& shape, size_t* len_out) {
+    PLayout L;
+    if (int rc = make_layout(hash, hiding, fp, shape, &L)) return rc;
+    *len_out = 4 * (size_t)L.proof_words;
+    return OK;
+}
+
+struct PcsVerifierDev::Impl {
+    PLayout L;
+    int device = -1;  // none until init has a context
+    size_t max_proofs = 0;
+    PState* st = nullptr;
+    uint32_t *idx = nullptr, *evs = nullptr, *alp = nullptr, *pa = nullptr, *pb = nullptr;
+    unsigned long long* key = nullptr;
+    // the host entry's staging: allocated by its first call (the device entry never needs it)
+    uint8_t* d_proofs = nullptr;
+    uint32_t *d_lens = nullptr, *d_roots = nullptr, *d_points = nullptr, *d_opened = nullptr, *d_cin = nullptr, *d_cout = nullptr, *d_status = nullptr;
+    hipStream_t stream = nullptr;
+    bool staging_ready = false;
+    ~Impl() {
+        for (void* p : {(void*)st, (void*)idx, (void*)evs, (void*)alp, (void*)pa, (void*)pb, (void*)key, (void*)d_proofs, (void*)d_lens,
+                        (void*)d_roots, (void*)d_points, (void*)d_opened, (void*)d_cin, (void*)d_cout, (void*)d_status})
+            if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+PcsVerifierDev::PcsVerifierDev() : im(new Impl()) {}
+PcsVerifierDev::~PcsVerifierDev() {
+    if (im->device < 0) { delete im; return; }  // init refused before anything was allocated: no device to visit
+    DeviceScope ds(im->device);
+    (void)ds.enter();
+    delete im;
+}
+size_t PcsVerifierDev::proof_len() const { return 4 * (size_t)im->L.proof_words; }
+size_t PcsVerifierDev::max_proofs() const { return im->max_proofs; }
+size_t PcsVerifierDev::total_columns() const { return im->L.total; }
+bool PcsVerifierDev::wave_form() const { return im->L.row_words >= PV_WAVE_MIN_COLS; }
+int PcsVerifierDev::hash() const { return im->L.hash; }
+int PcsVerifierDev::device() const { return im->device; }
+
+int PcsVerifierDev::init(int hash, bool hiding, const FriParams& fp, const PcsShape& shape, size_t max_proofs) {
+    if (int rc = make_layout(hash, hiding, fp, shape, &im->L)) return rc;
+    const PLayout& L = im->L;
+    if (max_proofs == 0) return fail(ERR_BAD_ARG, "pcs_verifier_create: max_proofs must be positive");
+    // the widest grid: one wavefront per (member, query), or one lane per opening
+    if (max_proofs > 0x7fffffffull || max_proofs * (uint64_t)L.nq * std::max(64u, L.n_in + L.n_fri) > 0x7fffffffull * 256ull)
+        return fail(ERR_BAD_ARG, "pcs_verifier_create: max_proofs x num_queries too large");
+    Context* cx = nullptr;
+    if (int rc = get_context(&cx)) return rc;
+    im->device = cx->device;
+    im->max_proofs = max_proofs;
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->st), max_proofs * sizeof(PState)));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->idx), max_proofs * L.nq * 4));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->evs), max_proofs * L.nq * (size_t)L.n_fri * 32));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->alp), max_proofs * (size_t)L.wmax * 16));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->pa), max_proofs * (size_t)L.n_pairs * 16));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->pb), max_proofs * (size_t)L.n_pairs * 16));
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->key), max_proofs * 8));
+    return OK;
+}
+
+int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_roots, const uint32_t* d_points,
+                               const uint32_t* d_opened, const uint32_t* d_chal_in, size_t n, uint32_t* d_status, uint32_t* d_rejected,
+                               uint32_t* d_chal_out, hipStream_t stream) {
+    const PLayout& L = im->L;
+    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (n > im->max_proofs) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: more proofs than the verifier was created for");
+    if (n && (!d_proofs || !d_roots || !d_points || !d_opened || !d_chal_in || !d_status)) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: null argument");
+    if (n && ((stride & 3u) || stride < proof_len())) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: the stride must be a multiple of 4 and at least the proof length");
+    if (misaligned(d_proofs, 4) || misaligned(d_lens, 4) || misaligned(d_roots, 4) || misaligned(d_points, 4) || misaligned(d_opened, 4) ||
+        misaligned(d_status, 4) || misaligned(d_rejected, 4))
+        return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: d_proofs, d_lens, d_roots, d_points, d_opened, d_status and d_rejected must be 4-byte aligned");
+    if (misaligned(d_chal_in, 8) || misaligned(d_chal_out, 8)) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: d_chal_in and d_chal_out must be 8-byte aligned");
+    DeviceScope ds(im->device);
+    if (int rc = ds.enter()) return rc;
+    if (d_rejected) P3_HIP(hipMemsetAsync(d_rejected, 0, 4, stream));
+    if (!n) return OK;
+    PArgs a{d_proofs, stride, d_lens, d_roots, d_points, d_opened, d_chal_in, d_chal_out, (uint32_t)n, im->st, im->idx, im->evs, im->alp, im->pa, im->pb, im->key};
+    hipLaunchKernelGGL(pv_transcript_kernel, dim3((uint32_t)n), dim3(64), 0, stream, a, L);
+    const uint64_t pq = (uint64_t)n * L.nq;
+    if (wave_form()) hipLaunchKernelGGL(pv_query_kernel<true>, dim3((uint32_t)((pq + 3) / 4)), dim3(256), 0, stream, a, L);
+    else hipLaunchKernelGGL(pv_query_kernel<false>, dim3((uint32_t)((pq + 255) / 256)), dim3(256), 0, stream, a, L);
+    const uint64_t lanes = pq * (L.n_in + L.n_fri);
+    if (L.hash == HASH_KECCAK)
+        hipLaunchKernelGGL(pv_open_kernel<HASH_KECCAK>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, a, L);
+    else
+        hipLaunchKernelGGL(pv_open_kernel<HASH_POSEIDON2>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, a, L);
+    hipLaunchKernelGGL(pv_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, im->key, (uint32_t)n, d_status, d_rejected);
+    P3_HIP(hipGetLastError());
+    return OK;
+}
+
+int PcsVerifierDev::verify_host(size_t n, const uint8_t* const* proofs, const size_t* lens, const uint32_t* roots, const uint32_t* points,
+                                const uint32_t* opened, Challenger* const* chals, uint32_t* status_out) {
+    const PLayout& L = im->L;
+    if (n && (!proofs || !lens || !roots || !points || !opened || !chals || !status_out)) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null argument");
+    for (size_t g = 0; g < n; g++) {
+        if (!chals[g]) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null challenger");
+        if (chals[g]->kind != L.hash) return fail(ERR_BAD_ARG, "pcs verify: the challenger belongs to another hash configuration");
+    }
+    DeviceScope ds(im->device);
+    if (int rc = ds.enter()) return rc;
+    const size_t plen = proof_len(), cap = im->max_proofs, SW = CHALLENGER_STATE_WORDS;
+    const size_t rw = (size_t)L.n_in * 8, pw = (size_t)L.n_slots * 4, ow = (size_t)L.total * 4;
+    if (!im->staging_ready) {  // each piece is made once (a call that failed half way is resumed by the next), the flag is set last
+        if (!im->stream) P3_HIP(hipStreamCreateWithFlags(&im->stream, hipStreamNonBlocking));
+        if (!im->d_proofs) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_proofs), cap * plen));
+        if (!im->d_lens) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_lens), cap * 4));
+        if (!im->d_roots) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_roots), cap * rw * 4));
+        if (!im->d_points) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_points), cap * pw * 4));
+        if (!im->d_opened) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_opened), cap * ow * 4));
+        if (!im->d_cin) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_cin), cap * SW * 4));
+        if (!im->d_cout) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_cout), cap * SW * 4));
+        if (!im->d_status) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_status), cap * 4));
+        im->staging_ready = true;
+    }
+    std::vector<uint32_t> hl(cap), hc(cap * SW), ho(cap * SW);
+    for (size_t base = 0; base < n; base += cap) {
+        const size_t m = std::min(cap, n - base);
+        for (size_t k = 0; k < m; k++) {
+            const size_t g = base + k;
+            if (lens[g] == plen) {
+                if (!proofs[g]) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null proof");
+                P3_HIP(hipMemcpyAsync(im->d_proofs + k * plen, proofs[g], plen, hipMemcpyHostToDevice, im->stream));
+                hl[k] = (uint32_t)plen;
+            } else {
+                hl[k] = lens[g] > 0xfffffffeull ? 0xffffffffu : (uint32_t)lens[g];  // a wrong length is rejected unread: nothing is uploaded
+            }
+            challenger_export(*chals[g], hc.data() + k * SW);
+        }
+        P3_HIP(hipMemcpyAsync(im->d_lens, hl.data(), m * 4, hipMemcpyHostToDevice, im->stream));
+        P3_HIP(hipMemcpyAsync(im->d_roots, roots + base * rw, m * rw * 4, hipMemcpyHostToDevice, im->stream));
+        P3_HIP(hipMemcpyAsync(im->d_points, points + base * pw, m * pw * 4, hipMemcpyHostToDevice, im->stream));
+        P3_HIP(hipMemcpyAsync(im->d_opened, opened + base * ow, m * ow * 4, hipMemcpyHostToDevice, im->stream));
+        P3_HIP(hipMemcpyAsync(im->d_cin, hc.data(), m * SW * 4, hipMemcpyHostToDevice, im->stream));
+        if (int rc = verify_dev(im->d_proofs, plen, im->d_lens, im->d_roots, im->d_points, im->d_opened, im->d_cin, m, im->d_status, nullptr,
+                                im->d_cout, im->stream))
+            return rc;
+        P3_HIP(hipMemcpyAsync(status_out + base, im->d_status, m * 4, hipMemcpyDeviceToHost, im->stream));
+        P3_HIP(hipMemcpyAsync(ho.data(), im->d_cout, m * SW * 4, hipMemcpyDeviceToHost, im->stream));
+        P3_HIP(hipStreamSynchronize(im->stream));
+        for (size_t k = 0; k < m; k++)
+            if (status_out[base + k] == 0)
+                if (int rc = challenger_import(ho.data() + k * SW, chals[base + k])) return rc;
+    }
+    return OK;
+}
+
+}  // namespace p3

@@ -162,6 +162,12 @@ class Pcs {
 };
 
 bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big);
+// A challenger as the words a device transcript imports and exports (transcript.hip.h DevState up to `pis`): the duplex state,
+// buffers and counters, then the Keccak streaming sponge.  import refuses counters no challenger can hold (pending inputs >= 8,
+// outputs > 8; pending block >= 136 bytes, output bytes > 32) and leaves *c as it was.
+constexpr uint32_t CHALLENGER_STATE_WORDS = 128;
+void challenger_export(const Challenger& c, uint32_t* words);
+int challenger_import(const uint32_t* words, Challenger* c);
 // verifier.hip: Pcs::verify on the host.  0 = accept; ERR_BAD_ARG for a refused argument; a positive code names the failed check
 // (the numbering of verify_fib_air's FRI half: 5 commit phase length, 6 query count, 7 final polynomial length, 8 trailing or missing
 // bytes, 9 truncated, 11 InvalidPowWitness, 12 query shape, 13 input opening, 14 FRI layer opening, 15 FinalPolyMismatch)

@@ -8,6 +8,20 @@ namespace p3 {
 // dictates; the other codes are the host verifier's (verifier.hip)
 constexpr uint32_t VERIFY_MALFORMED = 16;
 
+// The object's device for the duration of a call (HIP's current device is per thread): both batch verifiers enter their device
+// this way, so a call from a thread whose current device is another one is redirected, not refused.
+struct DeviceScope {
+    int prev = -1, want;
+    bool switched = false;
+    explicit DeviceScope(int dev) : want(dev) {}
+    int enter() {
+        P3_HIP(hipGetDevice(&prev));
+        if (prev != want) { P3_HIP(hipSetDevice(want)); switched = true; }
+        return OK;
+    }
+    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
 // host only: the byte length every proof of the configuration has
 int fib_proof_len(int hash, bool hiding, uint32_t log_n, const FriParams& fp, size_t* len_out);
 

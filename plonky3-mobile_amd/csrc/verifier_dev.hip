@@ -513,18 +513,6 @@ int make_layout(int hash, bool hiding, uint32_t log_n, const FriParams& fp, VLay
     return OK;
 }
 
-struct DeviceScope {  // the object's device for the duration of a call (HIP's current device is per thread)
-    int prev = -1, want;
-    bool switched = false;
-    explicit DeviceScope(int dev) : want(dev) {}
-    int enter() {
-        P3_HIP(hipGetDevice(&prev));
-        if (prev != want) { P3_HIP(hipSetDevice(want)); switched = true; }
-        return OK;
-    }
-    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 int fib_proof_len(int hash, bool hiding, uint32_t log_n, const FriParams& fp, size_t* len_out) {

@@ -13,6 +13,10 @@ from .gpu_dft import MONTY_ONE, P, _is_torch, _stream_ptr, dev_u32
 
 MAX_MATS, MAX_ROUNDS, MAX_POINTS, MAX_COLS = 8, 4, 4, 8192  # csrc/prover.h PCS_MAX_*
 HIDING_MAX_MATS, SALT, MAX_RANDOM_CODEWORDS, MAX_QUOTIENT_WIDTH = 4, 4, 8, 2048  # csrc/prover.h PCS_HIDING_MAX_MATS ...
+STATE_WORDS = 128  # include/p3hip.h P3HIP_CHALLENGER_STATE_WORDS
+MAX_SLOTS = 4  # csrc/pcs_verifier_dev.h PCS_MAX_SLOTS
+# diagnostic, not a stable interface (a tuning detail that moves with measurements; the tests use it to run both forms)
+WAVE_FORM_MIN_COLUMNS = 256  # csrc/pcs_verifier_dev.hip PV_WAVE_MIN_COLS: row words per query from which one wavefront serves a query
 
 
 def _words(a, n=None):
@@ -59,6 +63,17 @@ class Challenger:
         h = C.c_void_p()
         _lib.check(_lib.lib().p3hip_challenger_clone(self._h, C.byref(h)))
         return Challenger(self.hash, h)
+
+    def export_state(self):
+        """The challenger as the STATE_WORDS words a device transcript imports (include/p3hip.h p3hip_challenger_export)."""
+        out = np.zeros(STATE_WORDS, dtype=np.uint32)
+        _lib.check(_lib.lib().p3hip_challenger_export(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def import_state(self, words):
+        """The inverse of export_state; counters no challenger can hold are refused (P3HipError -1, the challenger unchanged)."""
+        w = _words(words, STATE_WORDS)
+        _lib.check(_lib.lib().p3hip_challenger_import(self._h, w.ctypes.data_as(C.c_void_p)))
 
     def free(self):
         if self._h:
@@ -253,3 +268,108 @@ def verify(params, hash, rounds, log_h, opened, proof, challenger, hiding=False)
         opened.ctypes.data_as(C.c_void_p), buf, len(proof), challenger._h, C.byref(code)))
     if code.value:
         raise PcsRejected(code.value, _lib.take_last_error() or "")
+
+
+class _Shape(C.Structure):
+    _fields_ = [("log_h", C.c_uint), ("n_rounds", C.c_size_t), ("mats_per_round", C.POINTER(C.c_size_t)), ("widths", C.POINTER(C.c_size_t)),
+                ("points_per_mat", C.POINTER(C.c_size_t)), ("n_slots", C.c_size_t), ("slots", C.POINTER(C.c_uint32))]
+
+
+def _shape(log_h, rounds, n_slots):
+    """rounds = [[(width, [slot of point 0, ...]) per matrix] per round] -> (p3hip_pcs_shape_t, what it points to)."""
+    mats = [len(r) for r in rounds]
+    widths = [int(w) for r in rounds for w, _ in r]
+    counts = [len(sl) for r in rounds for _, sl in r]
+    slots = [int(x) for r in rounds for _, sl in r for x in sl]
+    keep = ((C.c_size_t * max(len(mats), 1))(*mats), (C.c_size_t * max(len(widths), 1))(*widths),
+            (C.c_size_t * max(len(counts), 1))(*counts), (C.c_uint32 * max(len(slots), 1))(*slots))
+    return _Shape(log_h, len(rounds), keep[0], keep[1], keep[2], n_slots, keep[3]), keep
+
+
+def pcs_proof_len(params, hash, log_h, rounds, n_slots, hiding=False):
+    """The byte length every proof of the shape has (host only; rounds as PcsVerifier takes them)."""
+    sh, _keep = _shape(log_h, rounds, n_slots)
+    out = C.c_size_t()
+    _lib.check(_lib.lib().p3hip_pcs_proof_len(_hash_kind(hash), 1 if hiding else 0, C.cast(params._c(), C.c_void_p), C.byref(sh), C.byref(out)))
+    return out.value
+
+
+class PcsVerifier:
+    """Pcs::verify of TwoAdicFriPcs / HidingFriPcs for batches of members of ONE shape, on the device (include/p3hip.h "batches of PCS
+    proofs verified ON THE DEVICE").  rounds = [[(committed width, [slot of point 0, ...]) per matrix] per round]; a member supplies
+    n_slots points.  Statuses: 0 = accept, the host verifier's codes 11 / 13 / 14 / 15, or VERIFY_MALFORMED (16)."""
+
+    def __init__(self, log_h, rounds, n_slots, params=None, hash="poseidon2", hiding=False, max_proofs=64):
+        self.params = params or FriParameters()
+        self.log_h, self.rounds, self.n_slots, self.hash, self.hiding, self.max_proofs = log_h, rounds, n_slots, hash, hiding, max_proofs
+        self.n_rounds = len(rounds)
+        self.total = sum(int(w) * len(sl) for r in rounds for w, sl in r)
+        sh, _keep = _shape(log_h, rounds, n_slots)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p3hip_pcs_verifier_create(_hash_kind(hash), 1 if hiding else 0, C.cast(self.params._c(), C.c_void_p), C.byref(sh),
+                                                        max_proofs, C.byref(self._h)))
+        self.proof_len = pcs_proof_len(self.params, hash, log_h, rounds, n_slots, hiding)
+        self.wave_form = bool(_lib.lib().p3hip_pcs_verifier_wave_form(self._h))
+
+    def verify_many(self, proofs, roots, points, opened, challengers):
+        """proofs: a list of bytes; roots (n, n_rounds, 8), points (n, n_slots, 4), opened (n, total, 4): numpy uint32; challengers: a
+        list of Challenger, each the member's transcript before verification — an accepted member's is advanced as the host
+        verifier advances it, a rejected member's is left alone.  Returns a numpy uint32 array of statuses; batches larger than
+        max_proofs are split."""
+        n = len(proofs)
+        status = np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return status
+        if len(challengers) != n:
+            raise ValueError("one challenger per proof")
+        r, p, o = _words(roots, n * self.n_rounds * 8), _words(points, n * self.n_slots * 4), _words(opened, n * self.total * 4)
+        ptrs = (C.c_char_p * n)(*[bytes(x) for x in proofs])
+        lens = (C.c_size_t * n)(*[len(x) for x in proofs])
+        ch = (C.c_void_p * n)(*[c._h for c in challengers])
+        _lib.check(_lib.lib().p3hip_pcs_verifier_verify(self._h, n, ptrs, lens, r.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
+                                                        o.ctypes.data_as(C.c_void_p), ch, status.ctypes.data_as(_lib.u32p)))
+        return status
+
+    def verify_many_dev(self, proofs, roots, points, opened, chal_in, lens=None, n=None, stride=None, status=None, rejected=None,
+                        chal_out=None):
+        """The device entry on torch tensors, enqueued on torch's current stream and not synchronised.  proofs: a contiguous uint8 /
+        int32 device tensor, proof i at byte i * stride (default: the row length of a 2-d tensor); roots, points, opened, chal_in:
+        contiguous 32-bit device tensors of n x n_rounds x 8, n x n_slots x 4, n x total x 4 and n x STATE_WORDS words; lens: n 32-bit
+        byte lengths or None.  Returns (status, rejected, chal_out): int32 device tensors of n codes, one count and n x STATE_WORDS
+        words (chal_out=False: no transcripts are written, None is returned)."""
+        import torch
+        if n is None:
+            n = chal_in.shape[0]
+        if stride is None:
+            stride = proofs.stride(0) * proofs.element_size() if proofs.dim() == 2 else self.proof_len
+        need = ((roots, n * self.n_rounds * 8), (points, n * self.n_slots * 4), (opened, n * self.total * 4), (chal_in, n * STATE_WORDS))
+        for t, words in need + (((lens, n),) if lens is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() < words:
+                raise ValueError("expected contiguous device tensors of 32-bit words, one row per member")
+        if not proofs.is_cuda or not proofs.is_contiguous():
+            raise ValueError("expected contiguous device tensors")
+        if n and proofs.numel() * proofs.element_size() < (n - 1) * stride + self.proof_len:
+            raise ValueError("the proofs tensor is shorter than n proofs")
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=proofs.device)
+        if rejected is None:
+            rejected = torch.empty(1, dtype=torch.int32, device=proofs.device)
+        if chal_out is None:
+            chal_out = torch.empty((max(n, 1), STATE_WORDS), dtype=torch.int32, device=proofs.device)
+        _lib.check(_lib.lib().p3hip_pcs_verifier_verify_dev(
+            self._h, C.c_void_p(proofs.data_ptr()), stride, C.c_void_p(lens.data_ptr()) if lens is not None else None,
+            C.c_void_p(roots.data_ptr()), C.c_void_p(points.data_ptr()), C.c_void_p(opened.data_ptr()), C.c_void_p(chal_in.data_ptr()), n,
+            C.c_void_p(status.data_ptr()), C.c_void_p(rejected.data_ptr()), C.c_void_p(chal_out.data_ptr()) if chal_out is not False else None,
+            _stream_ptr()))
+        return status[:n], rejected, (chal_out[:n] if chal_out is not False else None)
+
+    def close(self):
+        if self._h:
+            _lib.lib().p3hip_pcs_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
