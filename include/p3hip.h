@@ -471,7 +471,8 @@ int p3hip_challenger_import(p3hip_challenger_t *c, const uint32_t words[P3HIP_CH
  *      the trace's log height.  An opening point on the LDE coset GENERATOR * <g_big> (a base-field z with (z / GENERATOR)^big = 1:
  *      upstream panics on the zero denominator) is refused on the host before anything is launched, naming round, matrix and point.
  *      Batches of proofs of one shape are verified on the device by p3hip_pcs_verifier_* (the section after the hiding PCS).
- *      Not covered: mixed heights.  HidingFriPcs: the section after this one. ---- */
+ *      MIXED HEIGHTS are opt-in at creation (p3hip_pcs_create_mixed, verified by p3hip_pcs_verify_mixed; below): an object from
+ *      p3hip_pcs_create refuses them as stated above.  HidingFriPcs: the section after this one. ---- */
 typedef struct p3hip_pcs p3hip_pcs_t;
 typedef struct p3hip_pcs_data p3hip_pcs_data_t;
 /* TwoAdicFriPcs::new(dft, mmcs, fri_params); stream / own_stream as p3hip_fib_prover_create */
@@ -503,6 +504,29 @@ int p3hip_pcs_verify(int hash, const p3hip_fri_params_t *params, unsigned log_h,
                      const size_t *mats_per_round, const size_t *widths, size_t n_rounds, const size_t *points_per_mat,
                      const uint32_t *points, const uint32_t *opened, const uint8_t *proof, size_t len,
                      p3hip_challenger_t *challenger, int *reject_code);
+/* The same object with matrices of MIXED heights admitted (upstream TwoAdicFriPcs's general case; from recall, parity unpinned: DESIGN.md
+ * section 3).  p3hip_pcs_commit_dev, p3hip_pcs_lde_dev (the height is the matrix's own) and p3hip_pcs_open serve it with the signatures
+ * above; a same-height open on it is the open of a p3hip_pcs_create object, launch for launch.  A CLASS is the set of matrices of one
+ * open that share log_big_m = log_h_m + log_blowup; log_big is the tallest class's.  One commitment is one tree over LDEs of their own
+ * heights (MerkleTreeMmcs injects the shorter ones), in input order.  Opened values are observed round -> matrix -> point -> column.
+ * Every class keeps its own count of alpha powers: a (matrix, point) pair of width w takes alpha^c .. alpha^(c + w - 1), c its class's
+ * count so far.  Every class with a point has one reduced-opening vector ro_c over GENERATOR * <g_big_c>; the commit phase starts from
+ * the tallest class's and adds beta^2 ro_c to the folded vector right after the fold that reaches 2^log_big_c elements, beta that
+ * round's challenge (a class with log_h_c == log_final_poly_len goes into the final vector).  A query index has log_big bits; round r's
+ * BatchOpening is opened at index >> (log_big - log_big_r), log_big_r the round's tallest LDE, which is its depth word and path length.
+ * Refused by name before any launch or draw (P3HIP_ERR_BAD_ARG, challenger unchanged): no matrix of the tallest height has an opening
+ * point (the FRI input would be missing); a matrix with log_h_m < log_final_poly_len; a point on the TALLEST LDE coset (it contains
+ * every smaller one); the capacities above, with log_h the tallest log height.  Not covered: a hiding object (p3hip_pcs_create_hiding)
+ * and the device batch verifier (p3hip_pcs_verifier_*) stay same-height. */
+int p3hip_pcs_create_mixed(int profile, int hash, const p3hip_fri_params_t *params, void *stream, int own_stream, p3hip_pcs_t **out);
+/* Pcs::verify for mixed heights, host code: p3hip_pcs_verify with log_heights (one per matrix, round -> matrix) in place of log_h.  With
+ * all heights equal it returns what p3hip_pcs_verify returns for the same bytes: the same return code and the same *reject_code.  (Of
+ * an argument set with SEVERAL faults the two may name different ones in the message: this entry looks at the round and matrix counts
+ * first, since it needs them to read log_heights.)  Reject codes as p3hip_pcs_verify. */
+int p3hip_pcs_verify_mixed(int hash, const p3hip_fri_params_t *params, const unsigned *log_heights, const uint32_t *roots /* 8 per round */,
+                           const size_t *mats_per_round, const size_t *widths, size_t n_rounds, const size_t *points_per_mat,
+                           const uint32_t *points, const uint32_t *opened, const uint8_t *proof, size_t len,
+                           p3hip_challenger_t *challenger, int *reject_code);
 void p3hip_pcs_data_free(p3hip_pcs_data_t *d);
 void p3hip_pcs_destroy(p3hip_pcs_t *pcs);
 
@@ -517,7 +541,7 @@ void p3hip_pcs_destroy(p3hip_pcs_t *pcs);
  *      every matrix and its salt); the 8192 batched columns count the random columns.  The rounds of one open are all hiding and of
  *      one configuration (hash, blowup, number of random codewords).  Opened values include the random columns.
  *      Batches of hiding proofs of one shape are verified on the device by p3hip_pcs_verifier_* (the next section).
- *      Not covered: mixed heights, more than 4 matrices per hiding commitment. ---- */
+ *      Not covered: mixed heights (a hiding object never accepts them), more than 4 matrices per hiding commitment. ---- */
 /* HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over MerkleTreeHidingMmcs::new(..,
  * SmallRng::seed_from_u64(mmcs_seed)) (fib_air.rs:40-65: 4, 1, 1); num_random_codewords in 1..8 */
 int p3hip_pcs_create_hiding(int profile, int hash, const p3hip_fri_params_t *params, unsigned num_random_codewords, uint64_t mmcs_seed,

@@ -345,11 +345,12 @@ class TwoAdicFriPcs {
         std::vector<uint32_t> opened;  // 4 words per value
         std::vector<uint8_t> proof;    // the FriProof section of the wire format
     };
+    // mixed_heights: commit and open take matrices of any power-of-two heights (p3hip_pcs_create_mixed); false: refused by name
     explicit TwoAdicFriPcs(FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2, int profile = P3HIP_PROFILE_LATENCY,
-                           void* stream = nullptr, bool own_stream = true)
+                           void* stream = nullptr, bool own_stream = true, bool mixed_heights = false)
         : fp_(fp), hash_(hash) {
         p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
-        check(p3hip_pcs_create(profile, hash, &c, stream, own_stream ? 1 : 0, &h_));
+        check((mixed_heights ? p3hip_pcs_create_mixed : p3hip_pcs_create)(profile, hash, &c, stream, own_stream ? 1 : 0, &h_));
     }
     TwoAdicFriPcs(const TwoAdicFriPcs&) = delete;
     TwoAdicFriPcs& operator=(const TwoAdicFriPcs&) = delete;
@@ -392,6 +393,17 @@ class TwoAdicFriPcs {
         int code = 0;
         check(p3hip_pcs_verify(hash_, &c, log_h, roots.data(), mats_per_round.data(), widths.data(), mats_per_round.size(), points_per_mat.data(),
                                points.data(), opened.data(), proof.data(), proof.size(), challenger.handle(), &code));
+        return code;
+    }
+    // the same for matrices of mixed heights: one log height per matrix, round -> matrix (p3hip_pcs_verify_mixed)
+    int verify(const std::vector<unsigned>& log_heights, const std::vector<uint32_t>& roots, const std::vector<size_t>& mats_per_round,
+               const std::vector<size_t>& widths, const std::vector<size_t>& points_per_mat, const std::vector<uint32_t>& points,
+               const std::vector<uint32_t>& opened, const std::vector<uint8_t>& proof, Challenger& challenger) const {
+        if (log_heights.size() != widths.size()) throw Error(P3HIP_ERR_BAD_ARG, "TwoAdicFriPcs::verify: one log height per matrix");
+        p3hip_fri_params_t c{fp_.log_blowup, fp_.log_final_poly_len, fp_.num_queries, fp_.proof_of_work_bits};
+        int code = 0;
+        check(p3hip_pcs_verify_mixed(hash_, &c, log_heights.data(), roots.data(), mats_per_round.data(), widths.data(), mats_per_round.size(),
+                                     points_per_mat.data(), points.data(), opened.data(), proof.data(), proof.size(), challenger.handle(), &code));
         return code;
     }
 

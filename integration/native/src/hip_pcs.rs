@@ -129,6 +129,30 @@ extern "C" {
         challenger: *mut p3hip_challenger_t,
         reject_code: *mut i32,
     ) -> i32;
+    fn p3hip_pcs_create_mixed(
+        profile: i32,
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        stream: *mut c_void,
+        own_stream: i32,
+        out: *mut *mut p3hip_pcs_t,
+    ) -> i32;
+    fn p3hip_pcs_verify_mixed(
+        hash: i32,
+        params: *const p3hip_fri_params_t,
+        log_heights: *const u32,
+        roots: *const u32,
+        mats_per_round: *const usize,
+        widths: *const usize,
+        n_rounds: usize,
+        points_per_mat: *const usize,
+        points: *const u32,
+        opened: *const u32,
+        proof: *const u8,
+        len: usize,
+        challenger: *mut p3hip_challenger_t,
+        reject_code: *mut i32,
+    ) -> i32;
     fn p3hip_pcs_create_hiding(
         profile: i32,
         hash: i32,

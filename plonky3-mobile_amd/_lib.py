@@ -138,6 +138,10 @@ _SIGS = {
                                  C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
     "p3hip_pcs_verify": (C.c_int, [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t,
                                    C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
+    "p3hip_pcs_create_mixed": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "p3hip_pcs_verify_mixed": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_uint), C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                         C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_int)]),
     "p3hip_pcs_create_hiding": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int,
                                           C.POINTER(C.c_void_p)]),
     "p3hip_pcs_commit_quotient_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,

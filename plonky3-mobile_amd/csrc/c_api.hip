@@ -1228,7 +1228,7 @@ int p3hip_challenger_clone(const p3hip_challenger_t* c, p3hip_challenger_t** out
 }
 void p3hip_challenger_destroy(p3hip_challenger_t* c) { delete c; }
 
-int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t* params, void* stream, int own_stream, p3hip_pcs_t** out) {
+static int pcs_create_plain(int profile, int hash, const p3hip_fri_params_t* params, void* stream, int own_stream, bool mixed, p3hip_pcs_t** out) {
     return guarded([&]() -> int {
         if (!params || !out) return fail(ERR_BAD_ARG, "pcs_create: null argument");
         if (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY) return fail(ERR_BAD_ARG, "pcs_create: unknown profile");
@@ -1244,10 +1244,16 @@ int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t* params, vo
         std::unique_ptr<p3hip_pcs> p(new p3hip_pcs());
         FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
         // on failure the object's destructor destroys the owned stream
-        if ((rc = p->pcs.init(fp, st, own, hash, profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY))) return rc;
+        if ((rc = p->pcs.init(fp, st, own, hash, profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY, mixed))) return rc;
         *out = p.release();
         return OK;
     });
+}
+int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t* params, void* stream, int own_stream, p3hip_pcs_t** out) {
+    return pcs_create_plain(profile, hash, params, stream, own_stream, false, out);
+}
+int p3hip_pcs_create_mixed(int profile, int hash, const p3hip_fri_params_t* params, void* stream, int own_stream, p3hip_pcs_t** out) {
+    return pcs_create_plain(profile, hash, params, stream, own_stream, true, out);
 }
 int p3hip_pcs_create_hiding(int profile, int hash, const p3hip_fri_params_t* params, unsigned num_random_codewords, uint64_t mmcs_seed,
                             uint64_t pcs_seed, void* stream, int own_stream, p3hip_pcs_t** out) {
@@ -1310,7 +1316,7 @@ int p3hip_pcs_lde_dev(const p3hip_pcs_data_t* data, size_t mat, const uint32_t**
         if (!data || !d_lde || !height || !width) return fail(ERR_BAD_ARG, "pcs_lde: null argument");
         if (mat >= data->d->lde.size()) return fail(ERR_BAD_ARG, "pcs_lde: matrix " + std::to_string(mat) + " of a commitment of " + std::to_string(data->d->lde.size()));
         *d_lde = data->d->lde[mat];
-        *height = (size_t)1 << data->d->log_big;
+        *height = (size_t)1 << (data->d->mat_log_h(mat) + (data->d->log_big - data->d->log_h));  // the matrix's own LDE
         *width = data->d->widths[mat];
         return OK;
     });
@@ -1346,6 +1352,23 @@ int p3hip_pcs_verify(int hash, const p3hip_fri_params_t* params, unsigned log_h,
         std::string why;
         Challenger ch = challenger->c;
         int rc = pcs_verify(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, &ch, &why);
+        if (rc < 0) return fail(rc, why);
+        challenger->c = ch;  // accepted or rejected, the transcript is where the verifier left it
+        if (rc > 0) { *reject_code = rc; set_error("pcs verification failed: " + why); }
+        return OK;
+    });
+}
+int p3hip_pcs_verify_mixed(int hash, const p3hip_fri_params_t* params, const unsigned* log_heights, const uint32_t* roots,
+                           const size_t* mats_per_round, const size_t* widths, size_t n_rounds, const size_t* points_per_mat,
+                           const uint32_t* points, const uint32_t* opened, const uint8_t* proof, size_t len, p3hip_challenger_t* challenger,
+                           int* reject_code) {
+    return guarded([&]() -> int {
+        if (!params || !challenger || !reject_code) return fail(ERR_BAD_ARG, "pcs_verify_mixed: null argument");
+        *reject_code = 0;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::string why;
+        Challenger ch = challenger->c;
+        int rc = pcs_verify_mixed(hash, fp, log_heights, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, &ch, &why);
         if (rc < 0) return fail(rc, why);
         challenger->c = ch;  // accepted or rejected, the transcript is where the verifier left it
         if (rc > 0) { *reject_code = rc; set_error("pcs verification failed: " + why); }

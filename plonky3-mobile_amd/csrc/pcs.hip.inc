@@ -1,6 +1,10 @@
 // TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over CALLER-SUPPLIED matrices: commit, open (prover.h Pcs).
 // Included by prover.hip (same namespace: ProverCore, QTree, the transcript kernels, the grind and query kernels are shared; the
-// fib kernels above are left as they are).  Every matrix of one open has the same height h.  On a hiding object (pcs_hiding.hip.inc, included at
+// fib kernels above are left as they are).  Every matrix of one open has the same height h, unless the object admits MIXED heights
+// (init's mixed_heights; include/p3hip.h p3hip_pcs_create_mixed states the protocol): then a CLASS is the set of matrices that share
+// log_big_m, each class has its own alpha counter and reduced-opening vector, and the fold that reaches a class's length adds beta^2 ro_c
+// (fri_fold_rollin_kernel, prover.hip).  One run of pcs_inv_denoms_kernel over the tallest domain serves every class: in bit-reversed order
+// the first big_c rows of GENERATOR * <g_big> are GENERATOR * <g_big_c>.  On a hiding object (pcs_hiding.hip.inc, included at
 // the end: HidingFriPcs) commit randomizes and salts, and open runs here over the committed matrices with salts in every opening.
 //
 // Conventions are the test oracle's restatement of upstream (stark.c, cited by line):
@@ -89,9 +93,9 @@ __global__ void __launch_bounds__(256) pcs_inv_denoms_kernel(TwoLevelTable roots
 // contiguous words rows r .. r + rps of the tile; a matrix wider than 64 takes one tile per blockIdx.y.
 struct PcsBaryArgs {
     const uint32_t* lde;
-    const uint32_t* xd;  // [K][h]
+    const uint32_t* xd;  // [K][xstride], the matrix reads the first h of each
     uint32_t* partials;  // [nblk][NP][w] extension elements
-    uint32_t w, h, pidx[PCS_MAX_POINTS];
+    uint32_t w, h, xstride, pidx[PCS_MAX_POINTS];
 };
 template <int NP>
 __global__ void __launch_bounds__(256) pcs_bary_kernel(PcsBaryArgs a) {
@@ -115,7 +119,7 @@ __global__ void __launch_bounds__(256) pcs_bary_kernel(PcsBaryArgs a) {
             const uint32_t va = a.lde[(size_t)r * w + col], vb = two ? a.lde[(size_t)r2 * w + col] : 0u;
 #pragma unroll
             for (int p = 0; p < NP; p++) {
-                const uint32_t* xd = a.xd + 4 * (size_t)a.pidx[p] * h;
+                const uint32_t* xd = a.xd + 4 * (size_t)a.pidx[p] * a.xstride;
                 const Ext ea = ld_ext(xd + 4 * (size_t)r), eb = ld_ext(xd + 4 * (size_t)r2);
 #pragma unroll
                 for (int c = 0; c < 4; c++) acc[p].c[c] = bb::add(acc[p].c[c], bb::dot2(ea.c[c], va, eb.c[c], vb));
@@ -153,9 +157,11 @@ __global__ void __launch_bounds__(256) pcs_partial_sum_kernel(const uint32_t* pa
     }
 }
 
-// A (matrix, point) pair in observation order: its first column's index among all opened values, its width, its point
+// A (matrix, point) pair in observation order: its first column's index among all opened values, its width, its point, the exponent of
+// its first alpha power (its class's counter: ooff when every matrix has one height), and its matrix's height: log_h, GENERATOR^h and
+// 1 / (h GENERATOR^h)
 struct PcsPair {
-    uint32_t ooff, width, point, pad;
+    uint32_t ooff, width, point, aoff, log_h, sn, denom, pad;
 };
 struct PcsOpenArgs {
     TsArgs ts;
@@ -163,25 +169,30 @@ struct PcsOpenArgs {
     const PcsPair* pairs;
     uint32_t* alp;         // [total] extension elements: alpha^i
     Ext z[PCS_MAX_POINTS];
-    uint32_t n_points, n_pairs, total, log_h, sn, denom;
+    uint32_t n_points, n_pairs, total, log_h, sn, denom;  // total: the length of the alpha table; log_h, sn, denom: the tallest height's
 };
 __device__ __forceinline__ Ext pcs_pick(const Ext* f, uint32_t k) { return k == 0 ? f[0] : k == 1 ? f[1] : k == 2 ? f[2] : f[3]; }
-// finish the opened values (interpolate_coset's factor (z^h - s^h) / (h s^h)), put them into the staging buffer, observe them in
-// order, sample the batching challenge and fill its power table (lane l: alpha^l, alpha^(l + 64), ...)
+// finish the opened values (interpolate_coset's factor (z^h - s^h) / (h s^h), h the pair's own height), put them into the staging
+// buffer, observe them in order, sample the batching challenge and fill its power table (lane l: alpha^l, alpha^(l + 64), ...)
+__device__ __forceinline__ void pcs_bary_factors(const PcsOpenArgs& a, uint32_t log_h, uint32_t sn, uint32_t denom, Ext* f) {
+#pragma unroll
+    for (uint32_t k = 0; k < PCS_MAX_POINTS; k++) {
+        Ext z = a.z[k < a.n_points ? k : 0];
+        for (uint32_t i = 0; i < log_h; i++) z = bb::sqr(z);
+        f[k] = bb::scale(bb::sub(z, bb::ext_from_base(sn)), denom);
+    }
+}
 __global__ void __launch_bounds__(64) pcs_ts_open_kernel(PcsOpenArgs a) {
     P3_LATENCY_BOUND_KERNEL();
     __shared__ KState ks;
     DevChal ch;
     ch.begin(a.ts.kind, a.ts.ds, &ks, false);
     Ext f[PCS_MAX_POINTS];
-#pragma unroll
-    for (uint32_t k = 0; k < PCS_MAX_POINTS; k++) {
-        Ext z = a.z[k < a.n_points ? k : 0];
-        for (uint32_t i = 0; i < a.log_h; i++) z = bb::sqr(z);
-        f[k] = bb::scale(bb::sub(z, bb::ext_from_base(a.sn)), a.denom);
-    }
+    uint32_t f_log_h = a.log_h;  // the factors in f are this height's: recomputed when a pair of another height comes (mixed heights)
+    pcs_bary_factors(a, a.log_h, a.sn, a.denom, f);
     for (uint32_t p = 0; p < a.n_pairs; p++) {
         const PcsPair pr = a.pairs[p];
+        if (pr.log_h != f_log_h) { pcs_bary_factors(a, pr.log_h, pr.sn, pr.denom, f); f_log_h = pr.log_h; }
         const Ext fp = pcs_pick(f, pr.point);
         for (uint32_t c = 0; c < pr.width; c++) {
             const uint32_t i = pr.ooff + c;
@@ -216,7 +227,7 @@ __global__ void __launch_bounds__(256) pcs_y_kernel(const PcsPair* pairs, uint32
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 0; k < 4; k++) y.c[k] = bb::add(bb::add(red[0][k], red[1][k]), bb::add(red[2][k], red[3][k]));
-        const Ext ao = ld_ext(alp + 4 * (size_t)pr.ooff);
+        const Ext ao = ld_ext(alp + 4 * (size_t)pr.aoff);
         st_ext(ay + 8 * (size_t)blockIdx.x, ao);
         st_ext(ay + 8 * (size_t)blockIdx.x + 4, bb::mul(ao, y));
     }
@@ -227,16 +238,16 @@ __global__ void __launch_bounds__(256) pcs_y_kernel(const PcsPair* pairs, uint32
 struct PcsReducedArgs {
     const uint32_t* lde;
     const uint32_t* alp;
-    const uint32_t* d;   // [K][big]
+    const uint32_t* d;   // [K][dstride], the matrix reads the first big of each
     const uint32_t* ay;  // [n_pairs][2]
     uint32_t* ro;
-    uint32_t w, big, np, first, pidx[PCS_MAX_POINTS], pair[PCS_MAX_POINTS];
+    uint32_t w, big, dstride, np, first, pidx[PCS_MAX_POINTS], pair[PCS_MAX_POINTS];
 };
 __device__ __forceinline__ void pcs_reduced_tail(const PcsReducedArgs& a, uint32_t j, const Ext& s) {
     Ext r = a.first ? bb::ext_zero() : ld_ext(a.ro + 4 * (size_t)j);
     for (uint32_t p = 0; p < a.np; p++) {
         const Ext ao = ld_ext(a.ay + 8 * (size_t)a.pair[p]), aoy = ld_ext(a.ay + 8 * (size_t)a.pair[p] + 4);
-        const Ext e = ld_ext(a.d + 4 * ((size_t)a.pidx[p] * a.big + j));
+        const Ext e = ld_ext(a.d + 4 * ((size_t)a.pidx[p] * a.dstride + j));
         r = bb::add(r, bb::mul(bb::sub(aoy, bb::mul(ao, s)), e));
     }
     st_ext(a.ro + 4 * (size_t)j, r);
@@ -390,6 +401,7 @@ struct Pcs::Impl {
     int hash = HASH_POSEIDON2, profile = PROFILE_LATENCY, device = -1;
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    bool mixed = false;  // matrices of mixed heights are admitted (init's mixed_heights)
     FriParams fp{};
     DevState* ds = nullptr;
     // open scratch: allocated at first use, grown when a larger shape arrives
@@ -433,6 +445,7 @@ struct Pcs::Impl {
     uint32_t* host_stage = nullptr;
     DevState host_ds;
     std::vector<PcsPair> host_pairs;
+    std::vector<uint32_t*> class_ro;  // by log_h: the reduced-opening vector of a class below the tallest (in the arena), or null
     ~Impl() {
         core.reset();
         if (host_stage) (void)hipHostFree(host_stage);
@@ -448,7 +461,7 @@ Pcs::Pcs() : im(new Impl()) {}
 Pcs::~Pcs() { delete im; }
 hipStream_t Pcs::stream() const { return im->stream; }
 
-int Pcs::init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile) {
+int Pcs::init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile, bool mixed_heights) {
     Impl& s = *im;
     s.stream = stream; s.own_stream = own_stream;  // recorded first: an owned stream is destroyed with the object even when init fails
     if (profile != PROFILE_THROUGHPUT && profile != PROFILE_LATENCY) return fail(ERR_BAD_ARG, "pcs: unknown profile");
@@ -456,7 +469,7 @@ int Pcs::init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash
     if (fp.log_blowup < 1) return fail(ERR_BAD_ARG, "pcs: log_blowup must be >= 1");
     if (fp.log_blowup + 1 > MAX_LOG_DOMAIN) return fail(ERR_BAD_ARG, "pcs: log_blowup too large");
     if (fp.proof_of_work_bits > 30) return fail(ERR_BAD_ARG, "pcs: proof_of_work_bits too large");
-    s.hash = hash; s.profile = profile; s.fp = fp;
+    s.hash = hash; s.profile = profile; s.fp = fp; s.mixed = mixed_heights;
     P3_HIP(hipGetDevice(&s.device));
     P3_HIP(hipMalloc(reinterpret_cast<void**>(&s.ds), sizeof(DevState)));
     return OK;
@@ -474,25 +487,28 @@ int Pcs::commit(const uint32_t* const* d_evals, const size_t* heights, const siz
     int rc = get_context(&cxp);
     if (rc) return rc;
     if (cxp->device != s.device) return fail(ERR_BAD_ARG, "pcs commit: created on device " + std::to_string(s.device) + ", current device is " + std::to_string(cxp->device));
-    const size_t h = heights[0];
+    size_t h = heights[0];  // the tallest
     for (size_t m = 0; m < n_mats; m++) {
         const std::string who = "pcs commit: matrix " + std::to_string(m);
         if (!d_evals[m]) return fail(ERR_BAD_ARG, who + " is null");
         if (!is_pow2(heights[m]) || heights[m] < 2) return fail(ERR_BAD_ARG, who + ": height must be a power of two >= 2");
-        if (heights[m] != h)
+        if (heights[m] != h && !s.mixed)
             return fail(ERR_BAD_ARG, who + " has height " + std::to_string(heights[m]) + ", matrix 0 has " + std::to_string(h) + ": mixed heights are not supported");
+        h = std::max(h, heights[m]);
         if (widths[m] < 1 || widths[m] > PCS_MAX_COLS) return fail(ERR_BAD_ARG, who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
         if (shifts && (shifts[m] == 0 || shifts[m] >= bb::P)) return fail(ERR_BAD_ARG, who + ": domain shift must be a nonzero field element (Montgomery word)");
     }
     const uint32_t log_h = log2u(h);
     if (log_h + s.fp.log_blowup > MAX_LOG_DOMAIN)
         return fail(ERR_BAD_ARG, "pcs commit: LDE domain above 2^" + std::to_string(MAX_LOG_DOMAIN) + " points (log_h + log_blowup)");
-    const size_t big = h << s.fp.log_blowup;
     std::unique_ptr<PcsData> data(new PcsData());
     data->log_h = log_h; data->log_big = log_h + s.fp.log_blowup; data->hash = s.hash; data->device = s.device;
     const uint32_t gen = bb::to_monty(bb::GEN);
-    std::vector<size_t> hh(n_mats, big);
+    std::vector<size_t> hh(n_mats);  // the LDEs' heights: one tree over them, the shorter ones injected (mmcs_commit)
     for (size_t m = 0; m < n_mats; m++) {
+        const size_t h = heights[m], big = h << s.fp.log_blowup;
+        hh[m] = big;
+        if (s.mixed) data->log_hs.push_back(log2u(h));
         uint32_t* p = nullptr;
         P3_HIP(hipMalloc(reinterpret_cast<void**>(&p), big * widths[m] * 4 + 64));
         data->lde.push_back(p);
@@ -521,14 +537,25 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     Context& cx = *cxp;
     if (cx.device != s.device) return fail(ERR_BAD_ARG, "pcs open: created on device " + std::to_string(s.device) + ", current device is " + std::to_string(cx.device));
     // ---- the shape, the distinct points, the pairs in observation order (round -> matrix -> point) ----
-    struct Mat { const uint32_t* lde; uint32_t w, np, ooff, pidx[PCS_MAX_POINTS], pair[PCS_MAX_POINTS]; };
+    // A class: the matrices whose LDEs share log_big_m (one, the tallest, unless the object admits mixed heights); it keeps its own
+    // count of alpha powers (cnt) and its height's interpolation constants; with a point it has its own reduced-opening vector (the
+    // tallest class's is the FRI input core.fri_vec, a shorter class's is Impl::class_ro, in the shape's arena)
+    struct Mat { const uint32_t* lde; uint32_t w, np, ooff, log_h, pidx[PCS_MAX_POINTS], pair[PCS_MAX_POINTS]; };
+    struct Class { uint32_t cnt = 0, sn = 0, denom = 0; bool started = false; };
     std::vector<Mat> mats;
     std::vector<uint32_t> shape;
+    Class cls[MAX_LOG_DOMAIN + 1];  // by log_h
     Ext zs[PCS_MAX_POINTS];
     uint32_t n_points = 0, total = 0;
     s.host_pairs.clear();
     if (!rounds[0]) return fail(ERR_BAD_ARG, "pcs open: round 0 is null");
-    const uint32_t log_h = rounds[0]->log_h, log_big = rounds[0]->log_big;
+    uint32_t log_h = rounds[0]->log_h;  // the tallest
+    if (s.mixed)
+        for (size_t r = 0; r < n_rounds; r++) {
+            if (!rounds[r]) return fail(ERR_BAD_ARG, "pcs open: round " + std::to_string(r) + " is null");
+            log_h = std::max(log_h, rounds[r]->log_h);
+        }
+    const uint32_t log_big = log_h + s.fp.log_blowup, gen = bb::to_monty(bb::GEN);
     shape.push_back(log_h);
     size_t mi = 0, pi = 0;
     for (size_t r = 0; r < n_rounds; r++) {
@@ -541,12 +568,20 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         shape.push_back((uint32_t)dt->lde.size());
         for (size_t m = 0; m < dt->lde.size(); m++, mi++) {
             const std::string who = "pcs open: round " + std::to_string(r) + " matrix " + std::to_string(m);
-            if (dt->log_h != log_h)
-                return fail(ERR_BAD_ARG, who + " has height 2^" + std::to_string(dt->log_h) + ", round 0 has 2^" + std::to_string(log_h) + ": mixed heights are not supported");
+            const uint32_t mlh = dt->mat_log_h(m);
+            if (mlh != log_h && !s.mixed)
+                return fail(ERR_BAD_ARG, who + " has height 2^" + std::to_string(mlh) + ", round 0 has 2^" + std::to_string(log_h) + ": mixed heights are not supported");
+            if (s.mixed && mlh < s.fp.log_final_poly_len)
+                return fail(ERR_BAD_ARG, who + " has height 2^" + std::to_string(mlh) + ", below the final polynomial's 2^" + std::to_string(s.fp.log_final_poly_len));
             const size_t np = points_per_mat[mi];
             if (np > PCS_MAX_POINTS) return fail(ERR_BAD_ARG, who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
-            Mat mt{dt->lde[m], (uint32_t)dt->widths[m], (uint32_t)np, total, {0}, {0}};
-            shape.push_back(mt.w); shape.push_back(mt.np);
+            Mat mt{dt->lde[m], (uint32_t)dt->widths[m], (uint32_t)np, total, mlh, {0}, {0}};
+            shape.push_back(mt.w); shape.push_back(mt.np); shape.push_back(mlh);
+            Class& cl = cls[mlh];
+            if (np && !cl.sn) {  // interpolate_coset's constants of this height
+                cl.sn = bb::pow(gen, 1ull << mlh);
+                cl.denom = bb::inv(bb::mul(bb::to_monty(1u << mlh), cl.sn));
+            }
             for (size_t p = 0; p < np; p++, pi++) {
                 const uint32_t* z = points + 4 * pi;
                 const std::string pw = who + " point " + std::to_string(p);
@@ -559,8 +594,8 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
                     memcpy(zs[n_points++].c, z, 16);
                 }
                 mt.pidx[p] = k; mt.pair[p] = (uint32_t)s.host_pairs.size();
-                s.host_pairs.push_back(PcsPair{total, mt.w, k, 0});
-                total += mt.w;
+                s.host_pairs.push_back(PcsPair{total, mt.w, k, cl.cnt, mlh, cl.sn, cl.denom, 0});
+                total += mt.w; cl.cnt += mt.w;
                 if (total > PCS_MAX_COLS)
                     return fail(ERR_BAD_ARG, pw + ": more than " + std::to_string(PCS_MAX_COLS) + " batched columns (sum of width over every (matrix, point) pair)");
             }
@@ -568,8 +603,11 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         }
     }
     if (total == 0) return fail(ERR_BAD_ARG, "pcs open: no opening point");
+    if (!cls[log_h].cnt)
+        return fail(ERR_BAD_ARG, "pcs open: no matrix of the tallest height 2^" + std::to_string(log_h) + " has an opening point: the FRI input would be missing");
     const uint32_t h = 1u << log_h, big = 1u << log_big, n_pairs = (uint32_t)s.host_pairs.size();
-    const uint32_t gen = bb::to_monty(bb::GEN);
+    uint32_t alp_len = 0;  // the alpha table: as long as the largest class counter (total when there is one class)
+    for (const Class& c : cls) alp_len = std::max(alp_len, c.cnt);
     hipStream_t st = s.stream;
 
     // ---- arena of this shape ----
@@ -586,14 +624,24 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         for (size_t r = 0; r < n_rounds; r++) {
             QTree t{};
             t.n_mats = (uint32_t)rounds[r]->lde.size();
-            for (uint32_t m = 0; m < t.n_mats; m++) { t.mat[m] = rounds[r]->lde[m]; t.width[m] = t.stride[m] = (uint32_t)rounds[r]->widths[m]; }
+            // a round's tree is as deep as its own tallest LDE: opened at index >> (log_big - that), a shorter matrix's row that shifted again
+            const uint32_t round_log_big = rounds[r]->log_big;
+            for (uint32_t m = 0; m < t.n_mats; m++) {
+                t.mat[m] = rounds[r]->lde[m]; t.width[m] = t.stride[m] = (uint32_t)rounds[r]->widths[m];
+                t.mshift[m] = rounds[r]->log_h - rounds[r]->mat_log_h(m);
+            }
             if (s.hiding) {  // stark_hiding.c:70-73: the values of every matrix, then one salt per matrix
                 for (uint32_t m = 0; m < t.n_mats; m++) { t.mat[t.n_mats + m] = rounds[r]->salts[m]; t.width[t.n_mats + m] = t.stride[t.n_mats + m] = PCS_SALT; }
                 t.n_mats *= 2;
             }
-            t.layers = rounds[r]->tree->layers; t.log_height = log_big; t.shift = 0;
+            t.layers = rounds[r]->tree->layers; t.log_height = round_log_big; t.shift = log_big - round_log_big;
             c->trees.push_back(t);
         }
+        // the reduced-opening vectors of the shorter classes: 2^log_big_c extension elements each, rolled in while folding
+        s.class_ro.assign(MAX_LOG_DOMAIN + 1, nullptr);
+        for (uint32_t lh = 0; lh < log_h; lh++)
+            if (cls[lh].cnt && (rc = c->alloc(&s.class_ro[lh], (size_t)4 << (lh + s.fp.log_blowup)))) return rc;
+
         c->lay.root_t = c->lay.root_q = c->lay.opened = 0;  // the staging buffer starts with the opened values
         c->lay.froots = 4 * total;
         if ((rc = c->layout("pcs open", PCS_STATE_WORDS + 1))) return rc;  // + the random streams' shortage flag
@@ -609,7 +657,8 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     size_t part_words = 0;
     for (size_t m = 0; m < mats.size(); m++) {
         const uint32_t w = mats[m].w, tiles = (w + 63) / 64, rps = w < 64 ? 64 / w : 1;
-        nblk[m] = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(1024, 4096 / tiles), h / std::min<uint32_t>(h, 32 * rps)));
+        const uint32_t mh = 1u << mats[m].log_h;
+        nblk[m] = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(1024, 4096 / tiles), mh / std::min<uint32_t>(mh, 32 * rps)));
         part_off[m] = part_words;
         part_words += (size_t)nblk[m] * mats[m].np * w * 4;
     }
@@ -617,9 +666,9 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     if ((rc = s.xd.reserve((size_t)n_points * h * 4))) return rc;
     if ((rc = s.partials.reserve(part_words))) return rc;
     if ((rc = s.sums.reserve((size_t)total * 4))) return rc;
-    if ((rc = s.alp.reserve((size_t)total * 4))) return rc;
+    if ((rc = s.alp.reserve((size_t)alp_len * 4))) return rc;
     if ((rc = s.ay.reserve((size_t)n_pairs * 8))) return rc;
-    if ((rc = s.pairs.reserve((size_t)n_pairs * 4))) return rc;
+    if ((rc = s.pairs.reserve((size_t)n_pairs * (sizeof(PcsPair) / 4)))) return rc;
 
     // ---- upload: the challenger's state, the pairs, the trees of this open's commitments ----
     chal_to_dev(*chal, &s.host_ds);
@@ -657,7 +706,7 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         const Mat& mt = mats[m];
         if (!mt.np) continue;
         PcsBaryArgs ba{};
-        ba.lde = mt.lde; ba.xd = s.xd.p; ba.partials = s.partials.p + part_off[m]; ba.w = mt.w; ba.h = h;
+        ba.lde = mt.lde; ba.xd = s.xd.p; ba.partials = s.partials.p + part_off[m]; ba.w = mt.w; ba.h = 1u << mt.log_h; ba.xstride = h;
         for (uint32_t p = 0; p < mt.np; p++) ba.pidx[p] = mt.pidx[p];
         const dim3 grid(nblk[m], (mt.w + 63) / 64), blk(256);
         switch (mt.np) {
@@ -676,28 +725,35 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         PcsOpenArgs oa{};
         oa.ts = ts; oa.sums = s.sums.p; oa.pairs = reinterpret_cast<const PcsPair*>(s.pairs.p); oa.alp = s.alp.p;
         for (uint32_t k = 0; k < n_points; k++) oa.z[k] = zs[k];
-        oa.n_points = n_points; oa.n_pairs = n_pairs; oa.total = total; oa.log_h = log_h;
-        oa.sn = bb::pow(gen, h);
-        oa.denom = bb::inv(bb::mul(bb::to_monty(h), oa.sn));
+        oa.n_points = n_points; oa.n_pairs = n_pairs; oa.total = alp_len; oa.log_h = log_h;
+        oa.sn = cls[log_h].sn; oa.denom = cls[log_h].denom;
         hipLaunchKernelGGL(pcs_ts_open_kernel, dim3(1), dim3(64), 0, st, oa);
         P3_HIP(hipGetLastError());
         hipLaunchKernelGGL(pcs_y_kernel, dim3(n_pairs), dim3(256), 0, st, oa.pairs, n_pairs, s.alp.p, core.pstage + L.opened, s.ay.p);
         P3_HIP(hipGetLastError());
     }
     // ---- reduced openings -> FRI input: every LDE word read once ----
+    // one vector per class: the tallest class's is the FRI input, a shorter class's waits in the arena for its fold.  The first
+    // big_c rows of the tallest domain are the class's own domain (bit-reversed order), so it reads the first big_c entries of d's rows.
+    std::vector<const uint32_t*> rollin(core.n_rounds, nullptr);
     {
-        bool first = true;
         for (const Mat& mt : mats) {
             if (!mt.np) continue;
+            Class& cl = cls[mt.log_h];
+            const uint32_t mbig = 1u << (mt.log_h + s.fp.log_blowup);
             PcsReducedArgs ra{};
-            ra.lde = mt.lde; ra.alp = s.alp.p; ra.d = s.d.p; ra.ay = s.ay.p; ra.ro = core.fri_vec + core.fri_vec_off[0];
-            ra.w = mt.w; ra.big = big; ra.np = mt.np; ra.first = first ? 1u : 0u;
+            ra.lde = mt.lde; ra.alp = s.alp.p; ra.d = s.d.p; ra.ay = s.ay.p;
+            ra.ro = mt.log_h == log_h ? core.fri_vec + core.fri_vec_off[0] : s.class_ro[mt.log_h];
+            ra.w = mt.w; ra.big = mbig; ra.dstride = big; ra.np = mt.np; ra.first = cl.started ? 0u : 1u;
             for (uint32_t p = 0; p < mt.np; p++) { ra.pidx[p] = mt.pidx[p]; ra.pair[p] = mt.pair[p]; }
-            if (mt.w <= 16) hipLaunchKernelGGL(pcs_reduced_narrow_kernel, dim3((big + 255) / 256), dim3(256), 0, st, ra);
-            else hipLaunchKernelGGL(pcs_reduced_tile_kernel, dim3((big + PCS_TILE - 1) / PCS_TILE), dim3(64), 0, st, ra);
+            if (mt.w <= 16) hipLaunchKernelGGL(pcs_reduced_narrow_kernel, dim3((mbig + 255) / 256), dim3(256), 0, st, ra);
+            else hipLaunchKernelGGL(pcs_reduced_tile_kernel, dim3((mbig + PCS_TILE - 1) / PCS_TILE), dim3(64), 0, st, ra);
             P3_HIP(hipGetLastError());
-            first = false;
+            cl.started = true;
         }
+        // the fold of round r leaves 2^(log_big - 1 - r) elements: the class of that length goes in there
+        for (uint32_t lh = 0; lh < log_h; lh++)
+            if (cls[lh].cnt) rollin[log_h - 1 - lh] = s.class_ro[lh];
     }
     // ---- FRI commit phase, final polynomial, grind, queries: ProverCore, as a fib proof runs them ----
     // hiding: the salts of every layer first, (big >> (r + 1)) x 4 draws of the `fri` stream in round order (stark_hiding.c:241); the
@@ -707,7 +763,7 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
         P3_HIP(hipMemsetAsync(err, 0, 4, st));
         if ((rc = s.fill(cx, s.rngs + 1, core.fri_salts, core.fri_salt_words, err))) return rc;
     }
-    if ((rc = core.fri_rounds(cx, ts, core.n_rounds))) return rc;
+    if ((rc = core.fri_rounds(cx, ts, core.n_rounds, rollin.data()))) return rc;
     if ((rc = core.fri_final(cx, ts))) return rc;
     if ((rc = core.grind_start(ts))) return rc;
     const uint32_t nq = s.fp.num_queries;

@@ -97,7 +97,8 @@ int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriPara
 
 // ---- TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over caller-supplied matrices (pcs.hip.inc), non-hiding ----
 // Every matrix of one open / verify has the same height h = 2^log_h (what p3_uni_stark produces for any AIR: trace, preprocessed
-// trace and quotient chunks); mixed heights are refused by name.  Capacities, refused by name when exceeded:
+// trace and quotient chunks); mixed heights are refused by name — unless the object was created for them (Pcs::init's mixed_heights;
+// verify: pcs_verify_mixed), see pcs.hip.inc.  Capacities, refused by name when exceeded:
 constexpr size_t PCS_MAX_MATS = 8;      // matrices per commitment (QTREE_MAX_MATS)
 constexpr size_t PCS_MAX_ROUNDS = 4;    // commitments per open
 constexpr size_t PCS_MAX_POINTS = 4;    // distinct opening points per open
@@ -116,6 +117,8 @@ struct PcsData {
     std::vector<uint32_t*> lde;
     std::vector<size_t> widths;
     uint32_t log_h = 0, log_big = 0;
+    std::vector<uint32_t> log_hs;  // per matrix, of a commitment of mixed heights (log_h is then the tallest); empty: all log_h
+    uint32_t mat_log_h(size_t m) const { return log_hs.empty() ? log_h : log_hs[m]; }
     int hash = 0, device = -1;
     Tree* tree = nullptr;
     bool hiding = false;
@@ -132,7 +135,9 @@ class Pcs {
     Pcs();
     ~Pcs();
     Pcs(const Pcs&) = delete;
-    int init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile);
+    // mixed_heights: commit and open take matrices of any power-of-two heights >= 2 (one class per height: pcs.hip.inc); false: they
+    // refuse them by name, as every object did before the option existed
+    int init(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile, bool mixed_heights = false);
     // HidingFriPcs::new(dft, mmcs, fri_params, num_random_codewords, SmallRng::seed_from_u64(pcs_seed)) over a MerkleTreeHidingMmcs
     // seeded with mmcs_seed (the FRI MMCS a clone of it): the object owns the three streams, which advance over its lifetime
     int init_hiding(const FriParams& fp, hipStream_t stream, bool own_stream, int hash, int profile, uint32_t num_random_codewords,
@@ -174,6 +179,11 @@ int challenger_import(const uint32_t* words, Challenger* c);
 int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
                size_t len, Challenger* chal, std::string* why);
+// the same for matrices of mixed heights: log_heights one per matrix, round -> matrix, in place of log_h.  With all heights equal it
+// returns what pcs_verify returns for the same bytes (the same code; of several refused arguments it may name another one).
+int pcs_verify_mixed(int hash, const FriParams& fp, const unsigned* log_heights, const uint32_t* roots, const size_t* mats_per_round,
+                     const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
+                     const uint8_t* proof, size_t len, Challenger* chal, std::string* why);
 // HidingFriPcs::verify: log_h the CALLER's log height (the committed polynomials have degree < 2^(log_h + 1)), widths the committed
 // widths, every input opening and FRI layer opening with a salt of PCS_SALT words; at most PCS_HIDING_MAX_MATS matrices a round
 int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round,

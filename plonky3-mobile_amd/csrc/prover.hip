@@ -273,6 +273,24 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(TwoLevelTable inv_roots /
     st_ext(out + 4 * (size_t)i, bb::add(s, d));
 }
 
+// The same fold with a shorter class of a mixed-height open rolled in (pcs.hip.inc): out[i] = fold(in)[i] + beta^2 ro[i] in the fold's own
+// pass — the folded element never goes to HBM and back for the addition.  beta^2 = (2 half_beta)^2: DevState keeps its layout.
+__global__ void __launch_bounds__(256) fri_fold_rollin_kernel(TwoLevelTable inv_roots /* w_len^-e */, const uint32_t* in,
+                                                              const uint32_t* __restrict__ ro, uint32_t* out, uint32_t half,
+                                                              uint32_t log_half, const DevState* __restrict__ ds, uint32_t round,
+                                                              uint32_t one_half) {
+    if (gridDim.x <= 512u) P3_LATENCY_BOUND_KERNEL();
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= half) return;
+    const Ext half_beta = ds->half_beta[round];
+    const Ext beta2 = bb::sqr(bb::add(half_beta, half_beta));
+    Ext lo = ld_ext(in + 8 * (size_t)i), hi = ld_ext(in + 8 * (size_t)i + 4), e = ld_ext(ro + 4 * (size_t)i);
+    uint32_t p = tl(inv_roots, brev(i, log_half));
+    Ext s = bb::scale(bb::add(lo, hi), one_half);
+    Ext d = bb::mul(bb::scale(half_beta, p), bb::sub(lo, hi));
+    st_ext(out + 4 * (size_t)i, bb::add(bb::add(s, d), bb::mul(beta2, e)));
+}
+
 // GrindingChallenger::grind: smallest canonical w with sample_bits(bits) == 0 after observe(w).  The sponge state
 // with the pending inputs comes from the device transcript; blocks whose whole range lies above a witness already
 // found return at once (the smallest one wins through atomicMin, as in a serial search).
@@ -341,6 +359,8 @@ struct QTree {
     uint32_t n_mats;  // values first, then their salts (if any), as listed
     const uint32_t* layers;
     uint32_t log_height, shift, slot_off;  // index used = query_index >> shift; slot_off in words
+    uint32_t mshift[QTREE_MAX_MATS];       // matrix m's row = that index >> mshift[m]: a shorter matrix injected into the tree (mixed
+                                           // heights, pcs.hip.inc); zero for every other user
 };
 __global__ void query_gather_kernel(const QTree* trees, const uint32_t* indices, uint32_t slot_words, uint32_t* out) {
     P3_LATENCY_BOUND_KERNEL();
@@ -350,7 +370,8 @@ __global__ void query_gather_kernel(const QTree* trees, const uint32_t* indices,
     uint32_t* dst = out + (size_t)blockIdx.x * slot_words + t.slot_off;
     uint32_t off = 0;
     for (uint32_t m = 0; m < t.n_mats; m++) {
-        for (uint32_t c = threadIdx.x; c < t.width[m]; c += blockDim.x) dst[off + c] = t.mat[m][index * t.stride[m] + c];
+        const uint64_t row = index >> t.mshift[m];  // index < 2^log_height: the row stays inside a matrix of 2^(log_height - mshift) rows
+        for (uint32_t c = threadIdx.x; c < t.width[m]; c += blockDim.x) dst[off + c] = t.mat[m][row * t.stride[m] + c];
         off += t.width[m];
     }
     uint64_t base = 0, len = 1ull << t.log_height;
@@ -797,8 +818,9 @@ struct ProverCore {
         return OK;
     }
     // FRI commit phase, rounds [0, r_end): commit the layer (ExtensionMmcs: rows of two ext elements, flattened), observe its root and
-    // sample beta, fold
-    int fri_rounds(Context& cx, const TsArgs& ts, uint32_t r_end) {
+    // sample beta, fold.  rollin (null for everyone but a mixed-height open): per round the vector of 2^(log_big - 1 - r) elements that
+    // the fold of round r adds as beta^2 ro, or null; a round without one runs fri_fold_kernel as ever
+    int fri_rounds(Context& cx, const TsArgs& ts, uint32_t r_end, const uint32_t* const* rollin = nullptr) {
         const uint32_t one_half = bb::inv(bb::to_monty(2));
         const size_t row = 8;
         int rc;
@@ -811,8 +833,12 @@ struct ProverCore {
             P3_HIP(hipGetLastError());
             TwoLevelTable inv_roots;
             if ((rc = cx.get_root_table(stream, log_half + 1, true, &inv_roots))) return rc;
-            hipLaunchKernelGGL(fri_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, stream, inv_roots, vec, fri_vec + fri_vec_off[r + 1],
-                               half, log_half, ts.ds, r, one_half);
+            if (rollin && rollin[r])
+                hipLaunchKernelGGL(fri_fold_rollin_kernel, dim3((half + 255) / 256), dim3(256), 0, stream, inv_roots, vec, rollin[r],
+                                   fri_vec + fri_vec_off[r + 1], half, log_half, ts.ds, r, one_half);
+            else
+                hipLaunchKernelGGL(fri_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, stream, inv_roots, vec, fri_vec + fri_vec_off[r + 1],
+                                   half, log_half, ts.ds, r, one_half);
             P3_HIP(hipGetLastError());
         }
         return OK;

@@ -122,8 +122,9 @@ struct FriCheck {
         return 0;
     }
     // one query's FRI walk: per round the sibling, its salt, the path to the round's root and the fold; then the final polynomial at
-    // the point the walk ends on against the folded value
-    int query(Reader& rd, size_t index, Ext folded, uint32_t* path) {
+    // the point the walk ends on against the folded value.  rolls (mixed heights: pcs_verify_mixed; empty for everyone else): the
+    // reduced opening ro_c of every shorter class by its log_big_c, added as beta^2 ro_c right after the fold that reaches 2^log_big_c
+    int query(Reader& rd, size_t index, Ext folded, uint32_t* path, const std::vector<std::pair<uint32_t, Ext>>& rolls = {}) {
         if (rd.u32() != n_rounds) return reject(why, 12, "query shape");
         size_t idx = index;
         for (uint32_t r = 0; r < n_rounds; r++) {
@@ -144,6 +145,8 @@ struct FriCheck {
             const uint32_t s = bb::pow(bb::two_adic_generator(lfh + 1), rev_bits_host(pair, lfh));
             Ext num = bb::mul(bb::sub(betas[r], bb::ext_from_base(s)), bb::sub(ev[1], ev[0]));
             folded = bb::add(ev[0], bb::scale(num, bb::inv(bb::sub(bb::neg(s), s))));
+            for (const auto& rl : rolls)
+                if (rl.first == lfh) folded = bb::add(folded, bb::mul(bb::sqr(betas[r]), rl.second));
             idx = pair;
         }
         const uint32_t lfinal = fp.log_blowup + fp.log_final_poly_len;
@@ -394,11 +397,28 @@ int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint
 // leaf row m0 || s0 || m1 || s1 ... (stark_hiding.c:300-322), each commit-phase opening carries its salt (FriCheck).
 static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                           size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
-                          size_t len, Challenger* chal, std::string* why, uint32_t salt_words, size_t max_mats) {
+                          size_t len, Challenger* chal, std::string* why, uint32_t salt_words, size_t max_mats,
+                          const unsigned* log_heights = nullptr) {
     auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
     if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
     if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
     if (chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
+    // mixed heights (log_heights: one per matrix, round -> matrix): log_h is the tallest matrix's.  lh[] is filled either way, and
+    // everything below reads the heights from it: with all heights equal the two entries run the same checks on the same numbers.
+    std::vector<uint32_t> lh;
+    if (log_heights) {
+        if (n_rounds == 0) return bad("pcs verify: zero rounds");
+        if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
+        size_t nm = 0;
+        for (size_t r = 0; r < n_rounds; r++) {
+            if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
+            if (mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
+            nm += mats_per_round[r];
+        }
+        lh.assign(log_heights, log_heights + nm);
+        log_h = *std::max_element(lh.begin(), lh.end());
+        if (*std::min_element(lh.begin(), lh.end()) < 1) return bad("pcs verify: LDE height outside [2^2, 2^27]");
+    }
     if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
     if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
     if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
@@ -411,6 +431,9 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
     std::vector<uint32_t> mat_pairs;           // per matrix: how many pairs
     Ext zs[PCS_MAX_POINTS];
     size_t n_points = 0, total = 0, mi = 0, pi = 0, row_max = 0;
+    if (!log_heights) for (size_t r = 0; r < n_rounds; r++) lh.insert(lh.end(), std::min(mats_per_round[r], max_mats), log_h);
+    bool class_has_point[bb::TWO_ADICITY + 1] = {false};  // by log_big_c
+    uint32_t round_log_big[PCS_MAX_ROUNDS] = {0};         // the round's tallest LDE: its tree's depth
     for (size_t r = 0; r < n_rounds; r++) {
         if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
         if (mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
@@ -419,6 +442,10 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
             const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
             if (widths[mi] < 1 || widths[mi] > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
             if (points_per_mat[mi] > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
+            if (lh[mi] < fp.log_final_poly_len)
+                return bad(who + " has height 2^" + std::to_string(lh[mi]) + ", below the final polynomial's 2^" + std::to_string(fp.log_final_poly_len));
+            round_log_big[r] = std::max(round_log_big[r], lh[mi] + fp.log_blowup);
+            if (points_per_mat[mi]) class_has_point[lh[mi] + fp.log_blowup] = true;
             row += widths[mi];
             mat_pairs.push_back((uint32_t)points_per_mat[mi]);
             for (size_t p = 0; p < points_per_mat[mi]; p++, pi++) {
@@ -440,6 +467,8 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
         row_max = std::max(row_max, row);
     }
     if (total == 0) return bad("pcs verify: no opening point");
+    if (!class_has_point[log_big])
+        return bad("pcs verify: no matrix of the tallest height 2^" + std::to_string(log_h) + " has an opening point: the FRI input would be missing");
     for (size_t i = 0; i < 4 * total; i++) if (opened[i] >= bb::P) return bad("pcs verify: opened value word " + std::to_string(i) + " is not a canonical field element");
     Challenger& ch = *chal;
     std::vector<Ext> ov(total), alp(total);
@@ -457,7 +486,7 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
         for (size_t r = 0; r < n_rounds; r++) {
             qbytes += 4;
             for (size_t m = 0; m < mats_per_round[r]; m++, mi++) qbytes += 4 + 4 * widths[mi] + (salt_words ? 4 + 4 * (size_t)salt_words : 0);
-            qbytes += 4 + 32 * (size_t)log_big;
+            qbytes += 4 + 32 * (size_t)round_log_big[r];
         }
         qbytes += 4;
         for (uint32_t r = 0; r < fri.n_rounds; r++) qbytes += 16 + (salt_words ? 4 + 4 * (size_t)salt_words : 0) + 4 + 32 * (size_t)(log_big - 1 - r);
@@ -470,15 +499,26 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
     std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(row_max), leaf(row_max + PCS_MAX_MATS * salt_words), salts(PCS_MAX_MATS * salt_words);
     std::vector<size_t> hh(2 * PCS_MAX_MATS, (size_t)1 << log_big), lw(2 * PCS_MAX_MATS);
     const uint32_t gen = bb::to_monty(bb::GEN);
+    // one reduced opening and one alpha counter per class (by log_big_c); the tallest class is the walk's start, the others roll in
+    Ext ro_c[bb::TWO_ADICITY + 1];
+    uint32_t xi_c[bb::TWO_ADICITY + 1];
+    size_t cnt_c[bb::TWO_ADICITY + 1];
+    std::vector<std::pair<uint32_t, Ext>> rolls;
     for (uint32_t q = 0; q < fp.num_queries; q++) {
         const size_t index = ch.sample_bits(log_big);
-        const uint32_t xi = bb::mul(gen, bb::pow(bb::two_adic_generator(log_big), rev_bits_host(index, log_big)));
+        for (uint32_t lb = 0; lb <= log_big; lb++) {
+            if (!class_has_point[lb]) continue;
+            ro_c[lb] = bb::ext_zero(); cnt_c[lb] = 0;
+            xi_c[lb] = bb::mul(gen, bb::pow(bb::two_adic_generator(lb), rev_bits_host(index >> (log_big - lb), lb)));
+        }
         if (rd.u32() != n_rounds) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
-        Ext ro = bb::ext_zero();
         size_t k = 0, pair = 0;
         mi = 0;
         for (size_t r = 0; r < n_rounds; r++) {
             const size_t nm = mats_per_round[r], m0 = mi;
+            const uint32_t log_big_r = round_log_big[r];  // this round's tree
+            const size_t index_r = index >> (log_big - log_big_r);
+            for (size_t m = 0; m < nm; m++) hh[salt_words ? 2 * m : m] = hh[salt_words ? 2 * m + 1 : m] = (size_t)1 << (lh[m0 + m] + fp.log_blowup);
             if (rd.u32() != nm) return reject(why, 12, "query shape");
             size_t off = 0;
             for (size_t m = 0; m < nm; m++) {
@@ -490,8 +530,8 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
                 if (rd.u32() != salt_words) return reject(why, 12, "query shape");
                 rd.felts(salts.data() + m * salt_words, salt_words);
             }
-            if (rd.u32() != log_big) return reject(why, 12, "query shape");
-            rd.digests(hash, path.data(), log_big);
+            if (rd.u32() != log_big_r) return reject(why, 12, "query shape");
+            rd.digests(hash, path.data(), log_big_r);
             if (rd.bad) return reject(why, 9, "truncated proof");
             if (salt_words) {  // the salts as width-4 matrices, each behind its matrix
                 size_t p = 0;
@@ -502,21 +542,24 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
                     memcpy(leaf.data() + p, salts.data() + m * salt_words, (size_t)salt_words * 4); p += salt_words;
                     lw[2 * m] = w; lw[2 * m + 1] = salt_words;
                 }
-                if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), 2 * nm, index, leaf.data(), path.data(), log_big, nullptr, false) != 0)
+                if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), 2 * nm, index_r, leaf.data(), path.data(), log_big_r, nullptr, false) != 0)
                     return reject(why, 13, "input opening");
-            } else if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index, row.data(), path.data(), log_big, nullptr, false) != 0)
+            } else if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index_r, row.data(), path.data(), log_big_r, nullptr, false) != 0)
                 return reject(why, 13, "input opening");
             off = 0;
             for (size_t m = 0; m < nm; m++, mi++) {
+                const uint32_t lb = lh[mi] + fp.log_blowup;
                 for (uint32_t p = 0; p < mat_pairs[mi]; p++, pair++) {
-                    const Ext dz = bb::inv(bb::sub(pairs[pair].z, bb::ext_from_base(xi)));
+                    const Ext dz = bb::inv(bb::sub(pairs[pair].z, bb::ext_from_base(xi_c[lb])));
                     for (size_t c = 0; c < widths[mi]; c++, k++)
-                        ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(ov[k], bb::ext_from_base(row[off + c])), dz)));
+                        ro_c[lb] = bb::add(ro_c[lb], bb::mul(alp[cnt_c[lb]++], bb::mul(bb::sub(ov[k], bb::ext_from_base(row[off + c])), dz)));
                 }
                 off += widths[mi];
             }
         }
-        if (int rc = fri.query(rd, index, ro, path.data())) return rc;
+        rolls.clear();
+        for (uint32_t lb = 0; lb < log_big; lb++) if (class_has_point[lb]) rolls.emplace_back(lb, ro_c[lb]);
+        if (int rc = fri.query(rd, index, ro_c[log_big], path.data(), rolls)) return rc;
     }
     if (why) why->clear();
     return 0;
@@ -527,6 +570,13 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
                size_t len, Challenger* chal, std::string* why) {
     return pcs_verify_any(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why, 0,
                           PCS_MAX_MATS);
+}
+int pcs_verify_mixed(int hash, const FriParams& fp, const unsigned* log_heights, const uint32_t* roots, const size_t* mats_per_round,
+                     const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
+                     const uint8_t* proof, size_t len, Challenger* chal, std::string* why) {
+    if (!log_heights) { if (why) *why = "pcs verify: null argument"; return (int)ERR_BAD_ARG; }
+    return pcs_verify_any(hash, fp, 0, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why, 0,
+                          PCS_MAX_MATS, log_heights);
 }
 int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                       size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,

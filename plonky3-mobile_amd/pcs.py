@@ -1,8 +1,9 @@
 """Host-side mirror of Plonky3's Pcs contract for TwoAdicFriPcs<BabyBear, GpuDft, MerkleTreeMmcs, ExtensionMmcs> over
 caller-supplied matrices (include/p3hip.h "TwoAdicFriPcs over CALLER-SUPPLIED matrices"), and of the challengers a caller
 drives between its calls; HidingFriPcs mirrors the hiding PCS the reference builds ("HidingFriPcs over CALLER-SUPPLIED matrices").
-Every matrix of one open / verify has the same height.  commit / open keep everything device-resident (one synchronisation each);
-verify is host code of the library."""
+Every matrix of one open / verify has the same height, unless the object was created with mixed_heights=True (include/p3hip.h
+p3hip_pcs_create_mixed; verify then takes a log height per matrix).  commit / open keep everything device-resident (one
+synchronisation each); verify is host code of the library."""
 import ctypes as C
 
 import numpy as np
@@ -120,14 +121,18 @@ def _flatten(rounds):
 class TwoAdicFriPcs:
     _hiding = False
 
-    def __init__(self, params=None, hash="poseidon2", profile="latency", own_stream=False):
+    def __init__(self, params=None, hash="poseidon2", profile="latency", own_stream=False, mixed_heights=False):
+        """mixed_heights: commit and open take matrices of any power-of-two heights (p3hip_pcs_create_mixed); False: they refuse
+        them by name.  A same-height open is the same either way."""
         import torch
         self.params = params or FriParameters()
         self.hash, self._kind = hash, _hash_kind(hash)
+        self.mixed_heights = bool(mixed_heights)
         self._h = C.c_void_p()
         torch.cuda.current_stream()  # make sure a context exists
-        _lib.check(_lib.lib().p3hip_pcs_create(profile_kind(profile), self._kind, C.cast(self.params._c(), C.c_void_p),
-                                               None if own_stream else _stream_ptr(), 1 if own_stream else 0, C.byref(self._h)))
+        create = _lib.lib().p3hip_pcs_create_mixed if mixed_heights else _lib.lib().p3hip_pcs_create
+        _lib.check(create(profile_kind(profile), self._kind, C.cast(self.params._c(), C.c_void_p),
+                          None if own_stream else _stream_ptr(), 1 if own_stream else 0, C.byref(self._h)))
 
     def commit(self, evaluations):
         """Pcs::commit.  evaluations: [(matrix, domain shift)] — the matrix a (h, w) torch device tensor (read in place) or numpy
@@ -156,7 +161,7 @@ class TwoAdicFriPcs:
         p, hh, ww = C.c_void_p(), C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib().p3hip_pcs_lde_dev(data._h, i, C.byref(p), C.byref(hh), C.byref(ww)))
         m = 1 << log_size
-        if m < data.dims[i][0] or m > hh.value:
+        if m < data.dims[i][0] or m > hh.value:  # hh: the matrix's own LDE height
             raise ValueError("get_evaluations_on_domain: 2^log_size must lie between the matrix height and the LDE height")
 
         class _View:  # the CUDA array interface: torch wraps the memory without copying; `owner` keeps the LDE alive
@@ -249,8 +254,17 @@ def verify(params, hash, rounds, log_h, opened, proof, challenger, hiding=False)
     """Pcs::verify on the host.  rounds = [((root, [width of matrix 0, ...]), [points of matrix 0, ...])]; opened as open returns
     it.  Returns None on accept; raises PcsRejected (code = the failed check) on a rejection and P3HipError(-1) for a refused
     argument.  The challenger is advanced as the verifier advances it.  hiding: HidingFriPcs::verify — log_h the caller's log
-    height, the widths the committed ones."""
+    height, the widths the committed ones.  log_h: an int (every matrix of that height: p3hip_pcs_verify), or per-matrix lists
+    [[log height of matrix 0, ...] per round] (mixed heights: p3hip_pcs_verify_mixed; not with hiding)."""
     L = _lib.lib()
+    mixed = not isinstance(log_h, (int, np.integer))
+    if mixed:
+        if hiding:
+            raise ValueError("verify: a hiding PCS takes one log height, not per-matrix lists")
+        lhs = [int(v) for r in log_h for v in r]
+        if [len(r) for r in log_h] != [len(ws) for (_, ws), _ in rounds]:
+            raise ValueError("verify: one log height per matrix")
+        log_h = (C.c_uint * max(len(lhs), 1))(*lhs)
     n = len(rounds)
     roots = np.concatenate([_words(r, 8) for (r, _), _ in rounds]) if n else np.zeros(8, np.uint32)
     mats = [len(ws) for (_, ws), _ in rounds]
@@ -262,7 +276,7 @@ def verify(params, hash, rounds, log_h, opened, proof, challenger, hiding=False)
     opened = _words(opened, 4 * sum(len(ps) * int(ws[i]) for (_, ws), mp in rounds for i, ps in enumerate(mp)))
     buf = (C.c_uint8 * max(len(proof), 1)).from_buffer_copy(bytes(proof) or b"\0")
     code = C.c_int()
-    fn = L.p3hip_pcs_verify_hiding if hiding else L.p3hip_pcs_verify
+    fn = L.p3hip_pcs_verify_hiding if hiding else L.p3hip_pcs_verify_mixed if mixed else L.p3hip_pcs_verify
     _lib.check(fn(
         _hash_kind(hash), C.cast(params._c(), C.c_void_p), log_h, roots.ctypes.data_as(C.c_void_p), (C.c_size_t * max(n, 1))(*mats), (C.c_size_t * max(len(widths), 1))(*widths), n, counts, points.ctypes.data_as(C.c_void_p),
         opened.ctypes.data_as(C.c_void_p), buf, len(proof), challenger._h, C.byref(code)))

@@ -10,6 +10,11 @@ device timestamps (events on the stream the PCS enqueues on), warm-up, repetitio
   python tools/pcs_bench.py --hiding               the device HidingFriPcs: commit / commit_quotient times, the copy yardstick of the two
                                                    streaming kernels, the hiding fib comparison (default profiles/pcs_hiding_open_bench.txt)
   python tools/pcs_bench.py --hiding --plain       the hiding commits only: the run to put under rocprofv3 --kernel-trace
+  python tools/pcs_bench.py --mixed                an open over MIXED heights (2^20 x 16 + 2^18 x 64 + 2^16 x 4, TwoAdicFriPcs(mixed_heights=
+                                                   True)) and a same-height 2^20 x 16 open in the same process; the copy yardsticks of the
+                                                   fold kernels (default profiles/pcs_mixed_open_bench.txt)
+  python tools/pcs_bench.py --mixed --plain        the opens only: the run to put under rocprofv3 --kernel-trace
+  python tools/pcs_bench.py --mixed --merge DIR    adds fri_fold_rollin_kernel beside fri_fold_kernel at the same length from DIR/**/*kernel_trace.csv
   python tools/pcs_bench.py --hiding --merge DIR   adds the device times of pcs_randomize_kernel / pcs_blind_kernel from DIR/**/*kernel_trace.csv
 
 Algorithmic bytes of the streaming kernels: reduced openings 4*big*w (every LDE word once), opened values 4*h*w (the low coset
@@ -152,6 +157,54 @@ def merge(prof_dir, out):
         out.append("%-14s   %-34s %10.1f us" % (name, "all kernels", tot))
 
 
+# ---- mixed heights ----
+MIXED = [(20, 16), (18, 64), (16, 4)]  # (log_h, width), one commitment, both points on every matrix
+FOLD_BYTES, ROLLIN_BYTES = 48, 64      # per output element: two inputs read and one output written, 16 bytes each; + ro read
+
+
+def run_mixed(p3, warmup, reps, plain, out):
+    import torch
+    rng = np.random.default_rng(1)
+    z = [((rng.integers(0, P, 4, dtype=np.uint64) << 32) % P).astype(np.uint32) for _ in range(2)]
+    pcs = p3.TwoAdicFriPcs(p3.FriParameters(*FRI), "poseidon2", mixed_heights=True)
+    for name, shape in (("mixed 2^20x16+2^18x64+2^16x4", MIXED), ("same  2^20x16", MIXED[:1])):
+        mats = [torch.randint(0, P, (1 << lh, w), dtype=torch.int32, device="cuda") for lh, w in shape]
+        if not plain:
+            out.append("%-30s commit (LDEs + one tree): %s" % (name, _fmt(_timed(lambda: pcs.commit([(m, None) for m in mats])[1].free(), warmup, reps))))
+        _, d = pcs.commit([(m, None) for m in mats])
+        arg = [(d, [[z[0], z[1]]] * len(mats))]
+        out.append("%-30s open: %s" % (name, _fmt(_timed(lambda: pcs.open(arg, p3.Challenger()), warmup, reps))))
+        d.free()
+    if not plain:
+        for lh, _ in MIXED[1:]:  # the folds that take a roll-in leave 2^(log_h + log_blowup) elements
+            half = 1 << (lh + FRI[0])
+            for what, per in (("fri_fold_kernel", FOLD_BYTES), ("fri_fold_rollin_kernel", ROLLIN_BYTES)):
+                out.append("fold to 2^%d elements: %-22s %10d bytes; a device-to-device copy of them runs at %.0f GB/s"
+                           % (lh + FRI[0], what, per * half, _copy_rate(per * half, warmup, reps)))
+    pcs.free()
+
+
+def merge_mixed(prof_dir, out):
+    """median device time of the two fold kernels at the lengths that take a roll-in, from a profiled --mixed --plain run (the plain
+    kernel's dispatches of that length come from the same-height opens of the same process)"""
+    files = glob.glob(os.path.join(prof_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        out.append("no kernel trace under %s" % prof_dir)
+        return
+    rows = list(csv.DictReader(open(files[0])))
+    grid = lambda r: int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)  # work-items of the launch: one per output element
+    for lh, _ in MIXED[1:]:
+        half = 1 << (lh + FRI[0])
+        for kernel, per in (("fri_fold_kernel", FOLD_BYTES), ("fri_fold_rollin_kernel", ROLLIN_BYTES)):
+            ns = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if kernel + "(" in r["Kernel_Name"].replace("p3::", "") and grid(r) == half]
+            if not ns:
+                out.append("fold to 2^%d elements: %-22s no dispatch of that length in the trace" % (lh + FRI[0], kernel))
+                continue
+            us = statistics.median(ns) / 1e3
+            out.append("fold to 2^%d elements: %-22s median %8.1f us of %d dispatches under rocprofv3 --kernel-trace; %d bytes -> %.0f GB/s"
+                       % (lh + FRI[0], kernel, us, len(ns), per * half, per * half / (us * 1e3)))
+
+
 # ---- HidingFriPcs ----
 HIDING_SHAPES = [(20, 2), (20, 64), (16, 2633)]  # (log_h, w) of a committed matrix
 NRC, CHUNKS, MAX_WQ = 4, 4, 2048
@@ -243,10 +296,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--hiding", action="store_true")
+    ap.add_argument("--mixed", action="store_true")
     ap.add_argument("-o", "--output")
     a = ap.parse_args()
-    a.output = a.output or os.path.join(ROOT, "profiles", "pcs_hiding_open_bench.txt" if a.hiding else "pcs_open_bench.txt")
+    a.output = a.output or os.path.join(ROOT, "profiles", "pcs_hiding_open_bench.txt" if a.hiding else "pcs_mixed_open_bench.txt" if a.mixed else "pcs_open_bench.txt")
     p3 = load_package()
+    if a.mixed:
+        out = ["# tools/pcs_bench.py --mixed: FRI parameters %s, Poseidon2 hashes, latency profile, 2 opening points on every matrix; device"
+               % (FRI,), "# timestamps, %d warm-up and %d timed repetitions per figure" % (a.warmup, a.reps)]
+        run_mixed(p3, a.warmup, a.reps, a.plain, out)
+        if a.merge:
+            merge_mixed(a.merge, out)
+        text = "\n".join(out) + "\n"
+        sys.stdout.write(text)
+        if not a.plain:
+            with open(a.output, "w") as f:
+                f.write(text)
+        return
     if a.hiding:
         out = ["# tools/pcs_bench.py --hiding: FRI parameters %s, %d random codewords, latency profile; device timestamps, %d warm-up and %d timed"
                % (FRI, NRC, a.warmup, a.reps), "# repetitions per figure"]
