@@ -516,8 +516,9 @@ int p3hip_pcs_verify(int hash, const p3hip_fri_params_t *params, unsigned log_h,
  * BatchOpening is opened at index >> (log_big - log_big_r), log_big_r the round's tallest LDE, which is its depth word and path length.
  * Refused by name before any launch or draw (P3HIP_ERR_BAD_ARG, challenger unchanged): no matrix of the tallest height has an opening
  * point (the FRI input would be missing); a matrix with log_h_m < log_final_poly_len; a point on the TALLEST LDE coset (it contains
- * every smaller one); the capacities above, with log_h the tallest log height.  Not covered: a hiding object (p3hip_pcs_create_hiding)
- * and the device batch verifier (p3hip_pcs_verifier_*) stay same-height. */
+ * every smaller one); the capacities above, with log_h the tallest log height.  Batches of mixed-height proofs of one shape are verified
+ * on the device by a verifier from p3hip_pcs_verifier_create_mixed.  Not covered: a hiding object (p3hip_pcs_create_hiding) stays
+ * same-height. */
 int p3hip_pcs_create_mixed(int profile, int hash, const p3hip_fri_params_t *params, void *stream, int own_stream, p3hip_pcs_t **out);
 /* Pcs::verify for mixed heights, host code: p3hip_pcs_verify with log_heights (one per matrix, round -> matrix) in place of log_h.  With
  * all heights equal it returns what p3hip_pcs_verify returns for the same bytes: the same return code and the same *reject_code.  (Of
@@ -626,6 +627,20 @@ int p3hip_pcs_verifier_verify_dev(p3hip_pcs_verifier_t *v, const uint8_t *d_proo
  * status_out[n]; synchronises.  Splits n > max_proofs into several rounds itself. */
 int p3hip_pcs_verifier_verify(p3hip_pcs_verifier_t *v, size_t n, const uint8_t *const *proofs, const size_t *lens, const uint32_t *roots,
                               const uint32_t *points, const uint32_t *opened, p3hip_challenger_t *const *challengers, uint32_t *status_out);
+/* MIXED HEIGHTS: the two entries above with log_heights (one log height per matrix, round -> matrix) in place of shape->log_h, which is
+ * ignored — p3hip_pcs_shape_t keeps its layout.  The proofs are those of a p3hip_pcs_create_mixed object; a member brings what a member
+ * of any shape brings (proof, n_rounds roots, n_slots points, the opened values in observation order, the state words) and is verified
+ * through p3hip_pcs_verifier_verify_dev / p3hip_pcs_verifier_verify; the reject-code contract above holds with p3hip_pcs_verify_mixed as
+ * H.  The gates and their messages are p3hip_pcs_verify_mixed's, in its order: the round and matrix counts first, a height below 2^1,
+ * the LDE height of the tallest matrix, a matrix below 2^log_final_poly_len, "no matrix of the tallest height ... has an opening point";
+ * widths, points per matrix, slots and the 8192 batched columns as above.  A point on the TALLEST LDE coset makes its member malformed.
+ * hiding = 1 is refused by name (P3HIP_ERR_BAD_ARG): no HidingFriPcs over mixed heights exists; the flag is there so that one needs no
+ * new entry.  With all heights equal both return what the same-height entries return: the same length, and a verifier that runs the
+ * same kernels.  No capacity beyond those of the same-height entries. */
+int p3hip_pcs_proof_len_mixed(int hash, int hiding, const p3hip_fri_params_t *params, const p3hip_pcs_shape_t *shape,
+                              const unsigned *log_heights, size_t *len_out);
+int p3hip_pcs_verifier_create_mixed(int hash, int hiding, const p3hip_fri_params_t *params, const p3hip_pcs_shape_t *shape,
+                                    const unsigned *log_heights, size_t max_proofs, p3hip_pcs_verifier_t **out);
 /* DIAGNOSTIC, not part of the stable ABI: 1 when the shape's reduced opening runs one wavefront per query, 0: one lane per query.  Which
  * form a shape gets is a tuning detail (today: 256 or more row words per query) and will move with measurements; the tests use this
  * entry to show that they run both forms.  Results never depend on the form. */

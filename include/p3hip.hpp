@@ -465,6 +465,20 @@ class PcsVerifier {
         check(p3hip_pcs_proof_len(hash, hiding ? 1 : 0, &c, &s, &proof_len_));
         check(p3hip_pcs_verifier_create(hash, hiding ? 1 : 0, &c, &s, max_proofs, &h_));
     }
+    // mixed heights: log_heights, one log height per matrix (round -> matrix), in place of log_h (p3hip_pcs_verifier_create_mixed);
+    // hiding is refused by the library
+    PcsVerifier(int hash, bool hiding, FriParameters fp, const std::vector<unsigned>& log_heights, const std::vector<size_t>& mats_per_round,
+                const std::vector<size_t>& widths, const std::vector<size_t>& points_per_mat, size_t n_slots, const std::vector<uint32_t>& slots,
+                size_t max_proofs)
+        : n_rounds_(mats_per_round.size()), n_slots_(n_slots) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        p3hip_pcs_shape_t s{0, mats_per_round.size(), mats_per_round.data(), widths.data(), points_per_mat.data(), n_slots, slots.data()};
+        if (widths.size() != points_per_mat.size()) throw Error(P3HIP_ERR_BAD_ARG, "PcsVerifier: one point count per matrix");
+        if (widths.size() != log_heights.size()) throw Error(P3HIP_ERR_BAD_ARG, "PcsVerifier: one log height per matrix");
+        for (size_t m = 0; m < widths.size(); m++) total_ += widths[m] * points_per_mat[m];
+        check(p3hip_pcs_proof_len_mixed(hash, hiding ? 1 : 0, &c, &s, log_heights.data(), &proof_len_));
+        check(p3hip_pcs_verifier_create_mixed(hash, hiding ? 1 : 0, &c, &s, log_heights.data(), max_proofs, &h_));
+    }
     PcsVerifier(const PcsVerifier&) = delete;
     PcsVerifier& operator=(const PcsVerifier&) = delete;
     ~PcsVerifier() { p3hip_pcs_verifier_destroy(h_); }

@@ -203,6 +203,23 @@ extern "C" {
         max_proofs: usize,
         out: *mut *mut p3hip_pcs_verifier_t,
     ) -> i32;
+    fn p3hip_pcs_proof_len_mixed(
+        hash: i32,
+        hiding: i32,
+        params: *const p3hip_fri_params_t,
+        shape: *const p3hip_pcs_shape_t,
+        log_heights: *const u32,
+        len_out: *mut usize,
+    ) -> i32;
+    fn p3hip_pcs_verifier_create_mixed(
+        hash: i32,
+        hiding: i32,
+        params: *const p3hip_fri_params_t,
+        shape: *const p3hip_pcs_shape_t,
+        log_heights: *const u32,
+        max_proofs: usize,
+        out: *mut *mut p3hip_pcs_verifier_t,
+    ) -> i32;
     fn p3hip_pcs_verifier_verify(
         v: *mut p3hip_pcs_verifier_t,
         n: usize,
@@ -508,6 +525,35 @@ pub struct HipPcsVerifier {
 }
 impl HipPcsVerifier {
     pub fn new(pcs: &HipPcs, log_h: u32, widths: &[Vec<usize>], slots: &[Vec<Vec<u32>>], n_slots: usize, max_proofs: usize) -> Result<Self, String> {
+        Self::create(pcs, log_h, None, widths, slots, n_slots, max_proofs)
+    }
+
+    /// The same for matrices of MIXED heights (p3hip_pcs_verifier_create_mixed): log_heights holds one log height per matrix, laid out
+    /// as widths.  Members are verified through verify_many as those of any other shape.  A hiding PCS is refused by the library.
+    pub fn new_mixed(
+        pcs: &HipPcs,
+        log_heights: &[Vec<u32>],
+        widths: &[Vec<usize>],
+        slots: &[Vec<Vec<u32>>],
+        n_slots: usize,
+        max_proofs: usize,
+    ) -> Result<Self, String> {
+        if log_heights.len() != widths.len() || log_heights.iter().zip(widths.iter()).any(|(l, w)| l.len() != w.len()) {
+            return Err("new_mixed: one log height per matrix".into());
+        }
+        let flat_h: Vec<u32> = log_heights.iter().flatten().copied().collect();
+        Self::create(pcs, 0, Some(&flat_h), widths, slots, n_slots, max_proofs)
+    }
+
+    fn create(
+        pcs: &HipPcs,
+        log_h: u32,
+        log_heights: Option<&[u32]>,
+        widths: &[Vec<usize>],
+        slots: &[Vec<Vec<u32>>],
+        n_slots: usize,
+        max_proofs: usize,
+    ) -> Result<Self, String> {
         let mats: Vec<usize> = widths.iter().map(|w| w.len()).collect();
         let flat_w: Vec<usize> = widths.iter().flatten().copied().collect();
         let counts: Vec<usize> = slots.iter().flatten().map(|s| s.len()).collect();
@@ -524,9 +570,19 @@ impl HipPcsVerifier {
         };
         let hiding = (pcs.num_random_codewords > 0) as i32;
         let (mut h, mut proof_len) = (core::ptr::null_mut(), 0usize);
-        let rc = unsafe { p3hip_pcs_proof_len(pcs.hash, hiding, &pcs.params, &shape, &mut proof_len) };
+        let rc = unsafe {
+            match log_heights {
+                Some(lh) => p3hip_pcs_proof_len_mixed(pcs.hash, hiding, &pcs.params, &shape, lh.as_ptr(), &mut proof_len),
+                None => p3hip_pcs_proof_len(pcs.hash, hiding, &pcs.params, &shape, &mut proof_len),
+            }
+        };
         if rc != 0 { return Err(last_error(rc)); }
-        let rc = unsafe { p3hip_pcs_verifier_create(pcs.hash, hiding, &pcs.params, &shape, max_proofs, &mut h) };
+        let rc = unsafe {
+            match log_heights {
+                Some(lh) => p3hip_pcs_verifier_create_mixed(pcs.hash, hiding, &pcs.params, &shape, lh.as_ptr(), max_proofs, &mut h),
+                None => p3hip_pcs_verifier_create(pcs.hash, hiding, &pcs.params, &shape, max_proofs, &mut h),
+            }
+        };
         if rc != 0 { return Err(last_error(rc)); }
         Ok(Self { h, proof_len, n_rounds: mats.len(), n_slots, total })
     }

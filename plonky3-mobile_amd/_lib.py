@@ -154,6 +154,9 @@ _SIGS = {
     "p3hip_challenger_import": (C.c_int, [C.c_void_p, C.c_void_p]),
     "p3hip_pcs_proof_len": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
     "p3hip_pcs_verifier_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "p3hip_pcs_proof_len_mixed": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
+    "p3hip_pcs_verifier_create_mixed": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint), C.c_size_t,
+                                                  C.POINTER(C.c_void_p)]),
     "p3hip_pcs_verifier_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3hip_pcs_verifier_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,

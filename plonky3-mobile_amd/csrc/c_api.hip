@@ -1403,7 +1403,15 @@ struct p3hip_pcs_verifier {
 static_assert(P3HIP_CHALLENGER_STATE_WORDS == CHALLENGER_STATE_WORDS, "include/p3hip.h and prover.h agree on the state's size");
 static int pcs_shape_of(const p3hip_pcs_shape_t* s, PcsShape* out, const char* who) {
     if (!s) return fail(ERR_BAD_ARG, std::string(who) + ": null argument");
-    *out = PcsShape{s->log_h, s->n_rounds, s->mats_per_round, s->widths, s->points_per_mat, s->n_slots, s->slots};
+    *out = PcsShape{s->log_h, s->n_rounds, s->mats_per_round, s->widths, s->points_per_mat, s->n_slots, s->slots, nullptr};
+    return OK;
+}
+// the mixed entries: log_heights in place of shape->log_h
+static int pcs_shape_mixed_of(const p3hip_pcs_shape_t* s, const unsigned* log_heights, PcsShape* out, const char* who) {
+    if (!log_heights) return fail(ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (int rc = pcs_shape_of(s, out, who)) return rc;
+    out->log_h = 0;
+    out->log_heights = log_heights;
     return OK;
 }
 extern "C" {
@@ -1435,6 +1443,29 @@ int p3hip_pcs_verifier_create(int hash, int hiding, const p3hip_fri_params_t* pa
         if (!params || !out) return fail(ERR_BAD_ARG, "pcs_verifier_create: null argument");
         PcsShape sh;
         if (int rc = pcs_shape_of(shape, &sh, "pcs_verifier_create")) return rc;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::unique_ptr<p3hip_pcs_verifier> h(new p3hip_pcs_verifier());
+        if (int rc = h->v.init(hash, hiding != 0, fp, sh, max_proofs)) return rc;
+        *out = h.release();
+        return OK;
+    });
+}
+int p3hip_pcs_proof_len_mixed(int hash, int hiding, const p3hip_fri_params_t* params, const p3hip_pcs_shape_t* shape, const unsigned* log_heights,
+                              size_t* len_out) {
+    return guarded([&]() -> int {
+        if (!params || !len_out) return fail(ERR_BAD_ARG, "pcs_proof_len_mixed: null argument");
+        PcsShape sh;
+        if (int rc = pcs_shape_mixed_of(shape, log_heights, &sh, "pcs_proof_len_mixed")) return rc;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        return pcs_proof_len(hash, hiding != 0, fp, sh, len_out);
+    });
+}
+int p3hip_pcs_verifier_create_mixed(int hash, int hiding, const p3hip_fri_params_t* params, const p3hip_pcs_shape_t* shape,
+                                    const unsigned* log_heights, size_t max_proofs, p3hip_pcs_verifier_t** out) {
+    return guarded([&]() -> int {
+        if (!params || !out) return fail(ERR_BAD_ARG, "pcs_verifier_create_mixed: null argument");
+        PcsShape sh;
+        if (int rc = pcs_shape_mixed_of(shape, log_heights, &sh, "pcs_verifier_create_mixed")) return rc;
         FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
         std::unique_ptr<p3hip_pcs_verifier> h(new p3hip_pcs_verifier());
         if (int rc = h->v.init(hash, hiding != 0, fp, sh, max_proofs)) return rc;

@@ -4,7 +4,7 @@
 //
 // A SHAPE fixes the layout of every proof: the FRI parameters, the committed log height, per round the matrices' widths, per matrix
 // its opening points as SLOTS (a member supplies n_slots points; pair (matrix, point) -> slot).  Every offset is then a function of
-// the shape: PLayout is computed on the host when the verifier is created and passed to the kernels by value (1.7 kB: it fits).
+// the shape: PLayout is computed on the host when the verifier is created and passed to the kernels by value (2.0 kB: it fits).
 //
 // SAFETY RULE.  NO LOAD ADDRESS AND NO LOOP BOUND DEPENDS ON A PROOF BYTE, AN OPENED VALUE, A POINT OR A CHALLENGER STATE WORD.  A
 // proof whose length differs from the shape's is rejected unread; every count / width / depth / salt-length word is compared with the
@@ -19,8 +19,9 @@
 //                         the roots, a base-field point on GENERATOR <g_big>, the state counters.  Then the transcript (DevChal,
 //                         transcript.hip.h) from the imported state: opened values, alpha, the commit-phase betas, the final
 //                         polynomial, the witness, the proof of work, the query indices; the state is exported.  Leaves in HBM per
-//                         member: alpha^c for c below the widest matrix, and per (matrix, point) pair alpha^off and
-//                         alpha^off Y, Y = sum_c alpha^c opened_c.
+//                         member: alpha^c for c below the widest matrix, and per (matrix, point) pair alpha^aoff and
+//                         alpha^aoff Y, Y = sum_c alpha^c opened_c, aoff the pair's alpha exponent.  The coset gate is against the
+//                         TALLEST coset, which contains every smaller one.
 //   pv_query_kernel       per (member, query): S_m = sum_c alpha^c row[c] ONCE per matrix, shared by its points;
 //                         ro = sum_pairs (alpha^off Y - alpha^off S_m) / (z - x) with the <= 4 slot denominators inverted together
 //                         (one inversion per query); then FriCheck::query's walk: writes every round's (ev0, ev1) leaf and compares
@@ -41,6 +42,19 @@
 //                         pv_query_kernel's pair plus its salt; hashed up the path in the proof (the per-lane sponge / compression
 //                         of mmcs_verify.hip) and compared with the member's root / the round's root in the proof.
 //   pv_finish_kernel      order key -> status, count of rejected members.
+// MIXED HEIGHTS (a verifier from p3hip_pcs_verifier_create_mixed whose matrices are not all of one height; pcs_verify_any with
+// log_heights is the specification).  A CLASS is the set of matrices of one log_big_c = log_h_c + log_blowup.  The layout knows
+// log_big_m per matrix, per round the tree depth log_big_r (its tallest matrix: path length, depth word), per pair its position among
+// the opened values AND its alpha exponent (its class's counter, which runs across rounds), and which classes have a point.  The
+// query and opening kernels take a compile-time MIXED parameter, so that a same-height shape runs the arithmetic it ran before; every
+// height, depth, injection level and shift below comes from PLayout, none from a member.
+//   pv_query_kernel<_, true>   one reduced opening per class, computed when the walk reaches its height (one batched inversion of the
+//                              slot denominators per class; one reduced opening live; nothing indexed by a runtime class number): the
+//                              tallest class starts the walk, and after the fold that reaches 2^log_big_c: folded += beta_r^2 ro_c.
+//   pv_open_kernel<_, true>    an input round's opening walks log_big_r levels from index >> (log_big - log_big_r); the leaf is the
+//                              round's tallest matrices in input order; a shorter class's row is hashed and compressed in (right
+//                              operand) at the level whose size equals its height, before that level's sibling.
+// A roll-in or an injection adds no check of its own: order keys and codes are where they were.
 // The first failure in the HOST's order decides the code: every check does atomicMin on a per-member word (order key << 8 | code).
 // Anything the host answers with 5..9 or 12, or refuses for a member's VALUES, is VERIFY_MALFORMED here (key 0 unless it is a shape
 // word inside a query, which keeps its place in the order so that an earlier query's 13 / 14 / 15 still wins).
@@ -82,18 +96,23 @@ struct PLayout {
     uint32_t salt, log_big, lfinal, n_fri, nq, fpl, pow_bits;
     uint32_t proof_words, nq_off, q_base, q_len, fpl_off, fpoly_off, witness_off;
     uint32_t n_in, n_slots, n_pairs, total, wmax, row_words;
+    // mixed heights.  mixed: the matrices are not all of one height (which kernels run); class_mask: bit log_big_c of every class with a
+    // point; per round its tree's depth and a bit per log_big_m among its matrices
+    uint32_t mixed, class_mask, log_big_r[PV_MAX_IN], round_mask[PV_MAX_IN];
     // input rounds; offsets are relative to a query's first word
     uint32_t nm[PV_MAX_IN], mat0[PV_MAX_IN], open_off[PV_MAX_IN], depth_off[PV_MAX_IN], leaf_len[PV_MAX_IN];
     // matrices, round -> matrix: width word at val_off - 1, salt length word at salt_off - 1; leaf_start: where the matrix begins in its leaf
+    // (mixed: in the row of its class, the matrices of its round and height in input order)
     uint32_t width[PV_MAX_ALLMATS], val_off[PV_MAX_ALLMATS], salt_off[PV_MAX_ALLMATS], leaf_start[PV_MAX_ALLMATS], np[PV_MAX_ALLMATS];
-    // (matrix, point) pairs, round -> matrix -> point: the first power of alpha the pair consumes, its slot, its matrix
-    uint16_t pair_off[PV_MAX_PAIRS];
+    uint8_t log_big_m[PV_MAX_ALLMATS];
+    // (matrix, point) pairs, round -> matrix -> point: where the pair's opened values begin, the first power of alpha it consumes (its
+    // class's counter; with one class the same number), its slot, its matrix
+    uint16_t pair_off[PV_MAX_PAIRS], pair_aoff[PV_MAX_PAIRS];
     uint8_t pair_slot[PV_MAX_PAIRS], pair_mat[PV_MAX_PAIRS];
     uint32_t nr_off, fri_off[PV_MAX_FRI];
     // constants of the field
     uint32_t gen, gen_inv, neg_half, gens[PV_MAX_FRI], gens_inv[PV_MAX_FRI];
 };
-static_assert(sizeof(PLayout) <= 3072, "passed by value in the kernel arguments");
 
 struct PState {
     Ext beta[PV_MAX_FRI];
@@ -117,6 +136,9 @@ struct PArgs {
     uint32_t* pb;             // n x n_pairs x 4: alpha^off Y
     unsigned long long* key;  // n
 };
+
+static_assert(sizeof(PLayout) + sizeof(PArgs) <= 4096, "both are passed by value: the kernel-argument segment holds 4 KB");
+static_assert(bb::TWO_ADICITY < 32 && PV_MAX_FRI > bb::TWO_ADICITY, "a class is a bit of a 32-bit mask and an index of gens[]");
 
 __device__ __forceinline__ uint64_t make_key(uint64_t order, uint32_t code) { return (order << 8) | code; }
 __device__ __forceinline__ void report(const PArgs& a, uint32_t i, uint64_t order, uint32_t code) {
@@ -191,7 +213,7 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
         for (uint32_t k = 0; k < cnt; k++) ch.observe((uint32_t)__shfl((int)v, (int)k, 64));
     }
     const Ext al = ch.sample_ext();
-    {   // alpha^c for c < wmax, and per pair alpha^off and alpha^off Y: lane l walks the columns l, l + 64, ...
+    {   // alpha^c for c < wmax, and per pair alpha^aoff and alpha^aoff Y: lane l walks the columns l, l + 64, ...
         Ext a64 = al;
         for (int k = 0; k < 6; k++) a64 = bb::sqr(a64);
         const Ext pl = bb::pow(al, (uint64_t)lane);
@@ -203,7 +225,7 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
         Ext mine[2];
         for (uint32_t h = 0; h < 2; h++) {
             const uint32_t pr = lane + 64 * h;
-            mine[h] = pr < L.n_pairs ? bb::pow(al, (uint64_t)L.pair_off[pr]) : bb::ext_one();
+            mine[h] = pr < L.n_pairs ? bb::pow(al, (uint64_t)L.pair_aoff[pr]) : bb::ext_one();
         }
         for (uint32_t pr = 0; pr < L.n_pairs; pr++) {
             const uint32_t off = L.pair_off[pr], wd = L.width[L.pair_mat[pr]];
@@ -244,21 +266,13 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
 // ---- 2. reduced opening and fold walk: per (member, query) ------------------------------------------------------------------
 __device__ __forceinline__ Ext pick4(const Ext d[4], uint32_t s) { return s == 0 ? d[0] : s == 1 ? d[1] : s == 2 ? d[2] : d[3]; }
 
-template <bool WAVE>
-__global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
-    const uint64_t gt = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t t = WAVE ? gt >> 6 : gt;  // WAVE: the same for every lane of a wave, so every branch below is wave-uniform
-    const uint32_t lane = WAVE ? (threadIdx.x & 63u) : 0u, step = WAVE ? 64u : 1u;
-    if (t >= (uint64_t)a.n * L.nq) return;
-    const uint32_t i = (uint32_t)(t / L.nq), q = (uint32_t)(t % L.nq);
-    if (!length_ok(a, L, i) || header_rejected(a, i)) return;
-    const uint32_t* w = proof_words(a, i);
-    const uint32_t* qw = w + L.q_base + (size_t)q * L.q_len;
-    const uint32_t* pts = a.points + (size_t)i * L.n_slots * 4;
-    const uint32_t* alp = a.alp + (size_t)i * L.wmax * 4;
-    const PState* st = a.st + i;
-    const uint32_t index = a.idx[t];
-    const uint32_t xi = bb::mul(L.gen, bb::pow(L.gens[L.log_big], rev_bits_dev(index, L.log_big)));
+// The reduced opening of ONE class at one query: sum over the class's (matrix, point) pairs of (alpha^aoff Y - alpha^aoff S_m) / (z - x),
+// x = GENERATOR g_lb^bitrev(index >> (log_big - lb)).  MIXED = false: lb is log_big and every matrix belongs (the one-class form, as it
+// always ran).  Which matrices belong is the layout's word: in the wave form the branch is wave-uniform.
+template <bool WAVE, bool MIXED>
+__device__ __forceinline__ Ext class_opening(const PArgs& a, const PLayout& L, uint32_t i, const uint32_t* qw, const uint32_t* pts,
+                                             const uint32_t* alp, uint32_t index, uint32_t lb, uint32_t lane, uint32_t step) {
+    const uint32_t xi = bb::mul(L.gen, bb::pow(L.gens[lb], rev_bits_dev(MIXED ? index >> (L.log_big - lb) : index, lb)));
     Ext dz[4];
     {   // 1 / (z_s - x) for the slots, one inversion
         Ext d[4], pre[4], acc = bb::ext_one();
@@ -272,10 +286,11 @@ __global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
 #pragma unroll
         for (int s = 3; s >= 0; s--) { dz[s] = bb::mul(inv, pre[s]); inv = bb::mul(inv, d[s]); }
     }
-    Ext folded = bb::ext_zero();
+    Ext ro = bb::ext_zero();
     uint32_t pair = 0;
     for (uint32_t r = 0; r < L.n_in; r++)
         for (uint32_t m = L.mat0[r]; m < L.mat0[r] + L.nm[r]; m++) {
+            if (MIXED && (L.log_big_m[m] != lb || L.np[m] == 0)) { pair += L.np[m]; continue; }
             const uint32_t* vals = qw + L.val_off[m];
             const uint32_t wd = L.width[m];
             Ext s = bb::ext_zero();
@@ -284,9 +299,27 @@ __global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
             for (uint32_t p = 0; p < L.np[m]; p++, pair++) {
                 const size_t po = 4 * ((size_t)i * L.n_pairs + pair);
                 const Ext num = bb::sub(ldx(a.pb, po), bb::mul(ldx(a.pa, po), s));
-                folded = bb::add(folded, bb::mul(num, pick4(dz, L.pair_slot[pair])));
+                ro = bb::add(ro, bb::mul(num, pick4(dz, L.pair_slot[pair])));
             }
         }
+    return ro;
+}
+
+template <bool WAVE, bool MIXED>
+__global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
+    const uint64_t gt = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t = WAVE ? gt >> 6 : gt;  // WAVE: the same for every lane of a wave, so every branch below is wave-uniform
+    const uint32_t lane = WAVE ? (threadIdx.x & 63u) : 0u, step = WAVE ? 64u : 1u;
+    if (t >= (uint64_t)a.n * L.nq) return;
+    const uint32_t i = (uint32_t)(t / L.nq), q = (uint32_t)(t % L.nq);
+    if (!length_ok(a, L, i) || header_rejected(a, i)) return;
+    const uint32_t* w = proof_words(a, i);
+    const uint32_t* qw = w + L.q_base + (size_t)q * L.q_len;
+    const uint32_t* pts = a.points + (size_t)i * L.n_slots * 4;
+    const uint32_t* alp = a.alp + (size_t)i * L.wmax * 4;
+    const PState* st = a.st + i;
+    const uint32_t index = a.idx[t];
+    Ext folded = class_opening<WAVE, MIXED>(a, L, i, qw, pts, alp, index, L.log_big, lane, step);  // the tallest class starts the walk
     uint32_t idx = index;
     uint32_t* evs = a.evs + t * L.n_fri * 8;
     for (uint32_t r = 0; r < L.n_fri; r++) {
@@ -299,8 +332,12 @@ __global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
             for (int c = 0; c < 4; c++) { evs[8 * r + c] = ev0.c[c]; evs[8 * r + 4 + c] = ev1.c[c]; }
         const uint32_t e = rev_bits_dev(pr, lfh);
         const uint32_t sx = bb::pow(L.gens[lfh + 1], e), s_inv = bb::pow(L.gens_inv[lfh + 1], e);
-        const Ext num = bb::mul(bb::sub(st->beta[r], bb::ext_from_base(sx)), bb::sub(ev1, ev0));
+        const Ext beta = st->beta[r];
+        const Ext num = bb::mul(bb::sub(beta, bb::ext_from_base(sx)), bb::sub(ev1, ev0));
         folded = bb::add(ev0, bb::scale(num, bb::mul(L.neg_half, s_inv)));  // 1 / (-s - s)
+        // the fold has reached 2^lfh elements: the class of that height rolls in (the fold onto the final vector included)
+        if (MIXED && ((L.class_mask >> lfh) & 1u))
+            folded = bb::add(folded, bb::mul(bb::sqr(beta), class_opening<WAVE, true>(a, L, i, qw, pts, alp, index, lfh, lane, step)));
         idx = pr;
     }
     const uint32_t xf = bb::pow(L.gens[L.lfinal], rev_bits_dev(idx, L.lfinal));
@@ -311,14 +348,15 @@ __global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
 
 // ---- 3. openings: one lane per (slot, member, query) ------------------------------------------------------------------------
 // What one lane opens.  n_ev = 8: an FRI leaf, evs[0..8) then `salt` words at tail.  n_ev = 0: an input round's leaf over the
-// matrices m0 .. m0 + nm of the layout, each followed by its salt, the words gathered from the query at qw.
+// matrices m0 .. m0 + nm of the layout, each followed by its salt, the words gathered from the query at qw.  Mixed heights: the
+// leaf is the round's tallest class (log_big_c = depth); inj has a bit per shorter class of the round, by log_big_c.
 struct LaneOpening {
     const uint32_t* evs;
     const uint32_t* qw;
     const uint32_t* tail;
     const uint32_t* path;
     const uint32_t* root;
-    uint32_t n_ev, m0, nm, leaf_len, depth, index;
+    uint32_t n_ev, m0, nm, leaf_len, depth, index, inj;
     __device__ __forceinline__ uint32_t leaf_word(const PLayout& L, uint32_t e) const {
         if (n_ev) return e < n_ev ? evs[e] : tail[e - n_ev];
         uint32_t m = m0;
@@ -327,25 +365,39 @@ struct LaneOpening {
         const uint32_t c = e - L.leaf_start[m];
         return c < L.width[m] ? qw[L.val_off[m] + c] : qw[L.salt_off[m] + (c - L.width[m])];
     }
+    // word e of the row of the round's class lb: the round's matrices of that height, in input order
+    __device__ __forceinline__ uint32_t class_word(const PLayout& L, uint32_t lb, uint32_t e) const {
+        uint32_t m = m0;
+        for (uint32_t k = 0; k < nm; k++)
+            if (L.log_big_m[m0 + k] == lb && e >= L.leaf_start[m0 + k]) m = m0 + k;
+        const uint32_t c = e - L.leaf_start[m];  // the class's first matrix starts at 0: one of them was taken
+        return c < L.width[m] ? qw[L.val_off[m] + c] : qw[L.salt_off[m] + (c - L.width[m])];
+    }
+    __device__ __forceinline__ uint32_t class_len(const PLayout& L, uint32_t lb) const {
+        uint32_t n = 0;
+        for (uint32_t k = 0; k < nm; k++)
+            if (L.log_big_m[m0 + k] == lb) n += L.width[m0 + k] + L.salt;
+        return n;
+    }
 };
 
-template <int HASH>
+template <int HASH, bool MIXED>
 __device__ __forceinline__ bool lane_open_mismatch(const PLayout& L, const LaneOpening& o, uint32_t& hi);
 
-// The two forms below restate mmcs_verify.hip's per-lane walks as verifier_dev.hip does (a fix there belongs here too): one height
-// class over words gathered from proof bytes and the fold pairs.
-// PaddingFreeSponge<Poseidon2-16, 16, 8, 8> over the leaf, TruncatedPermutation up the path
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    const p2f::MagicRegs smk = p2f::magic_regs();
-    double s[16], cur[8];
+// The two forms below restate mmcs_verify.hip's per-lane walks as verifier_dev.hip does (a fix there belongs here too) over words
+// gathered from proof bytes and the fold pairs: MIXED = false one height class; MIXED = true its injection schedule, the shorter
+// classes of an input round compressed in as the right operand at the level whose size equals their height.  (Written after the
+// schedule of mmcs_verify.hip's kernels: with a second sponge site inside the path loop this compiler keeps the Keccak state in scratch.)
+// PaddingFreeSponge<Poseidon2-16, 16, 8, 8> over the words word(0) .. word(len - 1), digest left in s[0..8)
+template <typename F>
+__device__ __forceinline__ void p2_sponge(double (&s)[16], uint32_t len, uint32_t& hi, F word) {
 #pragma unroll
     for (int k = 0; k < 16; k++) s[k] = 0.0;
-    for (uint32_t k = 0; k < o.leaf_len; k += 8) {
+    for (uint32_t k = 0; k < len; k += 8) {
 #pragma unroll
         for (int e = 0; e < 8; e++)
-            if (k + e < o.leaf_len) {
-                const uint32_t v = o.leaf_word(L, k + e);
+            if (k + e < len) {
+                const uint32_t v = word(k + e);
                 hi = max(hi, v);
                 s[e] = p2f::load_elem(v);
             }
@@ -353,6 +405,14 @@ __device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2>(const PLayout
 #pragma unroll
         for (int e = 0; e < 16; e++) s[e] = p2f::reduce(s[e]);
     }
+}
+
+// PaddingFreeSponge over the leaf, TruncatedPermutation up the path
+template <>
+__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2, false>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    const p2f::MagicRegs smk = p2f::magic_regs();
+    double s[16], cur[8];
+    p2_sponge(s, o.leaf_len, hi, [&](uint32_t e) { return o.leaf_word(L, e); });
 #pragma unroll
     for (int k = 0; k < 8; k++) cur[k] = s[k];
     for (uint32_t l = 0; l < o.depth; l++) {
@@ -374,21 +434,63 @@ __device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2>(const PLayout
     for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
     return mismatch;
 }
-
-// SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the leaf, CompressionFunctionFromHasher up the path; digest words are
-// raw u64 halves: any value is hashed
+// mixed heights: verify_lane_p2_kernel's schedule (mmcs_verify.hip), one sponge site and one compression site.  Level l's nodes have
+// 2^(depth - l) of them: the class of that height (the leaf at l = 0) is hashed, compressed in as the right operand, then the sibling.
 template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    uint64_t st[25], cur[4];
+__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2, true>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    const p2f::MagicRegs smk = p2f::magic_regs();
+    double s[16], cur[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) cur[k] = 0.0;
+    for (uint32_t l = 0; l <= o.depth; l++) {
+        const uint32_t lb = o.depth - l;
+        const bool has = l == 0 || ((o.inj >> lb) & 1u);
+        if (has) p2_sponge(s, l == 0 ? o.leaf_len : o.class_len(L, lb), hi, [&](uint32_t e) { return o.n_ev ? o.leaf_word(L, e) : o.class_word(L, lb, e); });
+        _Pragma("clang loop unroll(disable)")
+        for (uint32_t sub = 0; sub < 2; sub++) {
+            if (sub == 0) {
+                if (l == 0) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) cur[k] = s[k];
+                }
+                if (!has || l == 0) continue;
+#pragma unroll
+                for (int k = 0; k < 8; k++) { s[8 + k] = s[k]; s[k] = cur[k]; }
+            } else {
+                if (l == o.depth) continue;
+                const bool right = (o.index >> l) & 1u;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t sw = o.path[8 * l + k];
+                    hi = max(hi, sw);
+                    const double sd = p2f::load_elem(sw);
+                    s[k] = right ? sd : cur[k];
+                    s[8 + k] = right ? cur[k] : sd;
+                }
+            }
+            p2f::permute(s);
+#pragma unroll
+            for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
+        }
+    }
+    bool mismatch = false;
+#pragma unroll
+    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
+    return mismatch;
+}
+
+// SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the words word(0) .. word(len - 1), digest left in st[0..4)
+template <typename F>
+__device__ __forceinline__ void kk_sponge(uint64_t (&st)[25], uint32_t len, uint32_t& hi, F word) {
 #pragma unroll
     for (int k = 0; k < 25; k++) st[k] = 0;
-    const uint32_t n64 = (o.leaf_len + 1) / 2;
+    const uint32_t n64 = (len + 1) / 2;
     for (uint32_t b = 0; b < n64; b += 17) {
 #pragma unroll
         for (int k = 0; k < 17; k++) {
             const uint32_t e = 2 * (b + k);
-            if (e < o.leaf_len) {
-                const uint32_t lo = o.leaf_word(L, e), hw = e + 1 < o.leaf_len ? o.leaf_word(L, e + 1) : 0u;
+            if (e < len) {
+                const uint32_t lo = word(e), hw = e + 1 < len ? word(e + 1) : 0u;
                 hi = max(hi, max(lo, hw));
                 st[k] = (uint64_t)lo | ((uint64_t)hw << 32);
             }
@@ -396,6 +498,13 @@ __device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK>(const PLayout& L
         if (b + 17 >= n64) kk::permute_digest(st);  // the last block: only the digest words are read
         else kk::permute(st);
     }
+}
+
+// the sponge over the leaf, CompressionFunctionFromHasher up the path; digest words are raw u64 halves: any value is hashed
+template <>
+__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK, false>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    uint64_t st[25], cur[4];
+    kk_sponge(st, o.leaf_len, hi, [&](uint32_t e) { return o.leaf_word(L, e); });
 #pragma unroll
     for (int k = 0; k < 4; k++) cur[k] = st[k];
     for (uint32_t l = 0; l < o.depth; l++) {
@@ -417,8 +526,48 @@ __device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK>(const PLayout& L
     for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
     return mismatch;
 }
+// mixed heights: verify_lane_keccak_kernel's schedule (mmcs_verify.hip), as the Poseidon2 form above
+template <>
+__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK, true>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
+    uint64_t st[25], cur[4] = {0, 0, 0, 0};
+    for (uint32_t l = 0; l <= o.depth; l++) {
+        const uint32_t lb = o.depth - l;
+        const bool has = l == 0 || ((o.inj >> lb) & 1u);
+        if (has) kk_sponge(st, l == 0 ? o.leaf_len : o.class_len(L, lb), hi, [&](uint32_t e) { return o.n_ev ? o.leaf_word(L, e) : o.class_word(L, lb, e); });
+        _Pragma("clang loop unroll(disable)")
+        for (uint32_t sub = 0; sub < 2; sub++) {
+            uint64_t r4[4];
+            bool right = false;
+            if (sub == 0) {
+                if (l == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) cur[k] = st[k];
+                }
+                if (!has || l == 0) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++) r4[k] = st[k];
+            } else {
+                if (l == o.depth) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++) r4[k] = (uint64_t)o.path[8 * l + 2 * k] | ((uint64_t)o.path[8 * l + 2 * k + 1] << 32);
+                right = (o.index >> l) & 1u;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) { st[k] = right ? r4[k] : cur[k]; st[4 + k] = right ? cur[k] : r4[k]; }
+#pragma unroll
+            for (int k = 8; k < 25; k++) st[k] = 0;
+            kk::permute_digest(st);
+#pragma unroll
+            for (int k = 0; k < 4; k++) cur[k] = st[k];
+        }
+    }
+    bool mismatch = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
+    return mismatch;
+}
 
-template <int HASH>
+template <int HASH, bool MIXED>
 __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
     const uint64_t per_slot = (uint64_t)a.n * L.nq, t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= per_slot * (L.n_in + L.n_fri)) return;
@@ -442,12 +591,13 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
             if (qw[L.val_off[m] - 1] != L.width[m]) shape = true;
             if (L.salt && qw[L.salt_off[m] - 1] != L.salt) shape = true;
         }
-        o.depth = L.log_big;
+        o.depth = MIXED ? L.log_big_r[slot] : L.log_big;  // the round's own tree: the layout's word, compared with the proof's
         if (qw[L.depth_off[slot]] != o.depth) shape = true;
         o.path = qw + L.depth_off[slot] + 1;
         o.m0 = m0; o.nm = nm;
         o.leaf_len = L.leaf_len[slot];
-        o.index = index;
+        o.index = MIXED ? index >> (L.log_big - o.depth) : index;
+        if (MIXED) o.inj = L.round_mask[slot] & ~(1u << o.depth);  // the shorter classes of the round, by log_big_c
         o.root = a.roots + ((size_t)i * L.n_in + slot) * 8;
         code = CODE_INPUT_OPENING;
     } else {
@@ -468,7 +618,9 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
         o.root = w + 1 + 8 * r;
         code = CODE_FRI_OPENING;
     }
-    const bool mismatch = lane_open_mismatch<HASH>(L, o, hi);
+    // (the FRI lanes of a mixed shape take the MIXED walk too, with nothing to inject: sending them to the one-class walk puts both
+    // walks into one kernel, which takes the Poseidon2 form from 118 to 134 VGPRs, below four waves per SIMD)
+    const bool mismatch = lane_open_mismatch<HASH, MIXED>(L, o, hi);
     if (shape) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
     if (hi >= bb::P) report(a, i, KEY_HEADER, VERIFY_MALFORMED);
     if (mismatch) report(a, i, qkey + 2 * slot + 1, code);
@@ -487,11 +639,31 @@ __global__ void __launch_bounds__(256) pv_finish_kernel(const unsigned long long
 // ---- host: the layout of one shape ------------------------------------------------------------------------------------------
 // The gates and their messages are pcs_verify_any's (verifier.hip), in its order; what it checks on a member's values (canonical
 // points, the LDE coset, canonical opened values) is the kernels' business.  Slots take the place of its "distinct points" rule.
+// sh.log_heights (one per matrix, round -> matrix; sh.log_h is then ignored): mixed heights, gated as pcs_verify_any gates them, the
+// round and matrix counts first since log_heights is read by them.  With all heights equal the layout is the one-class layout.
 int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, PLayout* out) {
     auto bad = [&](const std::string& msg) { return fail(ERR_BAD_ARG, msg); };
     if (!sh.mats_per_round || !sh.widths || !sh.points_per_mat || !sh.slots) return bad("pcs verify: null argument");
     if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
     uint32_t log_h = sh.log_h;
+    const size_t n_rounds = sh.n_rounds, max_mats = hiding ? PCS_HIDING_MAX_MATS : PCS_MAX_MATS;
+    uint32_t lh[PV_MAX_ALLMATS];  // per matrix, filled either way
+    if (sh.log_heights) {
+        if (hiding) return bad("pcs verifier: mixed heights are not covered for HidingFriPcs (no hiding prover produces them): hiding must be 0");
+        if (n_rounds == 0) return bad("pcs verify: zero rounds");
+        if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
+        size_t nm = 0;
+        for (size_t r = 0; r < n_rounds; r++) {
+            if (sh.mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
+            if (sh.mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
+            nm += sh.mats_per_round[r];
+        }
+        log_h = 0;
+        uint32_t lo = ~0u;
+        for (size_t m = 0; m < nm; m++) { lh[m] = sh.log_heights[m]; log_h = std::max(log_h, lh[m]); lo = std::min(lo, lh[m]); }
+        // (the bounds on log_h and log_blowup alone, as in pcs_verify_any: a class is log_h_m + log_blowup, an index below, and must not wrap)
+        if (lo < 1 || log_h > bb::TWO_ADICITY || fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
+    }
     if (hiding) {
         if (log_h < 1 || log_h >= bb::TWO_ADICITY)
             return bad("pcs verify: log_h must be in [1, " + std::to_string(bb::TWO_ADICITY - 1) + "] (the caller's log height; the committed polynomials have degree < 2^(log_h + 1))");
@@ -501,7 +673,6 @@ int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, 
     if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
     if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
     if (fp.num_queries == 0) return bad("pcs verify: num_queries must be positive");
-    const size_t n_rounds = sh.n_rounds, max_mats = hiding ? PCS_HIDING_MAX_MATS : PCS_MAX_MATS;
     if (n_rounds == 0) return bad("pcs verify: zero rounds");
     if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
     if (sh.n_slots < 1 || sh.n_slots > PCS_MAX_SLOTS) return bad("pcs verifier: n_slots must be in [1, " + std::to_string(PCS_MAX_SLOTS) + "]");
@@ -519,6 +690,7 @@ int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, 
     L.n_slots = (uint32_t)sh.n_slots;
     const uint32_t D = 8;
     size_t mi = 0, pi = 0, total = 0;
+    uint32_t cnt[bb::TWO_ADICITY + 1] = {0};  // alpha powers consumed so far, per class
     uint64_t p = 1;  // within a query, behind the count of rounds
     for (size_t r = 0; r < n_rounds; r++) {
         const size_t nm = sh.mats_per_round[r];
@@ -527,24 +699,35 @@ int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, 
         L.nm[r] = (uint32_t)nm;
         L.mat0[r] = (uint32_t)mi;
         L.open_off[r] = (uint32_t)p++;
-        uint32_t leaf = 0;
+        uint32_t leaf[bb::TWO_ADICITY + 1] = {0};  // the row of each class of the round so far
         for (size_t m = 0; m < nm; m++, mi++) {
             const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
             const size_t wd = sh.widths[mi], np = sh.points_per_mat[mi];
             if (wd < 1 || wd > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
             if (np > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
+            if (!sh.log_heights) lh[mi] = log_h;
+            if (lh[mi] < fp.log_final_poly_len)
+                return bad(who + " has height 2^" + std::to_string(lh[mi]) + ", below the final polynomial's 2^" + std::to_string(fp.log_final_poly_len));
+            const uint32_t lb = lh[mi] + fp.log_blowup;  // <= log_big <= TWO_ADICITY
+            L.log_big_m[mi] = (uint8_t)lb;
+            L.log_big_r[r] = std::max(L.log_big_r[r], lb);
+            L.round_mask[r] |= 1u << lb;
+            if (np) L.class_mask |= 1u << lb;
+            if (lb != L.log_big) L.mixed = 1;
             L.width[mi] = (uint32_t)wd;
             L.np[mi] = (uint32_t)np;
             L.val_off[mi] = (uint32_t)(p + 1);
             p += 1 + wd;
-            L.leaf_start[mi] = leaf;
-            leaf += (uint32_t)wd + L.salt;
+            L.leaf_start[mi] = leaf[lb];
+            leaf[lb] += (uint32_t)wd + L.salt;
             L.wmax = std::max(L.wmax, (uint32_t)wd);
             L.row_words += (uint32_t)wd;
             for (size_t k = 0; k < np; k++, pi++) {
                 const std::string pw = who + " point " + std::to_string(k);
                 if (sh.slots[pi] >= sh.n_slots) return bad(pw + ": slot " + std::to_string(sh.slots[pi]) + " of " + std::to_string(sh.n_slots));
                 L.pair_off[pi] = (uint16_t)total;
+                L.pair_aoff[pi] = (uint16_t)cnt[lb];
+                cnt[lb] += (uint32_t)wd;
                 L.pair_slot[pi] = (uint8_t)sh.slots[pi];
                 L.pair_mat[pi] = (uint8_t)mi;
                 total += wd;
@@ -553,11 +736,13 @@ int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, 
         }
         if (L.salt)
             for (size_t m = 0; m < nm; m++) { L.salt_off[L.mat0[r] + m] = (uint32_t)(p + 1); p += 1 + L.salt; }
-        L.leaf_len[r] = leaf;
+        L.leaf_len[r] = leaf[L.log_big_r[r]];
         L.depth_off[r] = (uint32_t)p;
-        p += 1 + (uint64_t)D * L.log_big;
+        p += 1 + (uint64_t)D * L.log_big_r[r];
     }
     if (total == 0) return bad("pcs verify: no opening point");
+    if (!((L.class_mask >> L.log_big) & 1u))
+        return bad("pcs verify: no matrix of the tallest height 2^" + std::to_string(log_h) + " has an opening point: the FRI input would be missing");
     L.n_pairs = (uint32_t)pi;
     L.total = (uint32_t)total;
     L.nr_off = (uint32_t)p++;
@@ -664,13 +849,16 @@ int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uin
     PArgs a{d_proofs, stride, d_lens, d_roots, d_points, d_opened, d_chal_in, d_chal_out, (uint32_t)n, im->st, im->idx, im->evs, im->alp, im->pa, im->pb, im->key};
     hipLaunchKernelGGL(pv_transcript_kernel, dim3((uint32_t)n), dim3(64), 0, stream, a, L);
     const uint64_t pq = (uint64_t)n * L.nq;
-    if (wave_form()) hipLaunchKernelGGL(pv_query_kernel<true>, dim3((uint32_t)((pq + 3) / 4)), dim3(256), 0, stream, a, L);
-    else hipLaunchKernelGGL(pv_query_kernel<false>, dim3((uint32_t)((pq + 255) / 256)), dim3(256), 0, stream, a, L);
-    const uint64_t lanes = pq * (L.n_in + L.n_fri);
-    if (L.hash == HASH_KECCAK)
-        hipLaunchKernelGGL(pv_open_kernel<HASH_KECCAK>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, a, L);
-    else
-        hipLaunchKernelGGL(pv_open_kernel<HASH_POSEIDON2>, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, a, L);
+    const dim3 qgrid((uint32_t)(wave_form() ? (pq + 3) / 4 : (pq + 255) / 256));
+    if (wave_form() && L.mixed) hipLaunchKernelGGL((pv_query_kernel<true, true>), qgrid, dim3(256), 0, stream, a, L);
+    else if (wave_form()) hipLaunchKernelGGL((pv_query_kernel<true, false>), qgrid, dim3(256), 0, stream, a, L);
+    else if (L.mixed) hipLaunchKernelGGL((pv_query_kernel<false, true>), qgrid, dim3(256), 0, stream, a, L);
+    else hipLaunchKernelGGL((pv_query_kernel<false, false>), qgrid, dim3(256), 0, stream, a, L);
+    const dim3 ogrid((uint32_t)((pq * (L.n_in + L.n_fri) + 255) / 256));
+    if (L.hash == HASH_KECCAK && L.mixed) hipLaunchKernelGGL((pv_open_kernel<HASH_KECCAK, true>), ogrid, dim3(256), 0, stream, a, L);
+    else if (L.hash == HASH_KECCAK) hipLaunchKernelGGL((pv_open_kernel<HASH_KECCAK, false>), ogrid, dim3(256), 0, stream, a, L);
+    else if (L.mixed) hipLaunchKernelGGL((pv_open_kernel<HASH_POSEIDON2, true>), ogrid, dim3(256), 0, stream, a, L);
+    else hipLaunchKernelGGL((pv_open_kernel<HASH_POSEIDON2, false>), ogrid, dim3(256), 0, stream, a, L);
     hipLaunchKernelGGL(pv_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, im->key, (uint32_t)n, d_status, d_rejected);
     P3_HIP(hipGetLastError());
     return OK;

@@ -417,7 +417,9 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
         }
         lh.assign(log_heights, log_heights + nm);
         log_h = *std::max_element(lh.begin(), lh.end());
-        if (*std::min_element(lh.begin(), lh.end()) < 1) return bad("pcs verify: LDE height outside [2^2, 2^27]");
+        // (log_h and log_blowup bounded alone: lh + log_blowup indexes the per-class tables below and must not wrap)
+        if (*std::min_element(lh.begin(), lh.end()) < 1 || log_h > bb::TWO_ADICITY || fp.log_blowup > bb::TWO_ADICITY)
+            return bad("pcs verify: LDE height outside [2^2, 2^27]");
     }
     if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
     if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");

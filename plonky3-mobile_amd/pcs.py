@@ -300,28 +300,52 @@ def _shape(log_h, rounds, n_slots):
     return _Shape(log_h, len(rounds), keep[0], keep[1], keep[2], n_slots, keep[3]), keep
 
 
+def _log_heights(log_h, rounds, hiding, who):
+    """log_h as PcsVerifier / pcs_proof_len take it -> None for an int (every matrix of that height), or the per-matrix lists
+    [[log height per matrix] per round] flattened for the mixed entries (include/p3hip.h p3hip_pcs_verifier_create_mixed)"""
+    if not isinstance(log_h, (list, tuple)):  # anything else goes down the same-height path, which says what it makes of it
+        return None
+    if hiding:
+        raise ValueError("%s: a hiding PCS takes one log height, not per-matrix lists" % who)
+    if [len(r) for r in log_h] != [len(r) for r in rounds]:
+        raise ValueError("%s: one log height per matrix" % who)
+    lhs = [int(v) for r in log_h for v in r]
+    return (C.c_uint * max(len(lhs), 1))(*lhs)
+
+
 def pcs_proof_len(params, hash, log_h, rounds, n_slots, hiding=False):
-    """The byte length every proof of the shape has (host only; rounds as PcsVerifier takes them)."""
-    sh, _keep = _shape(log_h, rounds, n_slots)
+    """The byte length every proof of the shape has (host only; log_h and rounds as PcsVerifier takes them)."""
+    lhs = _log_heights(log_h, rounds, hiding, "pcs_proof_len")
+    sh, _keep = _shape(0 if lhs is not None else log_h, rounds, n_slots)
     out = C.c_size_t()
-    _lib.check(_lib.lib().p3hip_pcs_proof_len(_hash_kind(hash), 1 if hiding else 0, C.cast(params._c(), C.c_void_p), C.byref(sh), C.byref(out)))
+    if lhs is not None:
+        _lib.check(_lib.lib().p3hip_pcs_proof_len_mixed(_hash_kind(hash), 0, C.cast(params._c(), C.c_void_p), C.byref(sh), lhs, C.byref(out)))
+    else:
+        _lib.check(_lib.lib().p3hip_pcs_proof_len(_hash_kind(hash), 1 if hiding else 0, C.cast(params._c(), C.c_void_p), C.byref(sh), C.byref(out)))
     return out.value
 
 
 class PcsVerifier:
     """Pcs::verify of TwoAdicFriPcs / HidingFriPcs for batches of members of ONE shape, on the device (include/p3hip.h "batches of PCS
     proofs verified ON THE DEVICE").  rounds = [[(committed width, [slot of point 0, ...]) per matrix] per round]; a member supplies
-    n_slots points.  Statuses: 0 = accept, the host verifier's codes 11 / 13 / 14 / 15, or VERIFY_MALFORMED (16)."""
+    n_slots points.  log_h: an int (every matrix of that height), or per-matrix lists [[log height per matrix] per round] as verify
+    takes them (mixed heights: p3hip_pcs_verifier_create_mixed; ValueError with hiding).  Statuses: 0 = accept, the host verifier's
+    codes 11 / 13 / 14 / 15, or VERIFY_MALFORMED (16)."""
 
     def __init__(self, log_h, rounds, n_slots, params=None, hash="poseidon2", hiding=False, max_proofs=64):
         self.params = params or FriParameters()
         self.log_h, self.rounds, self.n_slots, self.hash, self.hiding, self.max_proofs = log_h, rounds, n_slots, hash, hiding, max_proofs
         self.n_rounds = len(rounds)
         self.total = sum(int(w) * len(sl) for r in rounds for w, sl in r)
-        sh, _keep = _shape(log_h, rounds, n_slots)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().p3hip_pcs_verifier_create(_hash_kind(hash), 1 if hiding else 0, C.cast(self.params._c(), C.c_void_p), C.byref(sh),
-                                                        max_proofs, C.byref(self._h)))
+        lhs = _log_heights(log_h, rounds, hiding, "PcsVerifier")
+        sh, _keep = _shape(0 if lhs is not None else log_h, rounds, n_slots)
+        if lhs is not None:
+            _lib.check(_lib.lib().p3hip_pcs_verifier_create_mixed(_hash_kind(hash), 0, C.cast(self.params._c(), C.c_void_p), C.byref(sh), lhs,
+                                                                  max_proofs, C.byref(self._h)))
+        else:
+            _lib.check(_lib.lib().p3hip_pcs_verifier_create(_hash_kind(hash), 1 if hiding else 0, C.cast(self.params._c(), C.c_void_p), C.byref(sh),
+                                                            max_proofs, C.byref(self._h)))
         self.proof_len = pcs_proof_len(self.params, hash, log_h, rounds, n_slots, hiding)
         self.wave_form = bool(_lib.lib().p3hip_pcs_verifier_wave_form(self._h))
 

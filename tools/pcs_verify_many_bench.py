@@ -7,7 +7,12 @@
   device   PcsVerifier at n = 1, 8, 64, 512: HIP events around the launches of the device entry (members resident), and end to end
            through the host entry, the upload included;
   split    the device entry's kernels at n = 64 under rocprofv3 --kernel-trace --stats (a child process), when rocprofv3 is on the PATH.
-Writes profiles/pcs_verify_many_bench.txt.      python3 tools/pcs_verify_many_bench.py [--out FILE] [--quick] [--shapes fib,w64,w2633]"""
+Writes profiles/pcs_verify_many_bench.txt.      python3 tools/pcs_verify_many_bench.py [--out FILE] [--quick] [--shapes fib,w64,w2633]
+  --mixed  the mixed-height verifier (PcsVerifier with a log height per matrix; proofs from TwoAdicFriPcs(mixed_heights=True); the host
+           column is p3hip_pcs_verify_mixed) at n = 64 on two shapes, into profiles/pcs_verify_many_mixed_bench.txt:
+           mixed  the fib-like shape with a second table eight times shorter: round 0 holds 2^20 x 2 and 2^17 x 2, both at two
+                  slots, round 1 holds 2^20 x 4 at one;
+           tall   the same with both tables at 2^20: what the shorter table saves and what its roll-in costs."""
 import argparse
 import csv
 import ctypes as C
@@ -29,7 +34,10 @@ from __graft_entry__ import load_package  # noqa: E402
 P = 0x78000001
 HASH, FRI = "poseidon2", (1, 0, 100, 16)
 # name -> (log_h, widths per round, slots per matrix per round)
-SHAPES = {"fib": (20, [[2], [4]], [[[0, 1]], [[0]]]), "w64": (20, [[64]], [[[0]]]), "w2633": (16, [[2633]], [[[0, 1]]])}
+SHAPES = {"fib": (20, [[2], [4]], [[[0, 1]], [[0]]]), "w64": (20, [[64]], [[[0]]]), "w2633": (16, [[2633]], [[[0, 1]]]),
+          # log_h as per-matrix lists: the mixed entries
+          "mixed": ([[20, 17], [20]], [[2, 2], [4]], [[[0, 1], [0, 1]], [[0]]]), "tall": ([[20, 20], [20]], [[2, 2], [4]], [[[0, 1], [0, 1]], [[0]]])}
+MIXED_SHAPES = ("mixed", "tall")
 DISTINCT = 4  # distinct members; larger batches repeat them (the verifier's work does not depend on which member it is)
 FIB_DEVICE_MS_N64 = 0.559  # profiles/verify_many_bench.txt, cfg2, device n = 64
 
@@ -44,13 +52,15 @@ def make_members(p3, name):
     log_h, widths, slots = SHAPES[name]
     rng = np.random.default_rng(len(name))
     n_slots = 1 + max(s for rs in slots for ms in rs for s in ms)
-    pcs = p3.TwoAdicFriPcs(p3.FriParameters(*FRI), HASH)
+    lists = not isinstance(log_h, int)
+    heights = log_h if lists else [[log_h] * len(ws) for ws in widths]
+    pcs = p3.TwoAdicFriPcs(p3.FriParameters(*FRI), HASH, mixed_heights=lists)
     out = []
     for _ in range(DISTINCT):
         pts = monty(rng.integers(0, P, (n_slots, 4), dtype=np.uint64))
         rounds, roots = [], []
-        for ws, ss in zip(widths, slots):
-            mats = [(torch.randint(0, P, (1 << log_h, w), dtype=torch.int32, device="cuda"), None) for w in ws]
+        for ws, ss, hs in zip(widths, slots, heights):
+            mats = [(torch.randint(0, P, (1 << lh, w), dtype=torch.int32, device="cuda"), None) for w, lh in zip(ws, hs)]
             root, data = pcs.commit(mats)
             rounds.append((data, [[pts[s] for s in ms] for ms in ss]))
             roots.append(root)
@@ -82,6 +92,11 @@ def host_rate(p3, name, members, threads, seconds):
     cw = (C.c_size_t * len(flat_w))(*flat_w)
     counts = [len(ms) for ss in slots for ms in ss]
     cc = (C.c_size_t * len(counts))(*counts)
+    lists = not isinstance(log_h, int)
+    entry = lib.p3hip_pcs_verify_mixed if lists else lib.p3hip_pcs_verify
+    if lists:
+        flat_h = [lh for hs in log_h for lh in hs]
+        log_h = (C.c_uint * len(flat_h))(*flat_h)
     prepared = []
     for m in members:
         pts = np.ascontiguousarray(np.concatenate([m["points"][s] for ss in slots for ms in ss for s in ms]))
@@ -98,7 +113,7 @@ def host_rate(p3, name, members, threads, seconds):
             roots, pts, opened, buf, ln, ch = prepared[k % len(prepared)]
             c, code = C.c_void_p(), C.c_int()
             assert lib.p3hip_challenger_clone(ch._h, C.byref(c)) == 0
-            rc = lib.p3hip_pcs_verify(0, params, log_h, roots.ctypes.data_as(C.c_void_p), mats, cw, len(widths), cc, pts.ctypes.data_as(C.c_void_p),
+            rc = entry(0, params, log_h, roots.ctypes.data_as(C.c_void_p), mats, cw, len(widths), cc, pts.ctypes.data_as(C.c_void_p),
                                       opened.ctypes.data_as(C.c_void_p), buf, ln, c, C.byref(code))
             lib.p3hip_challenger_destroy(c)
             assert rc == 0 and code.value == 0, (rc, code.value)
@@ -205,9 +220,10 @@ def kernel_split(name, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pcs_verify_many_bench.txt"))
+    ap.add_argument("--out")
+    ap.add_argument("--mixed", action="store_true", help="the mixed-height shapes at n = 64")
     ap.add_argument("--quick", action="store_true", help="n = 1, 8, 64 only and shorter host timing")
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--shapes")
     ap.add_argument("--trace-workload")
     ap.add_argument("--trace-n", type=int, default=64)
     a = ap.parse_args()
@@ -215,11 +231,17 @@ def main():
     if a.trace_workload:
         trace_workload(p3, a.trace_workload, a.trace_n)
         return
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles", "pcs_verify_many_mixed_bench.txt" if a.mixed else "pcs_verify_many_bench.txt")
+    if not a.shapes:
+        a.shapes = ",".join(MIXED_SHAPES if a.mixed else [s for s in SHAPES if s not in MIXED_SHAPES])
     names = [s for s in a.shapes.split(",") if s]
     lines = ["# tools/pcs_verify_many_bench.py: host PCS verifier against the device batch verifier, one box, one run.",
              "# %s, FRI (log_blowup, log_final_poly_len, queries, pow bits) = %s; host threads are Python threads around the C entry" % (HASH, FRI,),
              "# (the interpreter lock is released for the call).  device = HIP events around the device entry's launches, members resident;",
              "# e2e = the host entry: upload + verify + download, wall clock.  Medians."]
+    if a.mixed:
+        lines.append("# --mixed: a log height per matrix (p3hip_pcs_verifier_create_mixed); the host verifier is p3hip_pcs_verify_mixed.")
     splits = {name: kernel_split(name, 64) for name in names}  # the traced children first: this process has not opened the GPU yet
     verdict = []
     for name in names:
@@ -229,10 +251,10 @@ def main():
         h1 = host_rate(p3, name, members, 1, secs)
         h16 = host_rate(p3, name, members, 16, secs)
         total = sum(w * len(ms) for ws, ss in zip(widths, slots) for w, ms in zip(ws, ss))
-        lines += ["", "%s: 2^%d rows, widths %s, %d batched columns, proof %d bytes" % (name, log_h, widths, total, len(members[0]["proof"])),
+        lines += ["", "%s: 2^%s rows, widths %s, %d batched columns, proof %d bytes" % (name, log_h, widths, total, len(members[0]["proof"])),
                   "  host verifier    1 thread  %9.1f members/s  (%.2f ms per member)" % (h1, 1e3 / h1),
                   "  host verifier   16 threads %9.1f members/s" % h16]
-        for n in (1, 8, 64) if a.quick else (1, 8, 64, 512):
+        for n in (64,) if a.mixed else (1, 8, 64) if a.quick else (1, 8, 64, 512):
             dev_ms, e2e_ms, wave = device_rates(p3, name, members, n, 10 if n < 512 else 6)
             lines.append("  device n = %-4d  device %9.3f ms = %9.1f members/s    e2e %9.3f ms = %9.1f members/s" %
                          (n, dev_ms, n / dev_ms * 1e3, e2e_ms, n / e2e_ms * 1e3))
