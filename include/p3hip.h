@@ -647,6 +647,80 @@ int p3hip_pcs_verifier_create_mixed(int hash, int hiding, const p3hip_fri_params
 int p3hip_pcs_verifier_wave_form(const p3hip_pcs_verifier_t *v);
 void p3hip_pcs_verifier_destroy(p3hip_pcs_verifier_t *v);
 
+/* ---- caller-defined AIRs: the step of p3_uni_stark::prove between commit(trace) and commit(quotient) — quotient_values — and
+ *      check_constraints, for an AIR the caller describes as a small PROGRAM; with the PCS and the challenger above this is every piece
+ *      of prove(&config, &air, trace, &pis) / verify for an `air` of the caller's (plonky3-mobile_amd/air.py prove_air / verify_air
+ *      compose them).  DESIGN.md section 5.3.
+ *      The trace is a base-field matrix of `width` columns with `n_public` public values.  A program is a flat list of instructions
+ *      of FOUR uint32_t each, {op, dst, a, b}:
+ *        op  P3HIP_AIR_OP_ADD / _SUB / _MUL: slot[dst] = a op b;  P3HIP_AIR_OP_ASSERT_ZERO: constraint number k (k counts the
+ *            assertions in program order) is `a`; its dst and b words are 0
+ *        dst a value slot, < P3HIP_AIR_MAX_SLOTS
+ *        a, b operands: kind << P3HIP_AIR_KIND_SHIFT | index, kind one of P3HIP_AIR_KIND_SLOT (index: a slot some EARLIER instruction
+ *            wrote), _LOCAL / _NEXT (a column of the row / of the next row), _PUBLIC (a public value), _CONST (an entry of `consts`,
+ *            Montgomery words), _SELECTOR (P3HIP_AIR_SEL_FIRST_ROW / _LAST_ROW / _TRANSITION)
+ *      Degrees as upstream's SymbolicExpression: columns and selectors 1, publics and constants 0, add / sub the maximum, mul the
+ *      sum; log_quotient_degree = log2_ceil(max(d, 2) - 1) with d the largest constraint degree.
+ *      p3hip_air_create validates the WHOLE program and refuses, with P3HIP_ERR_BAD_ARG and a message naming the instruction: a column,
+ *      public, constant, selector or slot index out of range, a slot read before any instruction wrote it, an unknown opcode or kind,
+ *      zero constraints, a capacity exceeded.  After creation no index of the caller's is checked again: the kernels take no load
+ *      address and no loop bound that creation has not validated.  CAPACITIES: ---- */
+#define P3HIP_AIR_MAX_INSTRUCTIONS 65536
+#define P3HIP_AIR_MAX_CONSTRAINTS 4096
+#define P3HIP_AIR_MAX_SLOTS 64 /* 1 KiB of LDS each per workgroup of 256 rows: two workgroups fit a CU's 160 KiB */
+#define P3HIP_AIR_MAX_WIDTH 8192
+#define P3HIP_AIR_MAX_PUBLIC 4096
+#define P3HIP_AIR_MAX_CONSTS 65536
+#define P3HIP_AIR_MAX_DEGREE 9 /* of a constraint: at most 8 quotient chunks, what one commitment holds */
+#define P3HIP_AIR_MAX_LOG_QUOTIENT_DEGREE 3
+#define P3HIP_AIR_OP_ADD 0u
+#define P3HIP_AIR_OP_SUB 1u
+#define P3HIP_AIR_OP_MUL 2u
+#define P3HIP_AIR_OP_ASSERT_ZERO 3u
+#define P3HIP_AIR_KIND_SHIFT 24
+#define P3HIP_AIR_KIND_SLOT 0u
+#define P3HIP_AIR_KIND_LOCAL 1u
+#define P3HIP_AIR_KIND_NEXT 2u
+#define P3HIP_AIR_KIND_PUBLIC 3u
+#define P3HIP_AIR_KIND_CONST 4u
+#define P3HIP_AIR_KIND_SELECTOR 5u
+#define P3HIP_AIR_SEL_FIRST_ROW 0u
+#define P3HIP_AIR_SEL_LAST_ROW 1u
+#define P3HIP_AIR_SEL_TRANSITION 2u
+typedef struct p3hip_air p3hip_air_t;
+typedef struct {
+    uint32_t width, n_public, n_instructions;
+    uint32_t n_constraints, n_slots /* highest slot written + 1 */, max_degree, log_quotient_degree;
+} p3hip_air_info_t;
+/* an Air (p3_air::Air::eval recorded as a program); host code, no GPU touched: the device copy is made by the first device call, on
+ * that call's current device, which the object then belongs to: a later call makes that device current for its duration */
+int p3hip_air_create(size_t width, size_t n_public, const uint32_t *code /* 4 words per instruction */, size_t n_instr,
+                     const uint32_t *consts /* Montgomery */, size_t n_consts, p3hip_air_t **out);
+void p3hip_air_destroy(p3hip_air_t *air);
+int p3hip_air_info(const p3hip_air_t *air, p3hip_air_info_t *out);
+/* p3_uni_stark::quotient_values.  d_lde: the committed trace LDE as p3hip_pcs_lde_dev hands it out ((2^log_n << log_blowup) rows of
+ * `width` words on GENERATOR * <g_big>, bit-reversed; read in place).  With C = 2^log_quotient_degree and qn = 2^log_n * C the quotient
+ * domain GENERATOR * <g_qn> is the LDE's first qn rows: natural row i is LDE row bitrev(i, log qn), its next row is natural row (i + C)
+ * mod qn, x_i = GENERATOR g_qn^i; selectors are selectors_on_coset (Z_H = x^n - 1, is_first_row = Z_H / (x - 1), is_last_row = Z_H / (x -
+ * g_n^-1), is_transition = x - g_n^-1).  The quotient (sum_k alpha^(K-1-k) c_k(i)) / Z_H(x_i), four words, goes to C dense n x 4
+ * matrices: d_chunks_out[c] row r = natural row r C + c (16-byte aligned device pointers in a HOST array; chunk c is committed with
+ * domain shift GENERATOR g_qn^c).  pis: n_public Montgomery words, host memory.  log_blowup < log_quotient_degree is refused by name.
+ * Enqueues on `stream` (one small upload and one launch; the first call at a log qn also builds that domain's root table) and does
+ * not synchronise.  The per-call table (publics, alpha powers, chunk pointers) is the object's: calls on ONE Air go to one stream, where
+ * they may follow each other without a synchronisation (the upload reads pinned staging that a later call rewrites only after an
+ * event behind the earlier upload); calls on one Air from two streams at once are not supported. */
+int p3hip_air_quotient_dev(p3hip_air_t *air, void *stream, const uint32_t *d_lde, unsigned log_n, unsigned log_blowup, const uint32_t *pis,
+                           const uint32_t alpha[4], uint32_t *const *d_chunks_out);
+/* p3_uni_stark::check_constraints (debug builds of prove): the same program over the trace itself, d_trace 2^log_n rows of `width`
+ * words in natural order; selectors i == 0, i == n - 1, i != n - 1; next is row i + 1 mod n.  *row_out, *constraint_out: the smallest
+ * (row, constraint) whose value is nonzero, or -1, -1.  One pass, one synchronisation. */
+int p3hip_air_check_trace_dev(p3hip_air_t *air, void *stream, const uint32_t *d_trace, unsigned log_n, const uint32_t *pis,
+                              long long *row_out, int *constraint_out);
+/* VerifierConstraintFolder: the program over extension operands, host code.  local, next: width x 4 words; sels: is_first_row,
+ * is_last_row, is_transition at the point, 4 words each; out = sum_k alpha^(K-1-k) c_k by Horner's rule. */
+int p3hip_air_eval_ext(const p3hip_air_t *air, const uint32_t *local, const uint32_t *next, const uint32_t *pis, const uint32_t *sels,
+                       const uint32_t alpha[4], uint32_t out[4]);
+
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */
 typedef int (*p3hip_cpu_dft_fn)(void *user, const uint32_t *in, uint32_t *out, size_t height, size_t width);

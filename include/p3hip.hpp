@@ -512,6 +512,54 @@ class PcsVerifier {
     size_t n_rounds_ = 0, n_slots_ = 0, total_ = 0, proof_len_ = 0;
 };
 
+// A caller-defined AIR as a validated program (p3hip.h "caller-defined AIRs"): the quotient kernel, the trace check and the verifier's
+// evaluation.  code: 4 words per instruction {op, dst, a, b}; operands are air_operand(kind, index).
+inline uint32_t air_operand(uint32_t kind, uint32_t index) { return (kind << P3HIP_AIR_KIND_SHIFT) | index; }
+class Air {
+  public:
+    Air(size_t width, size_t n_public, const std::vector<uint32_t>& code, const std::vector<uint32_t>& consts) {
+        if (code.size() % 4) throw Error(P3HIP_ERR_BAD_ARG, "Air: four words per instruction");
+        check(p3hip_air_create(width, n_public, code.data(), code.size() / 4, consts.data(), consts.size(), &h_));
+        if (p3hip_air_info(h_, &info_) != 0) {
+            p3hip_air_destroy(h_);
+            throw Error(P3HIP_ERR_BAD_ARG, take_last_error());
+        }
+    }
+    Air(const Air&) = delete;
+    Air& operator=(const Air&) = delete;
+    ~Air() { p3hip_air_destroy(h_); }
+    const p3hip_air_info_t& info() const { return info_; }
+    size_t n_chunks() const { return (size_t)1 << info_.log_quotient_degree; }
+    p3hip_air_t* handle() const { return h_; }
+    // quotient_values: d_lde as p3hip_pcs_lde_dev hands it out; d_chunks: n_chunks() device matrices of 2^log_n x 4 words.  Enqueues only.
+    void quotient_dev(void* stream, const uint32_t* d_lde, unsigned log_n, unsigned log_blowup, const std::vector<uint32_t>& pis,
+                      const std::array<uint32_t, 4>& alpha, const std::vector<uint32_t*>& d_chunks) {
+        if (d_chunks.size() != n_chunks() || pis.size() != info_.n_public) throw Error(P3HIP_ERR_BAD_ARG, "Air: n_chunks chunk pointers, n_public public values");
+        check(p3hip_air_quotient_dev(h_, stream, d_lde, log_n, log_blowup, pis.data(), alpha.data(), d_chunks.data()));
+    }
+    // check_constraints over a device trace: {-1, -1} when every constraint holds, else the smallest failing {row, constraint}
+    std::pair<long long, int> check_trace_dev(void* stream, const uint32_t* d_trace, unsigned log_n, const std::vector<uint32_t>& pis) {
+        if (pis.size() != info_.n_public) throw Error(P3HIP_ERR_BAD_ARG, "Air: n_public public values");
+        long long row = -1;
+        int k = -1;
+        check(p3hip_air_check_trace_dev(h_, stream, d_trace, log_n, pis.data(), &row, &k));
+        return {row, k};
+    }
+    // the constraints over extension operands folded by Horner's rule (host): local, next width x 4 words; sels 3 x 4 words
+    std::array<uint32_t, 4> eval_ext(const std::vector<uint32_t>& local, const std::vector<uint32_t>& next, const std::vector<uint32_t>& pis,
+                                     const std::array<uint32_t, 12>& sels, const std::array<uint32_t, 4>& alpha) const {
+        if (local.size() != 4 * (size_t)info_.width || next.size() != local.size() || pis.size() != info_.n_public)
+            throw Error(P3HIP_ERR_BAD_ARG, "Air: width x 4 words per row, n_public public values");
+        std::array<uint32_t, 4> out{};
+        check(p3hip_air_eval_ext(h_, local.data(), next.data(), pis.data(), sels.data(), alpha.data(), out.data()));
+        return out;
+    }
+
+  private:
+    p3hip_air_t* h_ = nullptr;
+    p3hip_air_info_t info_{};
+};
+
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"
 inline std::string run_fib_air(unsigned log_n = 3, uint64_t a = 0, uint64_t b = 1, FriParameters fp = FriParameters(),
                                int hash = P3HIP_HASH_POSEIDON2) {

@@ -164,6 +164,12 @@ _SIGS = {
     "p3hip_pcs_verifier_wave_form": (C.c_int, [C.c_void_p]),
     "p3hip_pcs_verifier_destroy": (None, [C.c_void_p]),
     "p3hip_pcs_data_free": (None, [C.c_void_p]),
+    "p3hip_air_create": (C.c_int, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "p3hip_air_destroy": (None, [C.c_void_p]),
+    "p3hip_air_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "p3hip_air_quotient_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "p3hip_air_check_trace_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "p3hip_air_eval_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3hip_pcs_destroy": (None, [C.c_void_p]),
 }
 

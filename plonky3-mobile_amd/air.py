@@ -1,0 +1,532 @@
+"""Caller-defined AIRs (include/p3hip.h "caller-defined AIRs"): AirBuilder, shaped after p3_air::AirBuilder, records an AIR's
+constraints as an expression DAG and compiles it to the library's instruction list; Air owns the validated program and runs it —
+quotient_values and check_constraints on the device, the verifier's evaluation on the host; prove_air / verify_air are
+p3_uni_stark::prove / verify over a non-hiding TwoAdicFriPcs and a Challenger.  Field elements are Montgomery words unless said
+otherwise.  There is no CPU path for the device steps."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .gpu_dft import P, _is_torch, _stream_ptr, dev_u32
+from .pcs import Challenger, PcsRejected, _words
+
+# include/p3hip.h P3HIP_AIR_*
+OP_ADD, OP_SUB, OP_MUL, OP_ASSERT_ZERO = 0, 1, 2, 3
+KIND_SHIFT = 24
+KIND_SLOT, KIND_LOCAL, KIND_NEXT, KIND_PUBLIC, KIND_CONST, KIND_SELECTOR = range(6)
+SEL_FIRST_ROW, SEL_LAST_ROW, SEL_TRANSITION = 0, 1, 2
+MAX_INSTRUCTIONS, MAX_CONSTRAINTS, MAX_SLOTS, MAX_WIDTH, MAX_PUBLIC, MAX_CONSTS, MAX_DEGREE = 65536, 4096, 64, 8192, 4096, 65536, 9
+PROOF_MAGIC = 0x42463350
+OOD_EVALUATION_MISMATCH = 10
+
+_R = (1 << 32) % P
+_RINV = pow(_R, P - 2, P)
+
+
+def to_monty(v):
+    return (int(v) % P) * _R % P
+
+
+def from_monty(w):
+    return int(w) * _RINV % P
+
+
+def two_adic_generator(bits):
+    """(31^15)^(2^(27 - bits)), a Montgomery word"""
+    return to_monty(pow(pow(31, 15, P), 1 << (27 - bits), P))
+
+
+def operand(kind, index):
+    return (kind << KIND_SHIFT) | index
+
+
+# ---- expressions ----
+class Expr:
+    """A node of an AirBuilder's DAG.  + - * take expressions or canonical integers."""
+    __slots__ = ("b", "id")
+
+    def __init__(self, builder, node_id):
+        self.b, self.id = builder, node_id
+
+    def _lift(self, other):
+        if isinstance(other, Expr):
+            if other.b is not self.b:
+                raise ValueError("expressions of two builders")
+            return other
+        return self.b.const(other)
+
+    def __add__(self, o):
+        return self.b._binary(OP_ADD, self, self._lift(o))
+
+    def __radd__(self, o):
+        return self.b._binary(OP_ADD, self._lift(o), self)
+
+    def __sub__(self, o):
+        return self.b._binary(OP_SUB, self, self._lift(o))
+
+    def __rsub__(self, o):
+        return self.b._binary(OP_SUB, self._lift(o), self)
+
+    def __mul__(self, o):
+        return self.b._binary(OP_MUL, self, self._lift(o))
+
+    def __rmul__(self, o):
+        return self.b._binary(OP_MUL, self._lift(o), self)
+
+    def __neg__(self):
+        return self.b._binary(OP_SUB, self.b.const(0), self)
+
+
+class _Filtered:
+    """p3_air::FilteredAirBuilder: every assertion is multiplied by the condition."""
+
+    def __init__(self, builder, condition):
+        self._b, self._c = builder, condition
+
+    def assert_zero(self, e):
+        self._b.assert_zero(self._c * e)
+
+    def assert_eq(self, a, b):
+        self.assert_zero(self._b._expr(a) - b)
+
+
+class AirBuilder:
+    """Records constraints over a base-field trace of `width` columns with `n_public` public values; build() gives the Air."""
+
+    def __init__(self, width, n_public=0):
+        self.width, self.n_public = int(width), int(n_public)
+        self._nodes, self._ids, self._asserts = [], {}, []  # node: (kind, index) for a leaf, (op, a id, b id) otherwise
+        self._consts, self._const_ids = [], {}
+
+    def _leaf(self, kind, index):
+        return self._node(("leaf", kind, index))
+
+    def _node(self, key):
+        i = self._ids.get(key)
+        if i is None:
+            i = self._ids[key] = len(self._nodes)
+            self._nodes.append(key)
+        return Expr(self, i)
+
+    def _binary(self, op, a, b):
+        ia, ib = a.id, b.id
+        if op != OP_SUB and ia > ib:  # a + b and b + a are one node
+            ia, ib = ib, ia
+        return self._node(("op", op, ia, ib))
+
+    def _expr(self, e):
+        return e if isinstance(e, Expr) else self.const(e)
+
+    def local(self, c):
+        if not 0 <= c < self.width:
+            raise IndexError("column %d of a trace of width %d" % (c, self.width))
+        return self._leaf(KIND_LOCAL, int(c))
+
+    def next(self, c):
+        if not 0 <= c < self.width:
+            raise IndexError("column %d of a trace of width %d" % (c, self.width))
+        return self._leaf(KIND_NEXT, int(c))
+
+    def public(self, i):
+        if not 0 <= i < self.n_public:
+            raise IndexError("public value %d of %d" % (i, self.n_public))
+        return self._leaf(KIND_PUBLIC, int(i))
+
+    def const(self, v):
+        """a constant from a canonical integer (taken mod P)"""
+        w = to_monty(v)
+        i = self._const_ids.get(w)
+        if i is None:
+            i = self._const_ids[w] = len(self._consts)
+            self._consts.append(w)
+        return self._leaf(KIND_CONST, i)
+
+    @property
+    def is_first_row(self):
+        return self._leaf(KIND_SELECTOR, SEL_FIRST_ROW)
+
+    @property
+    def is_last_row(self):
+        return self._leaf(KIND_SELECTOR, SEL_LAST_ROW)
+
+    @property
+    def is_transition(self):
+        return self._leaf(KIND_SELECTOR, SEL_TRANSITION)
+
+    def assert_zero(self, e):
+        self._asserts.append(self._expr(e).id)
+
+    def assert_eq(self, a, b):
+        self.assert_zero(self._expr(a) - b)
+
+    def when_first_row(self):
+        return _Filtered(self, self.is_first_row)
+
+    def when_last_row(self):
+        return _Filtered(self, self.is_last_row)
+
+    def when_transition(self):
+        return _Filtered(self, self.is_transition)
+
+    def compile(self):
+        """-> (code as numpy uint32 (n, 4), consts as numpy uint32).  Every DAG node is emitted once, in the order the constraints
+        first need it; a slot is handed back after its value's last use and taken again by a later instruction."""
+        nodes = self._nodes
+        order, seen = [], set()  # ("op", node) | ("assert", node)
+        for root in self._asserts:
+            stack = [(root, False)]
+            while stack:  # post-order without recursion: a chain may be thousands of nodes deep
+                v, done = stack.pop()
+                if nodes[v][0] == "leaf" or (v in seen and not done):
+                    continue
+                if done:
+                    order.append(("op", v))
+                    continue
+                seen.add(v)
+                stack.append((v, True))
+                stack.append((nodes[v][3], False))
+                stack.append((nodes[v][2], False))
+            order.append(("assert", root))
+        last_use = {}
+        for pos, (what, v) in enumerate(order):
+            for u in ([v] if what == "assert" else nodes[v][2:4]):
+                last_use[u] = pos
+        slot_of, free, n_slots, code = {}, [], 0, []
+
+        def opnd(u):
+            if nodes[u][0] == "leaf":
+                return operand(nodes[u][1], nodes[u][2])
+            return operand(KIND_SLOT, slot_of[u])
+
+        def release(u, pos):
+            if nodes[u][0] == "op" and last_use[u] == pos and u in slot_of:
+                free.append(slot_of.pop(u))
+
+        for pos, (what, v) in enumerate(order):
+            if what == "assert":
+                code.append((OP_ASSERT_ZERO, 0, opnd(v), 0))
+                release(v, pos)
+                continue
+            _, op, a, b = nodes[v]
+            oa, ob = opnd(a), opnd(b)
+            release(a, pos)
+            release(b, pos)  # dst may be an operand's slot: a lane reads both operands before it writes
+            if v in last_use:
+                if free:
+                    s = min(free)
+                    free.remove(s)
+                else:
+                    s, n_slots = n_slots, n_slots + 1
+                slot_of[v] = s
+                code.append((op, s, oa, ob))
+        return np.array(code, dtype=np.uint32).reshape(-1, 4), np.array(self._consts, dtype=np.uint32)
+
+    def build(self):
+        code, consts = self.compile()
+        return Air(self.width, self.n_public, code, consts)
+
+
+class _Info(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "n_public", "n_instructions", "n_constraints", "n_slots", "max_degree", "log_quotient_degree")]
+
+
+class Air:
+    """A validated AIR program (p3hip_air_create; refusals raise P3HipError(-1) naming the instruction).  Owns the handle."""
+
+    def __init__(self, width, n_public, code, consts):
+        self.code = np.ascontiguousarray(code, dtype=np.uint32).reshape(-1, 4)
+        self.consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p3hip_air_create(int(width), int(n_public), self.code.ctypes.data_as(C.c_void_p), len(self.code),
+                                               self.consts.ctypes.data_as(C.c_void_p), self.consts.size, C.byref(self._h)))
+        info = _Info()
+        _lib.check(_lib.lib().p3hip_air_info(self._h, C.byref(info)))
+        self.width, self.n_public, self.n_instructions = info.width, info.n_public, info.n_instructions
+        self.n_constraints, self.n_slots, self.max_degree = info.n_constraints, info.n_slots, info.max_degree
+        self.log_quotient_degree = info.log_quotient_degree
+
+    @property
+    def n_chunks(self):
+        return 1 << self.log_quotient_degree
+
+    def _pis(self, pis):
+        p = _words(pis if pis is not None else [], self.n_public)
+        return p, (p.ctypes.data_as(C.c_void_p) if p.size else None)
+
+    def quotient(self, lde, log_n, log_blowup, pis, alpha):
+        """quotient_values: lde the committed trace LDE (TwoAdicFriPcs.get_evaluations_on_domain, any number of its rows from
+        2^(log_n + log_quotient_degree) on; read in place) -> the n_chunks chunk matrices, (2^log_n, 4) int32 device tensors; chunk
+        c is committed with domain shift GENERATOR g_qn^c.  Enqueued on torch's current stream, not synchronised."""
+        import torch
+        if not (lde.is_cuda and lde.is_contiguous() and lde.element_size() == 4 and lde.dim() == 2 and lde.shape[1] == self.width):
+            raise ValueError("quotient: a contiguous (rows, width) device matrix of 32-bit words")
+        if lde.shape[0] < (1 << (log_n + self.log_quotient_degree)):
+            raise ValueError("quotient: the LDE holds fewer rows than the quotient domain")
+        p, pp = self._pis(pis)
+        al = _words(alpha, 4)
+        chunks = [torch.empty((1 << log_n, 4), dtype=torch.int32, device=lde.device) for _ in range(self.n_chunks)]
+        ptrs = (C.c_void_p * self.n_chunks)(*[c.data_ptr() for c in chunks])
+        _lib.check(_lib.lib().p3hip_air_quotient_dev(self._h, _stream_ptr(), C.c_void_p(lde.data_ptr()), log_n, log_blowup, pp,
+                                                     al.ctypes.data_as(C.c_void_p), ptrs))
+        return chunks
+
+    def check_trace(self, trace, pis=None):
+        """check_constraints: trace a (2^log_n, width) device tensor (read in place) or numpy array (uploaded) -> None when every
+        constraint holds on every row, else the smallest failing (row, constraint)."""
+        t = trace.contiguous() if _is_torch(trace) else dev_u32(trace)
+        h = int(t.shape[0]) if t.dim() == 2 else 0
+        if t.dim() != 2 or t.element_size() != 4 or not t.is_cuda or t.shape[1] != self.width or h < 2 or h & (h - 1):
+            raise ValueError("check_trace: a (2^log_n, width) matrix of 32-bit words, log_n >= 1")
+        p, pp = self._pis(pis)
+        row, k = C.c_longlong(), C.c_int()
+        _lib.check(_lib.lib().p3hip_air_check_trace_dev(self._h, _stream_ptr(), C.c_void_p(t.data_ptr()), h.bit_length() - 1, pp,
+                                                        C.byref(row), C.byref(k)))
+        return None if row.value < 0 else (row.value, k.value)
+
+    def eval_ext(self, local, next, pis, sels, alpha):
+        """The constraints at a point, folded by Horner's rule (host): local, next (width, 4); sels (3, 4): is_first_row,
+        is_last_row, is_transition -> 4 words."""
+        lo, nx = _words(local, 4 * self.width), _words(next, 4 * self.width)
+        p, pp = self._pis(pis)
+        s, al, out = _words(sels, 12), _words(alpha, 4), np.zeros(4, dtype=np.uint32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(_lib.lib().p3hip_air_eval_ext(self._h, vp(lo), vp(nx), pp, vp(s), vp(al), vp(out)))
+        return out
+
+    def free(self):
+        if self._h:
+            _lib.lib().p3hip_air_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def fibonacci_air():
+    """FibonacciAir (native/src/fib_air.rs:224-264): columns (left, right), publics (a, b, x); five constraints."""
+    b = AirBuilder(2, 3)
+    left, right, nleft, nright = b.local(0), b.local(1), b.next(0), b.next(1)
+    first = b.when_first_row()
+    first.assert_eq(left, b.public(0))
+    first.assert_eq(right, b.public(1))
+    trans = b.when_transition()
+    trans.assert_eq(right, nleft)
+    trans.assert_eq(left + right, nright)
+    b.when_last_row().assert_eq(right, b.public(2))
+    return b.build()
+
+
+# ---- extension field on the host (canonical integers; x^4 = 11): the few operations verify_air needs ----
+def _emul(a, b):
+    out = [0, 0, 0, 0]
+    for i in range(4):
+        for j in range(4):
+            t = a[i] * b[j]
+            out[(i + j) & 3] += t * 11 if i + j >= 4 else t
+    return [v % P for v in out]
+
+
+def _eadd(a, b):
+    return [(x + y) % P for x, y in zip(a, b)]
+
+
+def _esub(a, b):
+    return [(x - y) % P for x, y in zip(a, b)]
+
+
+def _base(v):
+    return [v % P, 0, 0, 0]
+
+
+def _epow(a, e):
+    r = _base(1)
+    while e:
+        if e & 1:
+            r = _emul(r, a)
+        a = _emul(a, a)
+        e >>= 1
+    return r
+
+
+def _einv(a):
+    conj = [a[0], -a[1] % P, a[2], -a[3] % P]
+    n = _emul(a, conj)  # c + d x^2
+    c, d = n[0], n[2]
+    di = pow((c * c - 11 * d * d) % P, P - 2, P)
+    return _emul(conj, [c * di % P, 0, -d * di % P, 0])
+
+
+def _canon(words):
+    return [from_monty(w) for w in words]
+
+
+def _monty(vals):
+    return np.array([to_monty(v) for v in vals], dtype=np.uint32)
+
+
+# ---- p3_uni_stark::prove / verify ----
+def _prefix(ch, log_n, root_t, pis):
+    m = to_monty(log_n)
+    ch.observe([m, m])  # log_ext_degree, log_degree
+    ch.observe_digest(root_t)
+    if len(pis):
+        ch.observe(pis)
+    return ch.sample_ext()
+
+
+def chunk_shifts(log_n, log_quotient_degree):
+    """the domain shift of every quotient chunk: GENERATOR g_qn^c"""
+    g, s, out = from_monty(two_adic_generator(log_n + log_quotient_degree)), 31, []
+    for _ in range(1 << log_quotient_degree):
+        out.append(to_monty(s))
+        s = s * g % P
+    return out
+
+
+def prove_air(air, pcs, trace, pis=None):
+    """p3_uni_stark::prove(&config, &air, trace, &pis) over a non-hiding TwoAdicFriPcs: trace a (2^log_n, width) device tensor
+    (committed where it lies) or numpy array.  Returns the proof bytes: the header (magic, 1, log_n, the two roots, width and the
+    local values, width and the next values, the chunk count and per chunk 4 and its values), then the PCS's FriProof bytes.  The
+    host drives the challenger, so the call synchronises a few times (two commits, the open)."""
+    if getattr(pcs, "_hiding", False):
+        raise ValueError("prove_air: a non-hiding TwoAdicFriPcs")
+    pis = _words(pis if pis is not None else [], air.n_public)
+    h, w = (int(v) for v in trace.shape)
+    log_n = h.bit_length() - 1
+    if w != air.width or h < 2 or h & (h - 1):
+        raise ValueError("prove_air: a (2^log_n, %d) trace, log_n >= 1" % air.width)
+    lqd = air.log_quotient_degree
+    if pcs.params.log_blowup < lqd:
+        raise ValueError("prove_air: log_blowup %d is below the AIR's log_quotient_degree %d" % (pcs.params.log_blowup, lqd))
+    root_t, data_t = pcs.commit([(trace, None)])
+    ch, data_q = Challenger(pcs.hash), None
+    try:  # the trees and LDEs go back to the device whatever happens below
+        alpha = _prefix(ch, log_n, root_t, pis)
+        lde = pcs.get_evaluations_on_domain(data_t, 0, log_n + lqd)
+        chunks = air.quotient(lde, log_n, pcs.params.log_blowup, pis, alpha)
+        root_q, data_q = pcs.commit(list(zip(chunks, chunk_shifts(log_n, lqd))))
+        ch.observe_digest(root_q)
+        zeta = ch.sample_ext()
+        g_n = from_monty(two_adic_generator(log_n))
+        zeta_next = _monty([v * g_n for v in _canon(zeta)])
+        opened, fri = pcs.open([(data_t, [[zeta, zeta_next]]), (data_q, [[zeta]] * len(chunks))], ch)
+    finally:
+        data_t.free()
+        if data_q is not None:
+            data_q.free()
+        ch.free()
+    u = lambda *v: np.array(v, dtype=np.uint32)
+    o = opened.reshape(-1)
+    head = [u(PROOF_MAGIC, 1, log_n), root_t, root_q, u(w), o[:4 * w], u(w), o[4 * w:8 * w], u(len(chunks))]
+    for c in range(len(chunks)):
+        head += [u(4), o[8 * w + 16 * c:8 * w + 16 * (c + 1)]]
+    return np.concatenate(head).astype(np.uint32).tobytes() + fri
+
+
+class AirRejected(_lib.P3HipError):
+    """verify_air refused the proof: .code 1 magic / version, 2 log_n, 3 a count that is not the AIR's, 4 truncated or a word that is
+    no field element, 10 OodEvaluationMismatch, or the PCS verifier's code (include/p3hip.h p3hip_pcs_verify)."""
+
+
+def verify_air(air, proof, pis, log_n, params, hash="poseidon2"):
+    """p3_uni_stark::verify for a proof of prove_air, host code.  Every count in the header is compared with the AIR's own; none is
+    followed.  Returns None on accept, raises AirRejected otherwise."""
+    from . import pcs as _pcs
+    pis = _words(pis if pis is not None else [], air.n_public)
+    w, lqd = air.width, air.log_quotient_degree
+    if not isinstance(log_n, (int, np.integer)) or not 1 <= log_n <= 27 - lqd:
+        raise ValueError("verify_air: log_n must lie in 1..%d for this AIR (the quotient domain has 2^(log_n + %d) points)" % (27 - lqd, lqd))
+    n_chunks = 1 << lqd
+    words = np.frombuffer(bytes(proof[:len(proof) // 4 * 4]), dtype=np.uint32)
+    head_len = 3 + 16 + (1 + 4 * w) * 2 + 1 + 17 * n_chunks
+    pos, bad = [0], [False]
+
+    def u32():  # past the end: no count and no version is -1
+        pos[0] += 1
+        if pos[0] > len(words):
+            bad[0] = True
+            return -1
+        return int(words[pos[0] - 1])
+
+    def take(n):
+        out = np.zeros(n, dtype=np.uint32)
+        got = words[pos[0]:pos[0] + n]
+        out[:len(got)] = got
+        bad[0] |= len(got) < n
+        pos[0] += n
+        return out
+
+    def reject(code, msg):
+        raise AirRejected(code, msg)
+
+    if u32() != PROOF_MAGIC or u32() != 1:
+        reject(1, "bad magic or version")
+    if u32() != log_n:
+        reject(2, "log_n differs")
+    root_t, root_q = take(8), take(8)
+    if u32() != w:
+        reject(3, "local values: the count is not the AIR's width")
+    local = take(4 * w)
+    if u32() != w:
+        reject(3, "next values: the count is not the AIR's width")
+    nxt = take(4 * w)
+    if u32() != n_chunks:
+        reject(3, "quotient chunks: the count is not the AIR's")
+    chunks = []
+    for c in range(n_chunks):
+        if u32() != 4:
+            reject(3, "quotient chunk %d: the width is not 4" % c)
+        chunks.append(take(16))
+    if bad[0]:
+        reject(4, "truncated header")
+    opened = np.concatenate([local, nxt] + chunks)
+    if np.any(opened >= P) or (hash == "poseidon2" and (np.any(root_t >= P) or np.any(root_q >= P))):
+        reject(4, "a header word is not a canonical field element")
+    ch = Challenger(hash)
+    alpha = _prefix(ch, log_n, root_t, pis)
+    ch.observe_digest(root_q)
+    zeta = ch.sample_ext()
+    z = _canon(zeta)
+    n = 1 << log_n
+    g_n = from_monty(two_adic_generator(log_n))
+    ginv = pow(g_n, P - 2, P)
+    zeta_next = _monty([v * g_n for v in z])
+    # selectors_at_point on the trace domain
+    zh = _esub(_epow(z, n), _base(1))
+    first = _emul(zh, _einv(_esub(z, _base(1))))
+    last = _emul(zh, _einv(_esub(z, _base(ginv))))
+    trans = _esub(z, _base(ginv))
+    sels = np.concatenate([_monty(first), _monty(last), _monty(trans)])
+    folded = _canon(air.eval_ext(local, nxt, pis, sels, alpha))
+    # quotient(zeta) = sum_c zps_c sum_e X^e chunk_c[e], zps_c = prod_{j != c} Z_{D_j}(zeta) / Z_{D_j}(s_c), D_j = s_j <g_n>
+    shifts = [from_monty(s) for s in chunk_shifts(log_n, lqd)]
+    zn = _epow(z, n)
+    quot = [0, 0, 0, 0]
+    for c in range(n_chunks):
+        zps = _base(1)
+        for j in range(n_chunks):
+            if j != c:
+                sjn_inv = pow(pow(shifts[j], n, P), P - 2, P)
+                num = _esub([v * sjn_inv % P for v in zn], _base(1))  # Z_{D_j}(x) = (x / s_j)^n - 1
+                den = (pow(shifts[c], n, P) * sjn_inv - 1) % P
+                zps = _emul(zps, [v * pow(den, P - 2, P) % P for v in num])
+        ck = _canon(chunks[c])
+        val = [0, 0, 0, 0]
+        for e in range(4):
+            be = [0, 0, 0, 0]
+            be[e] = 1
+            val = _eadd(val, _emul(be, ck[4 * e:4 * e + 4]))
+        quot = _eadd(quot, _emul(zps, val))
+    if folded != _emul(quot, zh):
+        reject(OOD_EVALUATION_MISMATCH, "OodEvaluationMismatch")
+    rounds = [((root_t, [w]), [[zeta, zeta_next]]), ((root_q, [4] * n_chunks), [[zeta]] * n_chunks)]
+    try:
+        _pcs.verify(params, hash, rounds, log_n, opened.reshape(-1, 4), bytes(proof[4 * head_len:]), ch)
+    except PcsRejected as e:
+        raise AirRejected(e.code, e.message)
+    finally:
+        ch.free()
