@@ -21,6 +21,7 @@
 #include "challenger.h"
 #include "common.h"
 #include "keccak.hip.h"
+#include "lane_walk.hip.h"
 #include "mmcs.h"
 #include "poseidon2.hip.h"
 #include "poseidon2_coop.hip.h"
@@ -117,178 +118,60 @@ struct VerifySched {
 };
 static_assert(sizeof(VerifySched) <= 2048, "passed by value in the kernel arguments");
 
-__device__ __forceinline__ void load_digest_v(const uint32_t* p, uint32_t* out8) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    out8[0] = a.x; out8[1] = a.y; out8[2] = a.z; out8[3] = a.w;
-    out8[4] = b.x; out8[5] = b.y; out8[6] = b.z; out8[7] = b.w;
-}
 // status of one opening from what its lanes saw
 __device__ __forceinline__ uint32_t verdict(bool bad_index, bool not_canonical, bool mismatch) {
     return bad_index ? (uint32_t)MMCS_BAD_INDEX : not_canonical ? (uint32_t)MMCS_NOT_CANONICAL : mismatch ? (uint32_t)MMCS_ROOT_MISMATCH : 0u;
 }
-// d_rejected counted per wave: a ballot popcount and one vector atomic from the wave's first lane (lane 0 is active whenever a
-// lane of the wave is: lanes past n are the highest ones)
-__device__ __forceinline__ void count_rejected(bool rejected, uint32_t* d_rejected) {
-    const uint64_t b = __builtin_amdgcn_ballot_w64(rejected);
-    if (d_rejected && b && (threadIdx.x & 63u) == 0u) atomicAdd(d_rejected, (uint32_t)__builtin_popcountll(b));
-}
 
-// (verifier_dev.hip lane_open_mismatch<> restates the two per-lane walks below for ONE height class and 4-byte-aligned paths read out
-// of proof bytes: a fix to the absorb, the reduce after a permutation or the last-block digest form belongs in both files.)
-// ---- per lane, Poseidon2 (fp64) ----
-__global__ void __launch_bounds__(256) verify_lane_p2_kernel(VerifySched a, const uint32_t* indices, uint64_t n, const uint32_t* rows,
-                                                             const uint32_t* paths, uint32_t* status, uint32_t* d_rejected) {
+// ---- per lane: lane_walk.hip.h's injecting walk over the schedule ----
+// The word source: a cursor over one opening's row words, class by class as the walk reaches their levels, segment by segment within a class.
+struct SchedCursor {
+    const VerifySched& a;
+    const uint32_t* row;
+    uint32_t c = 0, seg = 0, off = 0;  // next class; the segment and the offset in it of the next word
+    __device__ __forceinline__ bool has(uint32_t l) const { return c < a.n_classes && a.level[c] == l; }
+    __device__ __forceinline__ uint32_t len(uint32_t) {
+        seg = a.seg_begin[c];
+        off = 0;
+        return a.total[c++];
+    }
+    __device__ __forceinline__ uint32_t word(uint32_t, uint32_t) {
+        while (off >= a.seg_w[seg]) { seg++; off = 0; }
+        return row[a.seg_off[seg] + off++];
+    }
+};
+// sibling loader: the path arrays are 16-byte aligned (mmcs_verify_many checks), a digest is two 16-byte loads
+struct PathDigests {
+    const uint32_t* path;
+    __device__ __forceinline__ void operator()(uint32_t l, uint32_t (&sw)[8]) const {
+        const uint4* q = reinterpret_cast<const uint4*>(path + l * 8);
+        const uint4 x = q[0], y = q[1];
+        sw[0] = x.x; sw[1] = x.y; sw[2] = x.z; sw[3] = x.w;
+        sw[4] = y.x; sw[5] = y.y; sw[6] = y.z; sw[7] = y.w;
+    }
+};
+template <int HASH>
+__device__ __forceinline__ void verify_lane(const VerifySched& a, const uint32_t* indices, uint64_t n, const uint32_t* rows, const uint32_t* paths,
+                                            uint32_t* status, uint32_t* d_rejected) {
     if (gridDim.x <= 512u) P3_LATENCY_BOUND_KERNEL();
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t index = indices[i];
-    const uint32_t* row = rows + i * a.row_words;
-    const uint32_t* path = paths + i * a.depth * 8;
-    const p2f::MagicRegs smk = p2f::magic_regs();
-    uint32_t hi = 0;  // the largest word seen: >= P decides the status
-    double s[16], cur[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) cur[k] = 0.0;
-    uint32_t c = 0;  // next class
-    for (uint32_t l = 0; l <= a.depth; l++) {
-        const bool has = c < a.n_classes && a.level[c] == l;
-        if (has) {  // the class row's sponge, digest left in s[0..8)
-#pragma unroll
-            for (int k = 0; k < 16; k++) s[k] = 0.0;
-            uint32_t seg = a.seg_begin[c], off = 0;
-            const uint32_t total = a.total[c];
-            for (uint32_t k = 0; k < total; k += 8) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    if (k + e < total) {
-                        while (off >= a.seg_w[seg]) { seg++; off = 0; }
-                        const uint32_t w = row[a.seg_off[seg] + off];
-                        hi = max(hi, w);
-                        s[e] = p2f::load_elem(w);
-                        off++;
-                    }
-                }
-                p2f::permute(s);
-#pragma unroll
-                for (int e = 0; e < 16; e++) s[e] = p2f::reduce(s[e]);  // the next permutation assumes |s| <= 2^33
-            }
-            c++;
-        }
-        // up to two compressions through ONE call site: the injected row digest (right operand, never swapped), then the sibling
-        _Pragma("clang loop unroll(disable)")
-        for (uint32_t sub = 0; sub < 2; sub++) {
-            if (sub == 0) {
-                if (l == 0) {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) cur[k] = s[k];
-                }
-                if (!has || l == 0) continue;
-#pragma unroll
-                for (int k = 0; k < 8; k++) { s[8 + k] = s[k]; s[k] = cur[k]; }
-            } else {
-                if (l == a.depth) continue;
-                uint32_t sw[8];
-                load_digest_v(path + l * 8, sw);
-                const bool right = (index >> l) & 1u;  // this opening's node is the right child: the sibling goes left
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    hi = max(hi, sw[k]);
-                    const double sd = p2f::load_elem(sw[k]);
-                    s[k] = right ? sd : cur[k];
-                    s[8 + k] = right ? cur[k] : sd;
-                }
-            }
-            p2f::permute(s);
-#pragma unroll
-            for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
-        }
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != a.root[k];
+    SchedCursor src{a, rows + i * a.row_words};
+    uint32_t hi = 0;  // the largest opened value (Poseidon2: or digest word) seen: >= P decides the status
+    const bool mismatch = lane_walk::walk<HASH, true>(src, PathDigests{paths + i * a.depth * 8}, a.depth, index, a.root, hi);
     const uint32_t st = verdict((index >> a.depth) != 0u, hi >= bb::P, mismatch);
     status[i] = st;
     count_rejected(st != 0u, d_rejected);
 }
-
-// ---- per lane, Keccak ----
+// (two kernels by name, not one template: the profiler output and the tools that read it know them as verify_lane_*_kernel)
+__global__ void __launch_bounds__(256) verify_lane_p2_kernel(VerifySched a, const uint32_t* indices, uint64_t n, const uint32_t* rows,
+                                                             const uint32_t* paths, uint32_t* status, uint32_t* d_rejected) {
+    verify_lane<HASH_POSEIDON2>(a, indices, n, rows, paths, status, d_rejected);
+}
 __global__ void __launch_bounds__(256) verify_lane_keccak_kernel(VerifySched a, const uint32_t* indices, uint64_t n, const uint32_t* rows,
                                                                  const uint32_t* paths, uint32_t* status, uint32_t* d_rejected) {
-    if (gridDim.x <= 512u) P3_LATENCY_BOUND_KERNEL();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t index = indices[i];
-    const uint32_t* row = rows + i * a.row_words;
-    const uint32_t* path = paths + i * a.depth * 8;
-    uint32_t hi = 0;  // the largest opened value seen (digest words are raw u64 halves: any value is hashed)
-    uint64_t st[25], cur[4] = {0, 0, 0, 0};
-    uint32_t c = 0;
-    for (uint32_t l = 0; l <= a.depth; l++) {
-        const bool has = c < a.n_classes && a.level[c] == l;
-        if (has) {  // SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the class row, digest left in st[0..4)
-#pragma unroll
-            for (int k = 0; k < 25; k++) st[k] = 0;
-            uint32_t seg = a.seg_begin[c], off = 0;
-            const uint32_t total = a.total[c], n64 = (total + 1) / 2;
-            auto next_word = [&]() {
-                while (off >= a.seg_w[seg]) { seg++; off = 0; }
-                const uint32_t w = row[a.seg_off[seg] + off];
-                off++;
-                hi = max(hi, w);
-                return w;
-            };
-            for (uint32_t b = 0; b < n64; b += 17) {
-#pragma unroll
-                for (int k = 0; k < 17; k++) {
-                    const uint32_t e = 2 * (b + k);
-                    if (e < total) {
-                        const uint64_t lo = next_word();
-                        const uint64_t hw = e + 1 < total ? next_word() : 0u;
-                        st[k] = lo | (hw << 32);
-                    }
-                }
-                if (b + 17 >= n64) kk::permute_digest(st);  // the last block: only the digest words are read
-                else kk::permute(st);
-            }
-            c++;
-        }
-        _Pragma("clang loop unroll(disable)")
-        for (uint32_t sub = 0; sub < 2; sub++) {
-            uint64_t r4[4];
-            bool right = false;
-            if (sub == 0) {
-                if (l == 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) cur[k] = st[k];
-                }
-                if (!has || l == 0) continue;
-#pragma unroll
-                for (int k = 0; k < 4; k++) r4[k] = st[k];
-            } else {
-                if (l == a.depth) continue;
-                uint32_t sw[8];
-                load_digest_v(path + l * 8, sw);
-#pragma unroll
-                for (int k = 0; k < 4; k++) r4[k] = (uint64_t)sw[2 * k] | ((uint64_t)sw[2 * k + 1] << 32);
-                right = (index >> l) & 1u;
-            }
-            // CompressionFunctionFromHasher<U64Hash, 2, 4>: one block of the two digests
-#pragma unroll
-            for (int k = 0; k < 4; k++) { st[k] = right ? r4[k] : cur[k]; st[4 + k] = right ? cur[k] : r4[k]; }
-#pragma unroll
-            for (int k = 8; k < 25; k++) st[k] = 0;
-            kk::permute_digest(st);
-#pragma unroll
-            for (int k = 0; k < 4; k++) cur[k] = st[k];
-        }
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)a.root[2 * k] | ((uint64_t)a.root[2 * k + 1] << 32));
-    const uint32_t stt = verdict((index >> a.depth) != 0u, hi >= bb::P, mismatch);
-    status[i] = stt;
-    count_rejected(stt != 0u, d_rejected);
+    verify_lane<HASH_KECCAK>(a, indices, n, rows, paths, status, d_rejected);
 }
 
 // element e of class c's row: its position in an opening's row words (e < total[c]; a short walk over the class's segments)

@@ -39,8 +39,8 @@
 //                         crossing.
 //   pv_open_kernel        one lane per (opening slot, member, query), slot-major so that the lanes of a wave walk paths of one depth:
 //                         an input round's leaf is m0 || m1 ... (with salts m0 || s0 || m1 || s1 ...), an FRI leaf the 8 words of
-//                         pv_query_kernel's pair plus its salt; hashed up the path in the proof (the per-lane sponge / compression
-//                         of mmcs_verify.hip) and compared with the member's root / the round's root in the proof.
+//                         pv_query_kernel's pair plus its salt; hashed up the path in the proof (lane_walk.hip.h) and compared
+//                         with the member's root / the round's root in the proof.
 //   pv_finish_kernel      order key -> status, count of rejected members.
 // MIXED HEIGHTS (a verifier from p3hip_pcs_verifier_create_mixed whose matrices are not all of one height; pcs_verify_any with
 // log_heights is the specification).  A CLASS is the set of matrices of one log_big_c = log_h_c + log_blowup.  The layout knows
@@ -63,15 +63,12 @@
 #include <cstring>
 #include <memory>
 
-#include "bb31.hip.h"
 #include "challenger.h"
 #include "common.h"
-#include "keccak.hip.h"
 #include "mmcs.h"
 #include "pcs_verifier_dev.h"
-#include "poseidon2_f64.hip.h"
 #include "prover.h"
-#include "transcript.hip.h"
+#include "verifier_dev_common.hip.h"
 
 namespace p3 {
 
@@ -79,13 +76,14 @@ using bb::Ext;
 
 namespace {
 
+using namespace vdev;
+
 constexpr uint32_t PV_MAX_IN = (uint32_t)PCS_MAX_ROUNDS, PV_MAX_ALLMATS = (uint32_t)(PCS_MAX_ROUNDS * PCS_MAX_MATS);
 constexpr uint32_t PV_MAX_PAIRS = PV_MAX_ALLMATS * (uint32_t)PCS_MAX_POINTS, PV_MAX_FRI = 28;
 constexpr uint32_t PV_WAVE_MIN_COLS = 256;
-constexpr uint32_t CODE_POW = 11, CODE_INPUT_OPENING = 13, CODE_FRI_OPENING = 14, CODE_FINAL_POLY = 15;
-// order keys (smaller = earlier in the host verifier's order)
-constexpr uint64_t KEY_HEADER = 0, KEY_POW = 1, KEY_QUERY0 = 2, KEY_NONE = ~0ull;
-constexpr uint32_t STEPS_PER_QUERY = 64;  // 2 (n_in + n_fri) + 1 <= 2 (4 + 27) + 1
+constexpr uint32_t CODE_INPUT_OPENING = 13;
+// order keys (smaller = earlier in the host verifier's order) behind KEY_HEADER
+constexpr uint64_t KEY_POW = 1, KEY_QUERY0 = 2;
 static_assert(PV_MAX_PAIRS <= 128, "the transcript kernel keeps two pair powers per lane");
 // where the Keccak half of an exported challenger begins (transcript.hip.h DevState)
 constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;
@@ -140,19 +138,8 @@ struct PArgs {
 static_assert(sizeof(PLayout) + sizeof(PArgs) <= 4096, "both are passed by value: the kernel-argument segment holds 4 KB");
 static_assert(bb::TWO_ADICITY < 32 && PV_MAX_FRI > bb::TWO_ADICITY, "a class is a bit of a 32-bit mask and an index of gens[]");
 
-__device__ __forceinline__ uint64_t make_key(uint64_t order, uint32_t code) { return (order << 8) | code; }
-__device__ __forceinline__ void report(const PArgs& a, uint32_t i, uint64_t order, uint32_t code) {
-    atomicMin(a.key + i, (unsigned long long)make_key(order, code));
-}
-__device__ __forceinline__ bool length_ok(const PArgs& a, const PLayout& L, uint32_t i) { return !a.lens || a.lens[i] == 4u * L.proof_words; }
 // the transcript kernel rejected the member before it produced anything the later kernels read
 __device__ __forceinline__ bool header_rejected(const PArgs& a, uint32_t i) { return (a.key[i] >> 8) == KEY_HEADER; }
-__device__ __forceinline__ const uint32_t* proof_words(const PArgs& a, uint32_t i) {
-    return reinterpret_cast<const uint32_t*>(a.proofs + (size_t)i * a.stride);
-}
-__device__ __forceinline__ Ext ldx(const uint32_t* w, size_t off) { return Ext{{w[off], w[off + 1], w[off + 2], w[off + 3]}}; }
-__device__ __forceinline__ void stx(uint32_t* w, size_t off, const Ext& e) { for (int c = 0; c < 4; c++) w[off + c] = e.c[c]; }
-__device__ __forceinline__ uint32_t rev_bits_dev(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32u - bits) : 0u; }
 __device__ __forceinline__ Ext wave_sum(Ext v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1)
@@ -240,19 +227,8 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
             }
         }
     }
-    PState* st = a.st + i;
-    for (uint32_t r = 0; r < L.n_fri; r++) {
-        ch.observe_n(w + 1 + 8 * r, 8);
-        const Ext beta = ch.sample_ext();
-        if (lane == 0) st->beta[r] = beta;
-    }
-    for (uint32_t k = 0; k < 4 * L.fpl; k++) ch.observe(w[L.fpoly_off + k]);
-    ch.observe(w[L.witness_off]);
-    if (ch.sample_bits(L.pow_bits) != 0) key = make_key(KEY_POW, CODE_POW);
-    for (uint32_t q = 0; q < L.nq; q++) {
-        const uint32_t index = ch.sample_bits(L.log_big);
-        if (lane == 0) a.idx[(size_t)i * L.nq + q] = index;
-    }
+    const FriTail tail{1, L.n_fri, L.fpoly_off, L.fpl, L.witness_off, L.pow_bits, L.nq, L.log_big};  // the roots follow the round count
+    if (!fri_transcript_tail(ch, w, lane, tail, a.st[i].beta, a.idx + (size_t)i * L.nq)) key = make_key(KEY_POW, CODE_POW);
     if (a.chal_out) {  // the other configuration's half of the state is zero, as challenger_export leaves it
         uint32_t* out = a.chal_out + (size_t)i * CHALLENGER_STATE_WORDS;
         const uint32_t lo = L.hash == HASH_POSEIDON2 ? SW_KC : 0u, hi = L.hash == HASH_POSEIDON2 ? CHALLENGER_STATE_WORDS : SW_KC;
@@ -324,25 +300,16 @@ __global__ void __launch_bounds__(256) pv_query_kernel(PArgs a, PLayout L) {
     uint32_t* evs = a.evs + t * L.n_fri * 8;
     for (uint32_t r = 0; r < L.n_fri; r++) {
         const uint32_t lfh = L.log_big - 1 - r;
-        const Ext sib = ldx(qw, L.fri_off[r]);
-        const bool odd = idx & 1u;
-        const Ext ev0 = odd ? sib : folded, ev1 = odd ? folded : sib;
-        const uint32_t pr = idx >> 1;
-        if (lane == 0)
-            for (int c = 0; c < 4; c++) { evs[8 * r + c] = ev0.c[c]; evs[8 * r + 4 + c] = ev1.c[c]; }
-        const uint32_t e = rev_bits_dev(pr, lfh);
-        const uint32_t sx = bb::pow(L.gens[lfh + 1], e), s_inv = bb::pow(L.gens_inv[lfh + 1], e);
         const Ext beta = st->beta[r];
-        const Ext num = bb::mul(bb::sub(beta, bb::ext_from_base(sx)), bb::sub(ev1, ev0));
-        folded = bb::add(ev0, bb::scale(num, bb::mul(L.neg_half, s_inv)));  // 1 / (-s - s)
+        Ext ev0, ev1;
+        folded = fri_fold_step(folded, idx, ldx(qw, L.fri_off[r]), beta, lfh, L.gens, L.gens_inv, L.neg_half, ev0, ev1);
+        if (lane == 0) { stx(evs, 8 * r, ev0); stx(evs, 8 * r + 4, ev1); }
         // the fold has reached 2^lfh elements: the class of that height rolls in (the fold onto the final vector included)
         if (MIXED && ((L.class_mask >> lfh) & 1u))
             folded = bb::add(folded, bb::mul(bb::sqr(beta), class_opening<WAVE, true>(a, L, i, qw, pts, alp, index, lfh, lane, step)));
-        idx = pr;
+        idx >>= 1;
     }
-    const uint32_t xf = bb::pow(L.gens[L.lfinal], rev_bits_dev(idx, L.lfinal));
-    Ext evf = bb::ext_zero();
-    for (uint32_t k = L.fpl; k-- > 0;) evf = bb::add(bb::scale(evf, xf), ldx(w, L.fpoly_off + 4 * (size_t)k));
+    const Ext evf = final_poly_eval(w, L.fpoly_off, L.fpl, L.gens[L.lfinal], L.lfinal, idx);
     if (lane == 0 && !bb::eq(evf, folded)) report(a, i, KEY_QUERY0 + (uint64_t)q * STEPS_PER_QUERY + 2 * (L.n_in + L.n_fri), CODE_FINAL_POLY);
 }
 
@@ -381,191 +348,18 @@ struct LaneOpening {
     }
 };
 
-template <int HASH, bool MIXED>
-__device__ __forceinline__ bool lane_open_mismatch(const PLayout& L, const LaneOpening& o, uint32_t& hi);
-
-// The two forms below restate mmcs_verify.hip's per-lane walks as verifier_dev.hip does (a fix there belongs here too) over words
-// gathered from proof bytes and the fold pairs: MIXED = false one height class; MIXED = true its injection schedule, the shorter
-// classes of an input round compressed in as the right operand at the level whose size equals their height.  (Written after the
-// schedule of mmcs_verify.hip's kernels: with a second sponge site inside the path loop this compiler keeps the Keccak state in scratch.)
-// PaddingFreeSponge<Poseidon2-16, 16, 8, 8> over the words word(0) .. word(len - 1), digest left in s[0..8)
-template <typename F>
-__device__ __forceinline__ void p2_sponge(double (&s)[16], uint32_t len, uint32_t& hi, F word) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) s[k] = 0.0;
-    for (uint32_t k = 0; k < len; k += 8) {
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (k + e < len) {
-                const uint32_t v = word(k + e);
-                hi = max(hi, v);
-                s[e] = p2f::load_elem(v);
-            }
-        p2f::permute(s);
-#pragma unroll
-        for (int e = 0; e < 16; e++) s[e] = p2f::reduce(s[e]);
+// lane_walk's word source.  MIXED = false: one height class, only level 0 has a row.  MIXED = true: level l's nodes are 2^(depth - l), and
+// the round's class of that height is hashed there.
+template <bool MIXED>
+struct OpeningWords {
+    const PLayout& L;
+    const LaneOpening& o;
+    __device__ __forceinline__ bool has(uint32_t l) const { return l == 0 || ((o.inj >> (o.depth - l)) & 1u); }
+    __device__ __forceinline__ uint32_t len(uint32_t l) const { return !MIXED || l == 0 ? o.leaf_len : o.class_len(L, o.depth - l); }
+    __device__ __forceinline__ uint32_t word(uint32_t l, uint32_t e) const {
+        return !MIXED || o.n_ev ? o.leaf_word(L, e) : o.class_word(L, o.depth - l, e);
     }
-}
-
-// PaddingFreeSponge over the leaf, TruncatedPermutation up the path
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2, false>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    const p2f::MagicRegs smk = p2f::magic_regs();
-    double s[16], cur[8];
-    p2_sponge(s, o.leaf_len, hi, [&](uint32_t e) { return o.leaf_word(L, e); });
-#pragma unroll
-    for (int k = 0; k < 8; k++) cur[k] = s[k];
-    for (uint32_t l = 0; l < o.depth; l++) {
-        const bool right = (o.index >> l) & 1u;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t sw = o.path[8 * l + k];
-            hi = max(hi, sw);
-            const double sd = p2f::load_elem(sw);
-            s[k] = right ? sd : cur[k];
-            s[8 + k] = right ? cur[k] : sd;
-        }
-        p2f::permute(s);
-#pragma unroll
-        for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
-    return mismatch;
-}
-// mixed heights: verify_lane_p2_kernel's schedule (mmcs_verify.hip), one sponge site and one compression site.  Level l's nodes have
-// 2^(depth - l) of them: the class of that height (the leaf at l = 0) is hashed, compressed in as the right operand, then the sibling.
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2, true>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    const p2f::MagicRegs smk = p2f::magic_regs();
-    double s[16], cur[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) cur[k] = 0.0;
-    for (uint32_t l = 0; l <= o.depth; l++) {
-        const uint32_t lb = o.depth - l;
-        const bool has = l == 0 || ((o.inj >> lb) & 1u);
-        if (has) p2_sponge(s, l == 0 ? o.leaf_len : o.class_len(L, lb), hi, [&](uint32_t e) { return o.n_ev ? o.leaf_word(L, e) : o.class_word(L, lb, e); });
-        _Pragma("clang loop unroll(disable)")
-        for (uint32_t sub = 0; sub < 2; sub++) {
-            if (sub == 0) {
-                if (l == 0) {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) cur[k] = s[k];
-                }
-                if (!has || l == 0) continue;
-#pragma unroll
-                for (int k = 0; k < 8; k++) { s[8 + k] = s[k]; s[k] = cur[k]; }
-            } else {
-                if (l == o.depth) continue;
-                const bool right = (o.index >> l) & 1u;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const uint32_t sw = o.path[8 * l + k];
-                    hi = max(hi, sw);
-                    const double sd = p2f::load_elem(sw);
-                    s[k] = right ? sd : cur[k];
-                    s[8 + k] = right ? cur[k] : sd;
-                }
-            }
-            p2f::permute(s);
-#pragma unroll
-            for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
-        }
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
-    return mismatch;
-}
-
-// SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the words word(0) .. word(len - 1), digest left in st[0..4)
-template <typename F>
-__device__ __forceinline__ void kk_sponge(uint64_t (&st)[25], uint32_t len, uint32_t& hi, F word) {
-#pragma unroll
-    for (int k = 0; k < 25; k++) st[k] = 0;
-    const uint32_t n64 = (len + 1) / 2;
-    for (uint32_t b = 0; b < n64; b += 17) {
-#pragma unroll
-        for (int k = 0; k < 17; k++) {
-            const uint32_t e = 2 * (b + k);
-            if (e < len) {
-                const uint32_t lo = word(e), hw = e + 1 < len ? word(e + 1) : 0u;
-                hi = max(hi, max(lo, hw));
-                st[k] = (uint64_t)lo | ((uint64_t)hw << 32);
-            }
-        }
-        if (b + 17 >= n64) kk::permute_digest(st);  // the last block: only the digest words are read
-        else kk::permute(st);
-    }
-}
-
-// the sponge over the leaf, CompressionFunctionFromHasher up the path; digest words are raw u64 halves: any value is hashed
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK, false>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    uint64_t st[25], cur[4];
-    kk_sponge(st, o.leaf_len, hi, [&](uint32_t e) { return o.leaf_word(L, e); });
-#pragma unroll
-    for (int k = 0; k < 4; k++) cur[k] = st[k];
-    for (uint32_t l = 0; l < o.depth; l++) {
-        const bool right = (o.index >> l) & 1u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint64_t r = (uint64_t)o.path[8 * l + 2 * k] | ((uint64_t)o.path[8 * l + 2 * k + 1] << 32);
-            st[k] = right ? r : cur[k];
-            st[4 + k] = right ? cur[k] : r;
-        }
-#pragma unroll
-        for (int k = 8; k < 25; k++) st[k] = 0;
-        kk::permute_digest(st);
-#pragma unroll
-        for (int k = 0; k < 4; k++) cur[k] = st[k];
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
-    return mismatch;
-}
-// mixed heights: verify_lane_keccak_kernel's schedule (mmcs_verify.hip), as the Poseidon2 form above
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK, true>(const PLayout& L, const LaneOpening& o, uint32_t& hi) {
-    uint64_t st[25], cur[4] = {0, 0, 0, 0};
-    for (uint32_t l = 0; l <= o.depth; l++) {
-        const uint32_t lb = o.depth - l;
-        const bool has = l == 0 || ((o.inj >> lb) & 1u);
-        if (has) kk_sponge(st, l == 0 ? o.leaf_len : o.class_len(L, lb), hi, [&](uint32_t e) { return o.n_ev ? o.leaf_word(L, e) : o.class_word(L, lb, e); });
-        _Pragma("clang loop unroll(disable)")
-        for (uint32_t sub = 0; sub < 2; sub++) {
-            uint64_t r4[4];
-            bool right = false;
-            if (sub == 0) {
-                if (l == 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) cur[k] = st[k];
-                }
-                if (!has || l == 0) continue;
-#pragma unroll
-                for (int k = 0; k < 4; k++) r4[k] = st[k];
-            } else {
-                if (l == o.depth) continue;
-#pragma unroll
-                for (int k = 0; k < 4; k++) r4[k] = (uint64_t)o.path[8 * l + 2 * k] | ((uint64_t)o.path[8 * l + 2 * k + 1] << 32);
-                right = (o.index >> l) & 1u;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) { st[k] = right ? r4[k] : cur[k]; st[4 + k] = right ? cur[k] : r4[k]; }
-#pragma unroll
-            for (int k = 8; k < 25; k++) st[k] = 0;
-            kk::permute_digest(st);
-#pragma unroll
-            for (int k = 0; k < 4; k++) cur[k] = st[k];
-        }
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
-    return mismatch;
-}
+};
 
 template <int HASH, bool MIXED>
 __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
@@ -618,9 +412,10 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
         o.root = w + 1 + 8 * r;
         code = CODE_FRI_OPENING;
     }
-    // (the FRI lanes of a mixed shape take the MIXED walk too, with nothing to inject: sending them to the one-class walk puts both
-    // walks into one kernel, which takes the Poseidon2 form from 118 to 134 VGPRs, below four waves per SIMD)
-    const bool mismatch = lane_open_mismatch<HASH, MIXED>(L, o, hi);
+    // (the FRI lanes of a mixed shape take the injecting walk too, with nothing to inject: sending them to the other form puts both
+    // walks into one kernel, which took the Poseidon2 form from 118 to 134 VGPRs when it was tried, below four waves per SIMD)
+    OpeningWords<MIXED> src{L, o};
+    const bool mismatch = lane_walk::walk<HASH, MIXED>(src, lane_walk::PathWords{o.path}, o.depth, o.index, o.root, hi);
     if (shape) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
     if (hi >= bb::P) report(a, i, KEY_HEADER, VERIFY_MALFORMED);
     if (mismatch) report(a, i, qkey + 2 * slot + 1, code);
@@ -628,12 +423,7 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
 
 // ---- 4. order key -> status -------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) pv_finish_kernel(const unsigned long long* key, uint32_t n, uint32_t* status, uint32_t* d_rejected) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = i < n;
-    const uint32_t st = act && key[i] != KEY_NONE ? (uint32_t)(key[i] & 0xffu) : 0u;
-    if (act) status[i] = st;
-    const uint64_t b = __builtin_amdgcn_ballot_w64(st != 0u);
-    if (d_rejected && b && (threadIdx.x & 63u) == 0u) atomicAdd(d_rejected, (uint32_t)__builtin_popcountll(b));
+    finish(key, n, status, d_rejected);
 }
 
 // ---- host: the layout of one shape ------------------------------------------------------------------------------------------

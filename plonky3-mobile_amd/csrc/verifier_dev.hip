@@ -15,20 +15,17 @@
 //                         rounds; writes every round's (ev0, ev1) leaf and compares the final polynomial with the folded value.
 //   vd_open_kernel        one lane per (opening slot, proof, query), slot-major so that the lanes of a wave walk paths of one depth:
 //                         assembles the leaf (salts included; FRI leaves from vd_query_kernel's pairs), hashes it up the path in the
-//                         proof (the per-lane sponge / compression of mmcs_verify.hip) and compares with the root.
+//                         proof (lane_walk.hip.h, the form without injection: one height class) and compares with the root.
 //   vd_finish_kernel      order key -> status, count of rejected proofs.
 // The first failure in the HOST's order decides the code: every check does atomicMin on a per-proof word (order key << 8 | code).
 #include <cstring>
 #include <memory>
 
-#include "bb31.hip.h"
 #include "common.h"
-#include "keccak.hip.h"
 #include "mmcs.h"
-#include "poseidon2_f64.hip.h"
 #include "prover.h"
-#include "transcript.hip.h"
 #include "verifier_dev.h"
+#include "verifier_dev_common.hip.h"
 
 namespace p3 {
 
@@ -36,11 +33,12 @@ using bb::Ext;
 
 namespace {
 
+using namespace vdev;
+
 constexpr uint32_t VD_MAX_OPENED = 36, VD_MAX_OPEN = 3, VD_MAX_SHAPE = 24, VD_MAX_CANON = 16, VD_MAX_ROUNDS = 28;
-constexpr uint32_t CODE_OOD = 10, CODE_POW = 11, CODE_COMMIT_OPENING = 13, CODE_FRI_OPENING = 14, CODE_FINAL_POLY = 15;
-// order keys (smaller = earlier in the host verifier's order)
-constexpr uint64_t KEY_HEADER = 0, KEY_OOD = 1, KEY_TAIL_SHAPE = 2, KEY_POW = 3, KEY_QUERY0 = 4, KEY_NONE = ~0ull;
-constexpr uint32_t STEPS_PER_QUERY = 64;  // 2 (n_open + n_rounds) + 1 <= 2 (3 + 27) + 1
+constexpr uint32_t CODE_OOD = 10, CODE_COMMIT_OPENING = 13;
+// order keys (smaller = earlier in the host verifier's order) behind KEY_HEADER
+constexpr uint64_t KEY_OOD = 1, KEY_TAIL_SHAPE = 2, KEY_POW = 3, KEY_QUERY0 = 4;
 
 struct VLayout {
     int hash, hiding;
@@ -82,19 +80,7 @@ struct VArgs {
     unsigned long long* key;  // n
 };
 
-__device__ __forceinline__ uint64_t make_key(uint64_t order, uint32_t code) { return (order << 8) | code; }
 __device__ __forceinline__ uint64_t kmin(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ void report(const VArgs& a, uint32_t i, uint64_t order, uint32_t code) {
-    atomicMin(a.key + i, (unsigned long long)make_key(order, code));
-}
-__device__ __forceinline__ bool length_ok(const VArgs& a, const VLayout& L, uint32_t i) {
-    return !a.lens || a.lens[i] == 4u * L.proof_words;
-}
-__device__ __forceinline__ const uint32_t* proof_words(const VArgs& a, uint32_t i) {
-    return reinterpret_cast<const uint32_t*>(a.proofs + (size_t)i * a.stride);
-}
-__device__ __forceinline__ Ext ldx(const uint32_t* w, uint32_t off) { return Ext{{w[off], w[off + 1], w[off + 2], w[off + 3]}}; }
-__device__ __forceinline__ uint32_t rev_bits_dev(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32u - bits) : 0u; }
 
 // ---- 1. transcript: one wavefront per proof ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) vd_transcript_kernel(VArgs a, VLayout L) {
@@ -167,18 +153,8 @@ __global__ void __launch_bounds__(64) vd_transcript_kernel(VArgs a, VLayout L) {
     const Ext al = ch.sample_ext();
     VState* st = a.st + i;
     if (lane == 0) { st->zeta = zeta; st->zeta_next = zeta_next; st->al = al; }
-    for (uint32_t r = 0; r < L.n_rounds; r++) {
-        ch.observe_n(w + L.froots_off + 8 * r, 8);
-        const Ext beta = ch.sample_ext();
-        if (lane == 0) st->beta[r] = beta;
-    }
-    for (uint32_t k = 0; k < 4 * L.fpl; k++) ch.observe(w[L.fpoly_off + k]);
-    ch.observe(w[L.witness_off]);
-    if (ch.sample_bits(L.pow_bits) != 0) key = kmin(key, make_key(KEY_POW, CODE_POW));
-    for (uint32_t q = 0; q < L.nq; q++) {
-        const uint32_t index = ch.sample_bits(L.log_big);
-        if (lane == 0) a.idx[(size_t)i * L.nq + q] = index;
-    }
+    const FriTail tail{L.froots_off, L.n_rounds, L.fpoly_off, L.fpl, L.witness_off, L.pow_bits, L.nq, L.log_big};
+    if (!fri_transcript_tail(ch, w, lane, tail, st->beta, a.idx + (size_t)i * L.nq)) key = kmin(key, make_key(KEY_POW, CODE_POW));
     if (lane == 0) a.key[i] = key;
 }
 
@@ -204,21 +180,13 @@ __global__ void __launch_bounds__(256) vd_query_kernel(VArgs a, VLayout L) {
     uint32_t idx = index;
     uint32_t* evs = a.evs + t * L.n_rounds * 8;
     for (uint32_t r = 0; r < L.n_rounds; r++) {
-        const uint32_t lfh = L.log_big - 1 - r;
-        const Ext sib = ldx(qw, L.fri_off[r]);
-        const bool odd = idx & 1u;
-        const Ext ev0 = odd ? sib : folded, ev1 = odd ? folded : sib;
-        const uint32_t pair = idx >> 1;
-        for (int c = 0; c < 4; c++) { evs[8 * r + c] = ev0.c[c]; evs[8 * r + 4 + c] = ev1.c[c]; }
-        const uint32_t e = rev_bits_dev(pair, lfh);
-        const uint32_t s = bb::pow(L.gens[lfh + 1], e), s_inv = bb::pow(L.gens_inv[lfh + 1], e);
-        const Ext num = bb::mul(bb::sub(st->beta[r], bb::ext_from_base(s)), bb::sub(ev1, ev0));
-        folded = bb::add(ev0, bb::scale(num, bb::mul(L.neg_half, s_inv)));  // 1 / (-s - s)
-        idx = pair;
+        Ext ev0, ev1;
+        folded = fri_fold_step(folded, idx, ldx(qw, L.fri_off[r]), st->beta[r], L.log_big - 1 - r, L.gens, L.gens_inv, L.neg_half, ev0, ev1);
+        stx(evs, 8 * r, ev0);
+        stx(evs, 8 * r + 4, ev1);
+        idx >>= 1;
     }
-    const uint32_t xf = bb::pow(L.gens[L.lfinal], rev_bits_dev(idx, L.lfinal));
-    Ext evf = bb::ext_zero();
-    for (uint32_t k = L.fpl; k-- > 0;) evf = bb::add(bb::scale(evf, xf), ldx(w, L.fpoly_off + 4 * k));
+    const Ext evf = final_poly_eval(w, L.fpoly_off, L.fpl, L.gens[L.lfinal], L.lfinal, idx);
     if (!bb::eq(evf, folded)) report(a, i, KEY_QUERY0 + (uint64_t)q * STEPS_PER_QUERY + 2 * (L.n_open + L.n_rounds), CODE_FINAL_POLY);
 }
 
@@ -232,6 +200,9 @@ struct LaneOpening {
     const uint32_t* path;
     const uint32_t* root;
     uint32_t n_ev, width, salt, leaf_len, depth, index;
+    // lane_walk's word source, one height class: only level 0 has a row
+    __device__ __forceinline__ uint32_t len(uint32_t) const { return leaf_len; }
+    __device__ __forceinline__ uint32_t word(uint32_t, uint32_t e) const { return leaf_word(e); }
     __device__ __forceinline__ uint32_t leaf_word(uint32_t e) const {
         if (e < n_ev) return evs[e];
         e -= n_ev;
@@ -239,96 +210,6 @@ struct LaneOpening {
         return c < width ? vals[m * (1 + width) + 1 + c] : salts[m * (1 + salt) + 1 + (c - width)];
     }
 };
-
-template <int HASH>
-__device__ __forceinline__ bool lane_open_mismatch(const LaneOpening& o, uint32_t& hi);
-
-// The two forms below restate mmcs_verify.hip's per-lane walks (a fix there belongs here too).  They are not shared functions because
-// those kernels walk a VerifySched of several height classes with injections over 16-byte-aligned path arrays, these one class over
-// words gathered from proof bytes and the fold pairs.
-// PaddingFreeSponge<Poseidon2-16, 16, 8, 8> over the leaf, TruncatedPermutation up the path (mmcs_verify.hip verify_lane_p2_kernel)
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_POSEIDON2>(const LaneOpening& o, uint32_t& hi) {
-    const p2f::MagicRegs smk = p2f::magic_regs();
-    double s[16], cur[8];
-#pragma unroll
-    for (int k = 0; k < 16; k++) s[k] = 0.0;
-    for (uint32_t k = 0; k < o.leaf_len; k += 8) {
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-            if (k + e < o.leaf_len) {
-                const uint32_t v = o.leaf_word(k + e);
-                hi = max(hi, v);
-                s[e] = p2f::load_elem(v);
-            }
-        p2f::permute(s);
-#pragma unroll
-        for (int e = 0; e < 16; e++) s[e] = p2f::reduce(s[e]);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) cur[k] = s[k];
-    for (uint32_t l = 0; l < o.depth; l++) {
-        const bool right = (o.index >> l) & 1u;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t sw = o.path[8 * l + k];
-            hi = max(hi, sw);
-            const double sd = p2f::load_elem(sw);
-            s[k] = right ? sd : cur[k];
-            s[8 + k] = right ? cur[k] : sd;
-        }
-        p2f::permute(s);
-#pragma unroll
-        for (int k = 0; k < 8; k++) cur[k] = p2f::reduce(s[k]);
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 8; k++) mismatch |= p2f::store_elem(cur[k], smk) != o.root[k];
-    return mismatch;
-}
-
-// SerializingHasher + PaddingFreeSponge<KeccakF, 25, 17, 4> over the leaf, CompressionFunctionFromHasher up the path
-// (mmcs_verify.hip verify_lane_keccak_kernel); digest words are raw u64 halves: any value is hashed
-template <>
-__device__ __forceinline__ bool lane_open_mismatch<HASH_KECCAK>(const LaneOpening& o, uint32_t& hi) {
-    uint64_t st[25], cur[4];
-#pragma unroll
-    for (int k = 0; k < 25; k++) st[k] = 0;
-    const uint32_t n64 = (o.leaf_len + 1) / 2;
-    for (uint32_t b = 0; b < n64; b += 17) {
-#pragma unroll
-        for (int k = 0; k < 17; k++) {
-            const uint32_t e = 2 * (b + k);
-            if (e < o.leaf_len) {
-                const uint32_t lo = o.leaf_word(e), hw = e + 1 < o.leaf_len ? o.leaf_word(e + 1) : 0u;
-                hi = max(hi, max(lo, hw));
-                st[k] = (uint64_t)lo | ((uint64_t)hw << 32);
-            }
-        }
-        if (b + 17 >= n64) kk::permute_digest(st);  // the last block: only the digest words are read
-        else kk::permute(st);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) cur[k] = st[k];
-    for (uint32_t l = 0; l < o.depth; l++) {
-        const bool right = (o.index >> l) & 1u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint64_t r = (uint64_t)o.path[8 * l + 2 * k] | ((uint64_t)o.path[8 * l + 2 * k + 1] << 32);
-            st[k] = right ? r : cur[k];
-            st[4 + k] = right ? cur[k] : r;
-        }
-#pragma unroll
-        for (int k = 8; k < 25; k++) st[k] = 0;
-        kk::permute_digest(st);
-#pragma unroll
-        for (int k = 0; k < 4; k++) cur[k] = st[k];
-    }
-    bool mismatch = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mismatch |= cur[k] != ((uint64_t)o.root[2 * k] | ((uint64_t)o.root[2 * k + 1] << 32));
-    return mismatch;
-}
 
 template <int HASH>
 __global__ void __launch_bounds__(256) vd_open_kernel(VArgs a, VLayout L) {
@@ -389,7 +270,7 @@ __global__ void __launch_bounds__(256) vd_open_kernel(VArgs a, VLayout L) {
         o.root = w + L.froots_off + 8 * r;
         code = CODE_FRI_OPENING;
     }
-    const bool mismatch = lane_open_mismatch<HASH>(o, hi);
+    const bool mismatch = lane_walk::walk<HASH, false>(o, lane_walk::PathWords{o.path}, o.depth, o.index, o.root, hi);
     if (shape_tail) report(a, i, KEY_TAIL_SHAPE, VERIFY_MALFORMED);
     if (shape_here) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
     if (hi >= bb::P) report(a, i, KEY_HEADER, VERIFY_MALFORMED);
@@ -398,12 +279,7 @@ __global__ void __launch_bounds__(256) vd_open_kernel(VArgs a, VLayout L) {
 
 // ---- 4. order key -> status -------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) vd_finish_kernel(const unsigned long long* key, uint32_t n, uint32_t* status, uint32_t* d_rejected) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = i < n;
-    const uint32_t st = act && key[i] != KEY_NONE ? (uint32_t)(key[i] & 0xffu) : 0u;
-    if (act) status[i] = st;
-    const uint64_t b = __builtin_amdgcn_ballot_w64(st != 0u);
-    if (d_rejected && b && (threadIdx.x & 63u) == 0u) atomicAdd(d_rejected, (uint32_t)__builtin_popcountll(b));
+    finish(key, n, status, d_rejected);
 }
 
 // ---- host: the layout of one configuration ------------------------------------------------------------------------------------
