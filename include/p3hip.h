@@ -706,9 +706,10 @@ int p3hip_air_info(const p3hip_air_t *air, p3hip_air_info_t *out);
  * matrices: d_chunks_out[c] row r = natural row r C + c (16-byte aligned device pointers in a HOST array; chunk c is committed with
  * domain shift GENERATOR g_qn^c).  pis: n_public Montgomery words, host memory.  log_blowup < log_quotient_degree is refused by name.
  * Enqueues on `stream` (one small upload and one launch; the first call at a log qn also builds that domain's root table) and does
- * not synchronise.  The per-call table (publics, alpha powers, chunk pointers) is the object's: calls on ONE Air go to one stream, where
- * they may follow each other without a synchronisation (the upload reads pinned staging that a later call rewrites only after an
- * event behind the earlier upload); calls on one Air from two streams at once are not supported. */
+ * not synchronise.  The per-call table (publics, alpha powers, chunk pointers) is the object's and is reused in stream order: calls on
+ * ONE Air may follow each other without a synchronisation (the upload reads pinned staging that a later call rewrites only after an
+ * event behind the earlier upload), also on different streams of one thread — a call on another stream than the one before it is
+ * ordered behind that call's kernel by an event, so two streams SERIALISE on one Air; they never overlap.  Not from two threads. */
 int p3hip_air_quotient_dev(p3hip_air_t *air, void *stream, const uint32_t *d_lde, unsigned log_n, unsigned log_blowup, const uint32_t *pis,
                            const uint32_t alpha[4], uint32_t *const *d_chunks_out);
 /* p3_uni_stark::check_constraints (debug builds of prove): the same program over the trace itself, d_trace 2^log_n rows of `width`

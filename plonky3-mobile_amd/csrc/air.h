@@ -28,6 +28,9 @@ struct Air {
     std::vector<uint32_t> h_tab;   // the table of the call being prepared
     uint32_t* h_pin = nullptr;     // pinned staging of tab_words words: the source of the upload
     void* up_done = nullptr;       // hipEvent_t recorded behind the upload: the staging is rewritten only after it
+    void* run_done = nullptr;      // hipEvent_t recorded behind the kernel (check: behind the memset too) on last_stream: a call on
+    void* last_stream = nullptr;   // ANOTHER stream waits for it before it touches d_tab / d_found
+    bool ran = false;
     ~Air();
 };
 

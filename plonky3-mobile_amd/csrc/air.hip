@@ -249,20 +249,30 @@ int ensure_device(Air& a) {
         (void)hipFree(block);
         return fail(ERR_HIP, std::string("air: upload of the program: ") + hipGetErrorString(e));
     }
-    hipEvent_t done = nullptr;
+    hipEvent_t done = nullptr, ran = nullptr;
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&a.h_pin), a.tab_words * 4, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ran, hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipFree(block);
         if (a.h_pin) (void)hipHostFree(a.h_pin);
+        if (done) (void)hipEventDestroy(done);
         a.h_pin = nullptr;
         return fail(ERR_HIP, std::string("air: staging of the per-call table: ") + hipGetErrorString(e));
     }
     a.up_done = done;
+    a.run_done = ran;
     a.d_code = block;
     a.d_consts = block + code_w;
     a.d_tab = a.d_consts + const_w;
     a.d_found = reinterpret_cast<unsigned long long*>(a.d_tab + a.tab_words);
+    return OK;
+}
+
+// d_tab and d_found are the object's, reused in stream order: a call on another stream than the last one's is ordered behind that
+// call's kernel before it writes either.  On one stream this is no operation.
+int order_behind_last_call(Air& a, hipStream_t st) {
+    if (a.ran && a.last_stream != (void*)st) P3_HIP(hipStreamWaitEvent(st, (hipEvent_t)a.run_done, 0));
     return OK;
 }
 
@@ -271,6 +281,7 @@ int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la
     int rc = get_context(&cx);
     if (rc) return rc;
     if (mode == 0 && (rc = cx->get_root_table(st, la.log_rows, false, &la.roots))) return rc;
+    if ((rc = order_behind_last_call(a, st))) return rc;
     // the upload reads pinned staging of the object's; the event behind it says when the staging may be written again (a wait that
     // ends at once unless the previous call's upload has not run yet).  d_tab itself is reused in stream order.
     if (a.h_tab.size() > a.tab_words) return fail(ERR_INTERNAL, "air: the per-call table outgrew its buffer");
@@ -287,6 +298,9 @@ int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la
     if (mode == 0) hipLaunchKernelGGL(air_kernel<0>, grid, block, lds, st, code, a.d_consts, a.d_tab, rows, la);
     else hipLaunchKernelGGL(air_kernel<1>, grid, block, lds, st, code, a.d_consts, a.d_tab, rows, la);
     P3_HIP(hipGetLastError());
+    P3_HIP(hipEventRecord((hipEvent_t)a.run_done, st));
+    a.last_stream = (void*)st;
+    a.ran = true;
     return OK;
 }
 
@@ -296,6 +310,7 @@ Air::~Air() {
     if (d_code) (void)hipFree(d_code);  // waits for the device: an enqueued upload or kernel of this object has run when it returns
     if (h_pin) (void)hipHostFree(h_pin);
     if (up_done) (void)hipEventDestroy((hipEvent_t)up_done);
+    if (run_done) (void)hipEventDestroy((hipEvent_t)run_done);
 }
 
 }  // namespace p3
@@ -414,6 +429,7 @@ int p3hip_air_check_trace_dev(p3hip_air_t* air, void* stream, const uint32_t* d_
         std::vector<uint32_t>& tab = a.h_tab;
         tab.assign(a.n_public ? a.n_public : 1, 0);
         if (a.n_public) memcpy(tab.data(), pis, a.n_public * 4);
+        if ((rc = order_behind_last_call(a, st))) return rc;
         P3_HIP(hipMemsetAsync(a.d_found, 0xff, 8, st));
         if ((rc = launch(a, 1, st, d_trace, la))) return rc;
         unsigned long long found = 0;

@@ -4,7 +4,7 @@ reference prover and verifier for any program built on pcs_ref.commit / open / v
 oracle/stark.c:37-70, 130-134 and 170-215 with the quotient split into chunks as p3_uni_stark does.  It shares nothing with the
 package's compiler but the instruction list itself: the encoding is restated here from include/p3hip.h.
 
-The three test AIRs and their trace generators are at the end; they are written with the package's AirBuilder, whose output —
+The four test AIRs and their trace generators are at the end; they are written with the package's AirBuilder, whose output —
 the instruction list — is what both sides then run."""
 import numpy as np
 
@@ -223,7 +223,7 @@ def verify(kind, fp, code, consts, width, proof, pis, log_n):
     return R.verify(kind, fp, log_n, rounds, opened, proof[4 * header_words(width, lqd):], ch)
 
 
-# ---- the test AIRs: (A) fib is the package's fibonacci_air(); (B) and (C) below ----
+# ---- the test AIRs: (A) fib is the package's fibonacci_air(); (B), (C) and (D) below ----
 B_K, B_K2 = 7, 3
 C_WIDTH = 70
 
@@ -276,10 +276,32 @@ def trace_c(log_n, s=9):
     return O.to_monty(np.array(rows, dtype=np.uint64)), O.to_monty(np.array([s % P], dtype=np.uint64))
 
 
+def air_d(p3):
+    """width 2 (x, y), public (x0), degree 9 under the transition filter, 8 quotient chunks: next.x = x^8 + y (three squarings);
+    next.y = y + x; first row x = x0"""
+    b = p3.AirBuilder(2, 1)
+    x, y = b.local(0), b.local(1)
+    x2 = x * x
+    x4 = x2 * x2
+    t = b.when_transition()
+    t.assert_eq(b.next(0), x4 * x4 + y)
+    t.assert_eq(b.next(1), y + x)
+    b.when_first_row().assert_eq(x, b.public(0))
+    return b.build()
+
+
+def trace_d(log_n, s=3, y0=5):
+    rows, (x, y) = [], (s % P, y0 % P)
+    for _ in range(1 << log_n):
+        rows.append((x, y))
+        x, y = (pow(x, 8, P) + y) % P, (y + x) % P
+    return O.to_monty(np.array(rows, dtype=np.uint64)), O.to_monty(np.array([s % P], dtype=np.uint64))
+
+
 def trace_fib(log_n, a=0, b=1):
     return O.generate_trace_rows(a, b, 1 << log_n), R.fib_pis(a, b, log_n)
 
 
 def all_airs(p3):
     """-> {name: (Air, trace generator)}"""
-    return {"fib": (p3.fibonacci_air(), trace_fib), "B": (air_b(p3), trace_b), "C": (air_c(p3), trace_c)}
+    return {"fib": (p3.fibonacci_air(), trace_fib), "B": (air_b(p3), trace_b), "C": (air_c(p3), trace_c), "D": (air_d(p3), trace_d)}

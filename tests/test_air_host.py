@@ -9,7 +9,7 @@ import pcs_ref as R
 
 P = R.P
 HASHES = [("poseidon2", 0), ("keccak", 1)]
-NAMES = ["fib", "B", "C"]
+NAMES = ["fib", "B", "C", "D"]
 
 
 @pytest.fixture(scope="module")
@@ -41,11 +41,14 @@ def test_reference_prover_reproduces_the_oracle_on_fib(oracle, airs, hash, kind)
 
 
 def test_degrees_and_chunks_of_the_test_airs(airs):
-    b, c = airs["B"][0], airs["C"][0]
+    b, c, d = airs["B"][0], airs["C"][0], airs["D"][0]
     assert (b.width, b.n_constraints, b.max_degree, b.log_quotient_degree, b.n_chunks) == (3, 6, 3, 1, 2)
     assert (c.width, c.n_constraints, c.max_degree, c.log_quotient_degree, c.n_chunks) == (70, 140, 4, 2, 4)
     assert A.degrees(b.code)[1] == 1 and A.degrees(c.code)[1] == 2 and max(A.degrees(c.code)[0]) == 4
     assert len(b.consts) == 2
+    # (D): three squarings and the transition filter give degree 9, the most a constraint may have: all 8 chunks
+    assert (d.width, d.n_public, d.n_constraints, d.max_degree, d.log_quotient_degree, d.n_chunks) == (2, 1, 3, 9, 3, 8)
+    assert A.degrees(d.code) == ([9, 2, 2], 3)
     # (C) has several times more value nodes than there are slots: its program exists only because slots are reused
     assert int((c.code[:, 0] != A.ASSERT_ZERO).sum()) > 4 * A.MAX_SLOTS and c.n_slots <= A.MAX_SLOTS
 
@@ -84,7 +87,7 @@ def _code_of(p3, call):
         return e.code
 
 
-@pytest.mark.parametrize("name,log_n,t", [("fib", 4, (1, 1, 3, 2)), ("B", 3, (1, 0, 3, 2)), ("B", 4, (2, 1, 2, 1)), ("C", 3, (2, 0, 2, 1))])
+@pytest.mark.parametrize("name,log_n,t", [("fib", 4, (1, 1, 3, 2)), ("B", 3, (1, 0, 3, 2)), ("B", 4, (2, 1, 2, 1)), ("C", 3, (2, 0, 2, 1)), ("D", 3, (3, 0, 3, 1))])
 def test_verify_air_accepts_reference_proofs_and_rejects_changes(p3, airs, name, log_n, t):
     air, gen = airs[name]
     trace, pis = gen(log_n)

@@ -1,6 +1,6 @@
 """GPU tests of caller-defined AIRs (include/p3hip.h "caller-defined AIRs", csrc/air.hip, plonky3-mobile_amd/air.py): the quotient
 kernel word for word against the independent evaluator of tests/air_ref.py on random matrices; prove_air byte for byte against the
-oracle and FibAirProver on the fib program and against the reference prover on two other AIRs; check_trace; lifetime.  No test
+oracle and FibAirProver on the fib program and against the reference prover on three other AIRs; check_trace; lifetime.  No test
 provokes a fault: a program the library refuses never reaches a launch (tests/test_air_host.py)."""
 import gc
 
@@ -15,7 +15,7 @@ P = R.P
 HASHES = [("poseidon2", 0), ("keccak", 1)]
 FRI_SETS = [(1, 0, 100, 16), (2, 0, 10, 4), (2, 2, 6, 5), (1, 3, 9, 0), (3, 1, 4, 10), (1, 0, 0, 0), (1, 8, 3, 2), (4, 0, 2, 1)]  # tests/test_gpu_pcs.py
 FIRST_ROWS = [(0, 1), (7, 11), (P - 1, 1)]
-NAMES = ["fib", "B", "C"]
+NAMES = ["fib", "B", "C", "D"]
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +61,7 @@ def test_quotient_chunks_equal_the_reference_on_random_matrices(p3, oracle, airs
 
 
 def test_quotient_of_a_program_that_fills_the_slots(p3, oracle):
-    """the three test AIRs live in one or two slots; a right-leaning sum keeps every term alive, so this program writes and reads slots
+    """the test AIRs live in two or three slots at the most; a right-leaning sum keeps every term alive, so this program writes and reads slots
     up to the cap (degree 3, two chunks), at 2^9 rows: several workgroups with 63 KiB of LDS each"""
     import torch
     b = p3.AirBuilder(66, 1)
@@ -110,7 +110,8 @@ def test_fib_program_proves_the_oracles_and_the_fib_provers_bytes(p3, oracle, ai
             p3.verify_air(air, proof, pis, log_n, p3.FriParameters(*t), hash)
 
 
-CASES_BC = [("B", 3, (1, 0, 5, 3)), ("B", 6, (2, 1, 4, 2)), ("B", 6, (1, 2, 6, 0)), ("B", 3, (2, 0, 3, 4)), ("C", 3, (2, 0, 4, 3)), ("C", 6, (2, 2, 3, 1))]
+CASES_BC = [("B", 3, (1, 0, 5, 3)), ("B", 6, (2, 1, 4, 2)), ("B", 6, (1, 2, 6, 0)), ("B", 3, (2, 0, 3, 4)), ("C", 3, (2, 0, 4, 3)), ("C", 6, (2, 2, 3, 1)),
+            ("D", 1, (3, 0, 2, 1)), ("D", 3, (3, 0, 3, 1)), ("D", 4, (4, 1, 2, 0)), ("D", 6, (3, 2, 4, 2))]  # 8 chunk matrices, 8 shifts
 
 
 @pytest.mark.parametrize("name,log_n,t", CASES_BC)
@@ -127,7 +128,7 @@ def test_other_airs_prove_the_reference_provers_bytes(p3, oracle, airs, name, lo
         assert A.verify(kind, t, air.code, air.consts, air.width, proof, pis, log_n) == 0
 
 
-@pytest.mark.parametrize("name,t", [("fib", (1, 0, 4, 2)), ("B", (1, 1, 4, 2)), ("C", (2, 0, 3, 1))])
+@pytest.mark.parametrize("name,t", [("fib", (1, 0, 4, 2)), ("B", (1, 1, 4, 2)), ("C", (2, 0, 3, 1)), ("D", (3, 0, 3, 1))])
 def test_proofs_of_broken_statements_are_rejected_by_both_verifiers(p3, oracle, airs, name, t):
     air, gen = airs[name]
     log_n = 4
