@@ -131,6 +131,88 @@ int p3hip_poseidon2_permute(uint32_t *states, size_t n);
 int p3hip_poseidon2_permute_variant_dev(uint32_t *d_states, size_t n, int variant, void *stream);
 int p3hip_poseidon2_f64_probe_dev(const double *d_in, uint32_t *d_out, size_t n, int mode, void *stream);
 
+/* ---- diagnostics / tests: the field probe ------------------------------------------------------------
+ * ONE primitive of the field arithmetic per call, lane by lane: lane i reads its k operands at in[i * k ..], calls the function of
+ * csrc/bb31.hip.h, csrc/poseidon2_f64.hip.h or csrc/ntt_narrow_f64.hip.h itself, and writes its m results at out[i * m ..].
+ * Integer and extension ops move uint32_t words (Montgomery words x * 2^32 mod P unless said otherwise); fp64 ops move doubles and
+ * return the function's RAW double (the word, as a double, for the three functions that produce a word), so that a test can assert a
+ * bound and not only a congruence.  _dev runs the DEVICE branch of each function (d_in / d_out device memory, enqueued on `stream`);
+ * _host runs the HOST branch of the integer and extension ops on host memory, needs no GPU, and refuses the fp64 ops by name (they are
+ * __device__ only).  Both refuse an unknown op and n > 2^22 with P3HIP_ERR_BAD_ARG and a message.  Operands outside an op's stated
+ * domain give an unspecified value, never an address: no load, store or loop bound depends on an operand, except the at most 64
+ * iterations of pow's exponent and the at most 27 squarings of two_adic_generator.
+ *
+ *  op  function                     in (k)                      out (m)  stated domain
+ *   1  add(a, b)                    a, b                        1        a, b in [0, P)
+ *   2  sub(a, b)                    a, b                        1        a, b in [0, P)
+ *   3  neg(a)                       a                           1        a in [0, P)
+ *   4  dbl(a)                       a                           1        a in [0, P)
+ *   5  mul(a, b)                    a, b                        1        a, b in [0, P)
+ *   6  sqr(a)                       a                           1        a in [0, P)
+ *   7  dot2(a0, b0, a1, b1)         a0, b0, a1, b1              1        all in [0, P); = (a0 b0 + a1 b1) 2^-32
+ *   8  to_monty(c)                  c (canonical)               1        c in [0, P)
+ *   9  from_monty(m)                m                           1 canon. any 32-bit word; = m 2^-32 mod P
+ *  10  pow7(x)                      x                           1        x in [0, P)
+ *  11  pow(base, e)                 base, e_lo, e_hi            1        base in [0, P), any 64-bit e; pow(., 0) = ONE
+ *  12  inv(a)                       a                           1        a in [0, P); inv(0) = 0
+ *  13  two_adic_generator(bits)     bits (a plain integer)      1        bits <= 27
+ *  14  smul(a, b)                   a, b as int32 bit patterns  1 int32  a, b in (-P, P); result in (-P, P), = a b 2^-32 mod P
+ *  15  sbox7_add(s, rc)             s, rc                       1        s, rc in [0, P); = (s + rc)^7 in Montgomery form
+ *  16  ext mul(a, b)                a[4], b[4]                  4        coefficients in [0, P); F[x] / (x^4 - 11)
+ *  17  ext sqr(a)                   a[4]                        4        "
+ *  18  ext inv(a)                   a[4]                        4        "; inv(0) = 0
+ *  19  ext pow(a, e)                a[4], e_lo, e_hi            4        ", any 64-bit e
+ *  20  ext scale(a, s)              a[4], s                     4        ", s in [0, P)
+ *  32  mulmod(a, b)                 a, b                        1        integers, |ab| < 2^76; |result| < 1.1 P
+ *  33  mulmod_p(a, b, aP)           a, b, aP                    1        integers a, b, |a| <= P/2 + 2 or a in [0, P), |ab| < 2^76,
+ *                                                                        aP = a / P or a * (1/P) correctly rounded
+ *  34  mulmod_p(a, b, a * pinv)     a, b                        1        as 33, aP formed on the device
+ *  35  mulmod_m(a, b, aP, ..)       a, b, aP                    1        as 33 and |b aP| < 2^51; also |a|, |b| <= 35 (P/2 + 1)
+ *  36  mulmod_m(a, b, a * pinv, ..) a, b                        1        as 35, aP formed on the device
+ *  37  add_scaled_pow2(tot, x, inv) tot, x, inv                 1        integers |tot| < 2^40, |x| < 2^44, inv = +-2^-K, 1 <= K <= 8
+ *  38  sbox7(x, ..)                 x                           1        integer |x| <= 35 (P/2 + 1) + P < 2^37; |result| <= P/2 + 2^9
+ *  39  store_elem(v)                v                           1 word   integer |v| < 2^37; = v 2^32 mod P in [0, P)
+ *  40  mulm(a, aP, b, ..)           a, aP, b                    1        integers, a in [0, P) or |a| <= P/2 + 2, |b aP| < 2^51
+ *  41  mulm(a, a * pinv, b, ..)     a, b                        1        as 40, aP formed on the device
+ *  42  word_centered(r)             r                           1 word   integer |r| <= P/2 + 2^22; = r mod P in [0, P)
+ *  43  word_any(x, ..)              x                           1 word   integer |x| < 2^43; = x mod P in [0, P)
+ * The uniform operands the fp64 functions take besides (".." above: the magic-number pair, -(P - 1), 1 / P, -1/2 + 2^-33) are formed
+ * as the kernels form them.  tests/field_ref.py holds the reference of every op and the exact model of every fp64 one. */
+#define P3HIP_FP_ADD 1
+#define P3HIP_FP_SUB 2
+#define P3HIP_FP_NEG 3
+#define P3HIP_FP_DBL 4
+#define P3HIP_FP_MUL 5
+#define P3HIP_FP_SQR 6
+#define P3HIP_FP_DOT2 7
+#define P3HIP_FP_TO_MONTY 8
+#define P3HIP_FP_FROM_MONTY 9
+#define P3HIP_FP_POW7 10
+#define P3HIP_FP_POW 11
+#define P3HIP_FP_INV 12
+#define P3HIP_FP_TWO_ADIC_GENERATOR 13
+#define P3HIP_FP_SMUL 14
+#define P3HIP_FP_SBOX7_ADD 15
+#define P3HIP_FP_EXT_MUL 16
+#define P3HIP_FP_EXT_SQR 17
+#define P3HIP_FP_EXT_INV 18
+#define P3HIP_FP_EXT_POW 19
+#define P3HIP_FP_EXT_SCALE 20
+#define P3HIP_FP_MULMOD 32
+#define P3HIP_FP_MULMOD_P 33
+#define P3HIP_FP_MULMOD_P_DEV 34
+#define P3HIP_FP_MULMOD_M 35
+#define P3HIP_FP_MULMOD_M_DEV 36
+#define P3HIP_FP_ADD_SCALED_POW2 37
+#define P3HIP_FP_SBOX7 38
+#define P3HIP_FP_STORE_ELEM 39
+#define P3HIP_FP_MULM 40
+#define P3HIP_FP_MULM_DEV 41
+#define P3HIP_FP_WORD_CENTERED 42
+#define P3HIP_FP_WORD_ANY 43
+int p3hip_field_probe_dev(int op, const void *d_in, void *d_out, size_t n, void *stream);
+int p3hip_field_probe_host(int op, const void *in, void *out, size_t n);
+
 /* ---- Mmcs<BabyBear>: MerkleTreeMmcs<Poseidon2 sponge 16/8/8, TruncatedPermutation 2/8/16, digest 8>
  *      (the Poseidon2 analogue of the Keccak MMCS wired at native/src/fib_air.rs:31-51) ------------ */
 typedef struct p3hip_tree p3hip_tree_t;

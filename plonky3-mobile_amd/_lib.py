@@ -41,6 +41,8 @@ _SIGS = {
     "p3hip_poseidon2_permute": (C.c_int, [C.c_void_p, C.c_size_t]),
     "p3hip_poseidon2_permute_variant_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "p3hip_poseidon2_f64_probe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "p3hip_field_probe_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "p3hip_field_probe_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "p3hip_mmcs_commit_dev": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                         C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "p3hip_mmcs_commit_async_dev": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),

@@ -334,6 +334,13 @@ int p3hip_poseidon2_f64_probe_dev(const double* d_in, uint32_t* d_out, size_t n,
         return poseidon2_f64_probe((hipStream_t)stream, d_in, d_out, n, mode);
     });
 }
+// test / diagnostics entries of the field primitives, one op per call (field_probe.hip)
+int p3hip_field_probe_dev(int op, const void* d_in, void* d_out, size_t n, void* stream) {
+    return guarded([&]() -> int { return field_probe((hipStream_t)stream, op, d_in, d_out, n); });
+}
+int p3hip_field_probe_host(int op, const void* in, void* out, size_t n) {
+    return guarded([&]() -> int { return field_probe_host(op, in, out, n); });
+}
 
 // ---- Mmcs ---------------------------------------------------------------------------------------
 }  // extern "C"

@@ -144,6 +144,12 @@ struct TraceCheck {
 };
 int fib_check_trace(Context& cx, hipStream_t stream, const uint32_t* d_trace, uint64_t n, const uint32_t pis[3], TraceCheck* out);
 
+// ---- field_probe.hip ----
+// Test probe of the field primitives (include/p3hip.h, P3HIP_FP_*): n lanes of op's operands in, op's results out.  The device form
+// enqueues on `stream`; the host form runs the host branches of the BB_HD functions and refuses the fp64 ops.
+int field_probe(hipStream_t stream, int op, const void* d_in, void* d_out, size_t n);
+int field_probe_host(int op, const void* in, void* out, size_t n);
+
 inline bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
 inline uint32_t log2u(uint64_t v) {
     uint32_t l = 0;

@@ -38,7 +38,10 @@ __device__ __forceinline__ Magic pin_magic() {
 // uniform constants, read from the kernel arguments (SGPR pairs: a VOP3 fp64 op takes one scalar operand)
 struct Uni { double npm1, pinv, fbias; };
 
-// a * b mod P for integers |b| < 2^51 / |a/P|, aP = a / P: |result| <= (1/2 + 2^-9) P
+// a * b mod P for integers with |b aP| < 2^51 AND |ab| < 2^76 (|b| < 2^45 for every |a| <= P), aP = a / P or a * (1 / P):
+// |result| <= P/2 + 1 + |ab| 2^-52, which is below (1/2 + 2^-9) P while |b| <= 2^43.  (This line used to give |b| < 2^51 / |a/P| alone:
+// from |ab| = 2^80 on, M - q (P - 1) is no longer a double and the result is not even congruent; a = 1482960300,
+// b = 1702156248324275 with aP = a * (1 / P) is the case tests/test_field_ref_host.py keeps.)
 // Largest |b| any input reaches: 2^B (P-1), the all-sum of a digit over a tile of P-1 words, which scale_by then multiplies by
 // the inter-digit twiddle or the coset scale; inside a digit, x - y = 2^(B-k) (P-1) for a tile holding P-1 at every 2^k-th
 // position.  tests/test_gpu_structured_inputs.py::test_narrow_f64_extreme_tiles (and .._headline_2_20_x_2) put both into every

@@ -4,7 +4,9 @@
 // instructions.  State elements are doubles holding integers congruent (mod P) to CANONICAL field values
 // (not Montgomery): the kernel converts at load/store.
 //   mulmod(a, b): h = a*b; l = fma(a, b, -h) (exact error); q = rint(h / P); r = fma(-q, P, h) + l
-//     exact for |a*b| < 2^84: h - qP is an integer below 2^32, l an integer below 2^31; result |r| < 1.1 P.
+//     exact for |a*b| < 2^84: h - qP is an integer below 2^33, l an integer below 2^31.  |r| < 1.1 P holds while |a*b| < 2^80 only
+//     (q is within 1/2 + |ab| 2^-52 / P of ab / P and |l| <= ulp(ab) / 2; at 2^83 the exact model reaches 1.6 P:
+//     tests/test_field_ref_host.py).  No kernel calls mulmod or mulmod_p any more; the field probe pins them to |ab| < 2^76.
 #pragma once
 #include "poseidon2.hip.h"
 
