@@ -1,26 +1,11 @@
 // pcs_verifier_dev.hip: batches of TwoAdicFriPcs / HidingFriPcs proofs of ONE shape verified on the device (include/p3hip.h
 // p3hip_pcs_verifier_*).
 #pragma once
+#include "pcs_layout.h"  // PcsShape, PCS_MAX_SLOTS
 #include "prover.h"
 #include "verifier_dev.h"
 
 namespace p3 {
-
-constexpr size_t PCS_MAX_SLOTS = 4;  // point slots of a shape: what PCS_MAX_POINTS distinct values are to the host verifier
-
-// What every proof of one configuration shares.  (Not the C ABI's p3hip_pcs_shape_t, which has no log_heights: c_api.hip fills this.)
-//  widths: the committed widths (random columns included when hiding); slots: one
-// slot < n_slots per (matrix, point) pair, round -> matrix -> point.
-struct PcsShape {
-    uint32_t log_h = 0;  // the caller's height, as for the host verifiers
-    size_t n_rounds = 0;
-    const size_t* mats_per_round = nullptr;
-    const size_t* widths = nullptr;
-    const size_t* points_per_mat = nullptr;
-    size_t n_slots = 0;
-    const uint32_t* slots = nullptr;
-    const unsigned* log_heights = nullptr;  // mixed heights: one log height per matrix, round -> matrix; log_h is then ignored
-};
 
 // host only: the byte length every proof of the shape has
 int pcs_proof_len(int hash, bool hiding, const FriParams& fp, const PcsShape& shape, size_t* len_out);

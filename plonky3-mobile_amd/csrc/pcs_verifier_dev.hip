@@ -4,7 +4,8 @@
 //
 // A SHAPE fixes the layout of every proof: the FRI parameters, the committed log height, per round the matrices' widths, per matrix
 // its opening points as SLOTS (a member supplies n_slots points; pair (matrix, point) -> slot).  Every offset is then a function of
-// the shape: PLayout is computed on the host when the verifier is created and passed to the kernels by value (2.0 kB: it fits).
+// the shape: PLayout is computed on the host when the verifier is created and passed to the kernels by value (2.0 kB: it fits).  It is
+// pcs_layout's (pcs_layout.h), the one layout pcs_verify_any reads too: the shape gates and the offsets exist once.
 //
 // SAFETY RULE.  NO LOAD ADDRESS AND NO LOOP BOUND DEPENDS ON A PROOF BYTE, AN OPENED VALUE, A POINT OR A CHALLENGER STATE WORD.  A
 // proof whose length differs from the shape's is rejected unread; every count / width / depth / salt-length word is compared with the
@@ -69,6 +70,7 @@
 #include "pcs_verifier_dev.h"
 #include "prover.h"
 #include "verifier_dev_common.hip.h"
+#include "verifier_dev_host.h"
 
 namespace p3 {
 
@@ -78,8 +80,6 @@ namespace {
 
 using namespace vdev;
 
-constexpr uint32_t PV_MAX_IN = (uint32_t)PCS_MAX_ROUNDS, PV_MAX_ALLMATS = (uint32_t)(PCS_MAX_ROUNDS * PCS_MAX_MATS);
-constexpr uint32_t PV_MAX_PAIRS = PV_MAX_ALLMATS * (uint32_t)PCS_MAX_POINTS, PV_MAX_FRI = 28;
 constexpr uint32_t PV_WAVE_MIN_COLS = 256;
 constexpr uint32_t CODE_INPUT_OPENING = 13;
 // order keys (smaller = earlier in the host verifier's order) behind KEY_HEADER
@@ -88,29 +88,6 @@ static_assert(PV_MAX_PAIRS <= 128, "the transcript kernel keeps two pair powers 
 // where the Keccak half of an exported challenger begins (transcript.hip.h DevState)
 constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;
 static_assert(offsetof(DevState, pis) == (size_t)CHALLENGER_STATE_WORDS * 4 && CHALLENGER_STATE_WORDS % 2 == 0, "state words");
-
-struct PLayout {
-    int hash;
-    uint32_t salt, log_big, lfinal, n_fri, nq, fpl, pow_bits;
-    uint32_t proof_words, nq_off, q_base, q_len, fpl_off, fpoly_off, witness_off;
-    uint32_t n_in, n_slots, n_pairs, total, wmax, row_words;
-    // mixed heights.  mixed: the matrices are not all of one height (which kernels run); class_mask: bit log_big_c of every class with a
-    // point; per round its tree's depth and a bit per log_big_m among its matrices
-    uint32_t mixed, class_mask, log_big_r[PV_MAX_IN], round_mask[PV_MAX_IN];
-    // input rounds; offsets are relative to a query's first word
-    uint32_t nm[PV_MAX_IN], mat0[PV_MAX_IN], open_off[PV_MAX_IN], depth_off[PV_MAX_IN], leaf_len[PV_MAX_IN];
-    // matrices, round -> matrix: width word at val_off - 1, salt length word at salt_off - 1; leaf_start: where the matrix begins in its leaf
-    // (mixed: in the row of its class, the matrices of its round and height in input order)
-    uint32_t width[PV_MAX_ALLMATS], val_off[PV_MAX_ALLMATS], salt_off[PV_MAX_ALLMATS], leaf_start[PV_MAX_ALLMATS], np[PV_MAX_ALLMATS];
-    uint8_t log_big_m[PV_MAX_ALLMATS];
-    // (matrix, point) pairs, round -> matrix -> point: where the pair's opened values begin, the first power of alpha it consumes (its
-    // class's counter; with one class the same number), its slot, its matrix
-    uint16_t pair_off[PV_MAX_PAIRS], pair_aoff[PV_MAX_PAIRS];
-    uint8_t pair_slot[PV_MAX_PAIRS], pair_mat[PV_MAX_PAIRS];
-    uint32_t nr_off, fri_off[PV_MAX_FRI];
-    // constants of the field
-    uint32_t gen, gen_inv, neg_half, gens[PV_MAX_FRI], gens_inv[PV_MAX_FRI];
-};
 
 struct PState {
     Ext beta[PV_MAX_FRI];
@@ -136,7 +113,6 @@ struct PArgs {
 };
 
 static_assert(sizeof(PLayout) + sizeof(PArgs) <= 4096, "both are passed by value: the kernel-argument segment holds 4 KB");
-static_assert(bb::TWO_ADICITY < 32 && PV_MAX_FRI > bb::TWO_ADICITY, "a class is a bit of a 32-bit mask and an index of gens[]");
 
 // the transcript kernel rejected the member before it produced anything the later kernels read
 __device__ __forceinline__ bool header_rejected(const PArgs& a, uint32_t i) { return (a.key[i] >> 8) == KEY_HEADER; }
@@ -427,132 +403,15 @@ __global__ void __launch_bounds__(256) pv_finish_kernel(const unsigned long long
 }
 
 // ---- host: the layout of one shape ------------------------------------------------------------------------------------------
-// The gates and their messages are pcs_verify_any's (verifier.hip), in its order; what it checks on a member's values (canonical
-// points, the LDE coset, canonical opened values) is the kernels' business.  Slots take the place of its "distinct points" rule.
-// sh.log_heights (one per matrix, round -> matrix; sh.log_h is then ignored): mixed heights, gated as pcs_verify_any gates them, the
-// round and matrix counts first since log_heights is read by them.  With all heights equal the layout is the one-class layout.
+// pcs_layout (pcs_layout.hip) derives it, for this verifier and for pcs_verify_any alike: the shape gates and their messages are there, once.
+// What pcs_verify_any checks on a member's values (canonical points, the LDE coset, canonical opened values) is the kernels' business; slots
+// take the place of its "distinct points" rule.  Only this verifier needs a proof to fit PLayout's 32-bit words.
 int make_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, PLayout* out) {
-    auto bad = [&](const std::string& msg) { return fail(ERR_BAD_ARG, msg); };
-    if (!sh.mats_per_round || !sh.widths || !sh.points_per_mat || !sh.slots) return bad("pcs verify: null argument");
-    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
-    uint32_t log_h = sh.log_h;
-    const size_t n_rounds = sh.n_rounds, max_mats = hiding ? PCS_HIDING_MAX_MATS : PCS_MAX_MATS;
-    uint32_t lh[PV_MAX_ALLMATS];  // per matrix, filled either way
-    if (sh.log_heights) {
-        if (hiding) return bad("pcs verifier: mixed heights are not covered for HidingFriPcs (no hiding prover produces them): hiding must be 0");
-        if (n_rounds == 0) return bad("pcs verify: zero rounds");
-        if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
-        size_t nm = 0;
-        for (size_t r = 0; r < n_rounds; r++) {
-            if (sh.mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
-            if (sh.mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
-            nm += sh.mats_per_round[r];
-        }
-        log_h = 0;
-        uint32_t lo = ~0u;
-        for (size_t m = 0; m < nm; m++) { lh[m] = sh.log_heights[m]; log_h = std::max(log_h, lh[m]); lo = std::min(lo, lh[m]); }
-        // (the bounds on log_h and log_blowup alone, as in pcs_verify_any: a class is log_h_m + log_blowup, an index below, and must not wrap)
-        if (lo < 1 || log_h > bb::TWO_ADICITY || fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
-    }
-    if (hiding) {
-        if (log_h < 1 || log_h >= bb::TWO_ADICITY)
-            return bad("pcs verify: log_h must be in [1, " + std::to_string(bb::TWO_ADICITY - 1) + "] (the caller's log height; the committed polynomials have degree < 2^(log_h + 1))");
-        log_h++;
-    }
-    if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
-    if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
-    if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
-    if (fp.num_queries == 0) return bad("pcs verify: num_queries must be positive");
-    if (n_rounds == 0) return bad("pcs verify: zero rounds");
-    if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
-    if (sh.n_slots < 1 || sh.n_slots > PCS_MAX_SLOTS) return bad("pcs verifier: n_slots must be in [1, " + std::to_string(PCS_MAX_SLOTS) + "]");
-    PLayout& L = *out;
-    memset(&L, 0, sizeof(L));
-    L.hash = hash;
-    L.salt = hiding ? PCS_SALT : 0;
-    L.log_big = log_h + fp.log_blowup;
-    L.lfinal = fp.log_blowup + fp.log_final_poly_len;
-    L.n_fri = L.log_big - L.lfinal;
-    L.nq = fp.num_queries;
-    L.fpl = 1u << fp.log_final_poly_len;
-    L.pow_bits = fp.proof_of_work_bits;
-    L.n_in = (uint32_t)n_rounds;
-    L.n_slots = (uint32_t)sh.n_slots;
-    const uint32_t D = 8;
-    size_t mi = 0, pi = 0, total = 0;
-    uint32_t cnt[bb::TWO_ADICITY + 1] = {0};  // alpha powers consumed so far, per class
-    uint64_t p = 1;  // within a query, behind the count of rounds
-    for (size_t r = 0; r < n_rounds; r++) {
-        const size_t nm = sh.mats_per_round[r];
-        if (nm == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
-        if (nm > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
-        L.nm[r] = (uint32_t)nm;
-        L.mat0[r] = (uint32_t)mi;
-        L.open_off[r] = (uint32_t)p++;
-        uint32_t leaf[bb::TWO_ADICITY + 1] = {0};  // the row of each class of the round so far
-        for (size_t m = 0; m < nm; m++, mi++) {
-            const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
-            const size_t wd = sh.widths[mi], np = sh.points_per_mat[mi];
-            if (wd < 1 || wd > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
-            if (np > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
-            if (!sh.log_heights) lh[mi] = log_h;
-            if (lh[mi] < fp.log_final_poly_len)
-                return bad(who + " has height 2^" + std::to_string(lh[mi]) + ", below the final polynomial's 2^" + std::to_string(fp.log_final_poly_len));
-            const uint32_t lb = lh[mi] + fp.log_blowup;  // <= log_big <= TWO_ADICITY
-            L.log_big_m[mi] = (uint8_t)lb;
-            L.log_big_r[r] = std::max(L.log_big_r[r], lb);
-            L.round_mask[r] |= 1u << lb;
-            if (np) L.class_mask |= 1u << lb;
-            if (lb != L.log_big) L.mixed = 1;
-            L.width[mi] = (uint32_t)wd;
-            L.np[mi] = (uint32_t)np;
-            L.val_off[mi] = (uint32_t)(p + 1);
-            p += 1 + wd;
-            L.leaf_start[mi] = leaf[lb];
-            leaf[lb] += (uint32_t)wd + L.salt;
-            L.wmax = std::max(L.wmax, (uint32_t)wd);
-            L.row_words += (uint32_t)wd;
-            for (size_t k = 0; k < np; k++, pi++) {
-                const std::string pw = who + " point " + std::to_string(k);
-                if (sh.slots[pi] >= sh.n_slots) return bad(pw + ": slot " + std::to_string(sh.slots[pi]) + " of " + std::to_string(sh.n_slots));
-                L.pair_off[pi] = (uint16_t)total;
-                L.pair_aoff[pi] = (uint16_t)cnt[lb];
-                cnt[lb] += (uint32_t)wd;
-                L.pair_slot[pi] = (uint8_t)sh.slots[pi];
-                L.pair_mat[pi] = (uint8_t)mi;
-                total += wd;
-                if (total > PCS_MAX_COLS) return bad(pw + ": more than " + std::to_string(PCS_MAX_COLS) + " batched columns");
-            }
-        }
-        if (L.salt)
-            for (size_t m = 0; m < nm; m++) { L.salt_off[L.mat0[r] + m] = (uint32_t)(p + 1); p += 1 + L.salt; }
-        L.leaf_len[r] = leaf[L.log_big_r[r]];
-        L.depth_off[r] = (uint32_t)p;
-        p += 1 + (uint64_t)D * L.log_big_r[r];
-    }
-    if (total == 0) return bad("pcs verify: no opening point");
-    if (!((L.class_mask >> L.log_big) & 1u))
-        return bad("pcs verify: no matrix of the tallest height 2^" + std::to_string(log_h) + " has an opening point: the FRI input would be missing");
-    L.n_pairs = (uint32_t)pi;
-    L.total = (uint32_t)total;
-    L.nr_off = (uint32_t)p++;
-    for (uint32_t r = 0; r < L.n_fri; r++) {
-        L.fri_off[r] = (uint32_t)p;
-        p += 4 + (L.salt ? 1 + L.salt : 0) + 1 + (uint64_t)D * (L.log_big - 1 - r);
-    }
-    L.q_len = (uint32_t)p;
-    L.nq_off = 1 + D * L.n_fri;
-    L.q_base = L.nq_off + 1;
-    const uint64_t after = (uint64_t)L.q_base + p * L.nq;
-    if (after + 2 + 4ull * L.fpl > 0x3fffffffull) return bad("pcs verifier: a proof of this shape exceeds 2^32 bytes");
-    L.fpl_off = (uint32_t)after;
-    L.fpoly_off = L.fpl_off + 1;
-    L.witness_off = L.fpoly_off + 4 * L.fpl;
-    L.proof_words = L.witness_off + 1;
-    L.gen = bb::to_monty(bb::GEN);
-    L.gen_inv = bb::inv(L.gen);
-    L.neg_half = bb::inv(bb::neg(bb::dbl(bb::ONE)));
-    for (uint32_t b = 0; b < PV_MAX_FRI; b++) { L.gens[b] = bb::two_adic_generator(b); L.gens_inv[b] = bb::inv(L.gens[b]); }
+    if (!sh.slots) return fail(ERR_BAD_ARG, "pcs verify: null argument");
+    std::string why;
+    uint64_t words = 0;
+    if (int rc = pcs_layout(hash, hiding, fp, sh, out, &words, &why)) return fail(rc, why);
+    if (words > 0x3fffffffull) return fail(ERR_BAD_ARG, "pcs verifier: a proof of this shape exceeds 2^32 bytes");
     return OK;
 }
 
@@ -565,33 +424,16 @@ int pcs_proof_len(int hash, bool hiding, const FriParams& fp, const PcsShape& sh
     return OK;
 }
 
-struct PcsVerifierDev::Impl {
+struct PcsVerifierDev::Impl : VerifierDevHost {
     PLayout L;
-    int device = -1;  // none until init has a context
-    size_t max_proofs = 0;
     PState* st = nullptr;
     uint32_t *idx = nullptr, *evs = nullptr, *alp = nullptr, *pa = nullptr, *pb = nullptr;
     unsigned long long* key = nullptr;
-    // the host entry's staging: allocated by its first call (the device entry never needs it)
-    uint8_t* d_proofs = nullptr;
-    uint32_t *d_lens = nullptr, *d_roots = nullptr, *d_points = nullptr, *d_opened = nullptr, *d_cin = nullptr, *d_cout = nullptr, *d_status = nullptr;
-    hipStream_t stream = nullptr;
-    bool staging_ready = false;
-    ~Impl() {
-        for (void* p : {(void*)st, (void*)idx, (void*)evs, (void*)alp, (void*)pa, (void*)pb, (void*)key, (void*)d_proofs, (void*)d_lens,
-                        (void*)d_roots, (void*)d_points, (void*)d_opened, (void*)d_cin, (void*)d_cout, (void*)d_status})
-            if (p) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    uint32_t *d_roots = nullptr, *d_points = nullptr, *d_opened = nullptr, *d_cin = nullptr, *d_cout = nullptr;  // staging of the host entry
 };
 
 PcsVerifierDev::PcsVerifierDev() : im(new Impl()) {}
-PcsVerifierDev::~PcsVerifierDev() {
-    if (im->device < 0) { delete im; return; }  // init refused before anything was allocated: no device to visit
-    DeviceScope ds(im->device);
-    (void)ds.enter();
-    delete im;
-}
+PcsVerifierDev::~PcsVerifierDev() { delete im; }
 size_t PcsVerifierDev::proof_len() const { return 4 * (size_t)im->L.proof_words; }
 size_t PcsVerifierDev::max_proofs() const { return im->max_proofs; }
 size_t PcsVerifierDev::total_columns() const { return im->L.total; }
@@ -610,14 +452,10 @@ int PcsVerifierDev::init(int hash, bool hiding, const FriParams& fp, const PcsSh
     if (int rc = get_context(&cx)) return rc;
     im->device = cx->device;
     im->max_proofs = max_proofs;
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->st), max_proofs * sizeof(PState)));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->idx), max_proofs * L.nq * 4));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->evs), max_proofs * L.nq * (size_t)L.n_fri * 32));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->alp), max_proofs * (size_t)L.wmax * 16));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->pa), max_proofs * (size_t)L.n_pairs * 16));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->pb), max_proofs * (size_t)L.n_pairs * 16));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->key), max_proofs * 8));
-    return OK;
+    return im->alloc({Impl::buf(&im->st, max_proofs * sizeof(PState)), Impl::buf(&im->idx, max_proofs * L.nq * 4),
+                      Impl::buf(&im->evs, max_proofs * L.nq * (size_t)L.n_fri * 32), Impl::buf(&im->alp, max_proofs * (size_t)L.wmax * 16),
+                      Impl::buf(&im->pa, max_proofs * (size_t)L.n_pairs * 16), Impl::buf(&im->pb, max_proofs * (size_t)L.n_pairs * 16),
+                      Impl::buf(&im->key, max_proofs * 8)});
 }
 
 int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_roots, const uint32_t* d_points,
@@ -625,9 +463,7 @@ int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uin
                                uint32_t* d_chal_out, hipStream_t stream) {
     const PLayout& L = im->L;
     auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-    if (n > im->max_proofs) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: more proofs than the verifier was created for");
-    if (n && (!d_proofs || !d_roots || !d_points || !d_opened || !d_chal_in || !d_status)) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: null argument");
-    if (n && ((stride & 3u) || stride < proof_len())) return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: the stride must be a multiple of 4 and at least the proof length");
+    if (int rc = im->check_batch("pcs_verifier_verify_dev", n, !d_proofs || !d_roots || !d_points || !d_opened || !d_chal_in || !d_status, stride, proof_len())) return rc;
     if (misaligned(d_proofs, 4) || misaligned(d_lens, 4) || misaligned(d_roots, 4) || misaligned(d_points, 4) || misaligned(d_opened, 4) ||
         misaligned(d_status, 4) || misaligned(d_rejected, 4))
         return fail(ERR_BAD_ARG, "pcs_verifier_verify_dev: d_proofs, d_lens, d_roots, d_points, d_opened, d_status and d_rejected must be 4-byte aligned");
@@ -666,33 +502,14 @@ int PcsVerifierDev::verify_host(size_t n, const uint8_t* const* proofs, const si
     if (int rc = ds.enter()) return rc;
     const size_t plen = proof_len(), cap = im->max_proofs, SW = CHALLENGER_STATE_WORDS;
     const size_t rw = (size_t)L.n_in * 8, pw = (size_t)L.n_slots * 4, ow = (size_t)L.total * 4;
-    if (!im->staging_ready) {  // each piece is made once (a call that failed half way is resumed by the next), the flag is set last
-        if (!im->stream) P3_HIP(hipStreamCreateWithFlags(&im->stream, hipStreamNonBlocking));
-        if (!im->d_proofs) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_proofs), cap * plen));
-        if (!im->d_lens) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_lens), cap * 4));
-        if (!im->d_roots) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_roots), cap * rw * 4));
-        if (!im->d_points) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_points), cap * pw * 4));
-        if (!im->d_opened) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_opened), cap * ow * 4));
-        if (!im->d_cin) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_cin), cap * SW * 4));
-        if (!im->d_cout) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_cout), cap * SW * 4));
-        if (!im->d_status) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_status), cap * 4));
-        im->staging_ready = true;
-    }
-    std::vector<uint32_t> hl(cap), hc(cap * SW), ho(cap * SW);
+    if (int rc = im->stage(plen, {Impl::buf(&im->d_roots, cap * rw * 4), Impl::buf(&im->d_points, cap * pw * 4), Impl::buf(&im->d_opened, cap * ow * 4),
+                                  Impl::buf(&im->d_cin, cap * SW * 4), Impl::buf(&im->d_cout, cap * SW * 4)}))
+        return rc;
+    std::vector<uint32_t> hc(cap * SW), ho(cap * SW);
     for (size_t base = 0; base < n; base += cap) {
         const size_t m = std::min(cap, n - base);
-        for (size_t k = 0; k < m; k++) {
-            const size_t g = base + k;
-            if (lens[g] == plen) {
-                if (!proofs[g]) return fail(ERR_BAD_ARG, "pcs_verifier_verify: null proof");
-                P3_HIP(hipMemcpyAsync(im->d_proofs + k * plen, proofs[g], plen, hipMemcpyHostToDevice, im->stream));
-                hl[k] = (uint32_t)plen;
-            } else {
-                hl[k] = lens[g] > 0xfffffffeull ? 0xffffffffu : (uint32_t)lens[g];  // a wrong length is rejected unread: nothing is uploaded
-            }
-            challenger_export(*chals[g], hc.data() + k * SW);
-        }
-        P3_HIP(hipMemcpyAsync(im->d_lens, hl.data(), m * 4, hipMemcpyHostToDevice, im->stream));
+        if (int rc = im->upload("pcs_verifier_verify", m, proofs + base, lens + base, plen)) return rc;
+        for (size_t k = 0; k < m; k++) challenger_export(*chals[base + k], hc.data() + k * SW);
         P3_HIP(hipMemcpyAsync(im->d_roots, roots + base * rw, m * rw * 4, hipMemcpyHostToDevice, im->stream));
         P3_HIP(hipMemcpyAsync(im->d_points, points + base * pw, m * pw * 4, hipMemcpyHostToDevice, im->stream));
         P3_HIP(hipMemcpyAsync(im->d_opened, opened + base * ow, m * ow * 4, hipMemcpyHostToDevice, im->stream));
@@ -700,7 +517,7 @@ int PcsVerifierDev::verify_host(size_t n, const uint8_t* const* proofs, const si
         if (int rc = verify_dev(im->d_proofs, plen, im->d_lens, im->d_roots, im->d_points, im->d_opened, im->d_cin, m, im->d_status, nullptr,
                                 im->d_cout, im->stream))
             return rc;
-        P3_HIP(hipMemcpyAsync(status_out + base, im->d_status, m * 4, hipMemcpyDeviceToHost, im->stream));
+        if (int rc = im->download_status(status_out + base, m)) return rc;
         P3_HIP(hipMemcpyAsync(ho.data(), im->d_cout, m * SW * 4, hipMemcpyDeviceToHost, im->stream));
         P3_HIP(hipStreamSynchronize(im->stream));
         for (size_t k = 0; k < m; k++)

@@ -180,7 +180,9 @@ int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* ro
                size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
                size_t len, Challenger* chal, std::string* why);
 // the same for matrices of mixed heights: log_heights one per matrix, round -> matrix, in place of log_h.  With all heights equal it
-// returns what pcs_verify returns for the same bytes (the same code; of several refused arguments it may name another one).
+// returns what pcs_verify returns for the same bytes (the same code; of several refused arguments it may name another one).  The same holds
+// for all three between builds: the shape's gates (pcs_layout.h) run before the checks of the points' values, so of a refused point and a
+// refused shape the shape is named, wherever the point stands.
 int pcs_verify_mixed(int hash, const FriParams& fp, const unsigned* log_heights, const uint32_t* roots, const size_t* mats_per_round,
                      const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
                      const uint8_t* proof, size_t len, Challenger* chal, std::string* why);

@@ -12,6 +12,7 @@
 #include "challenger.h"
 #include "common.h"
 #include "mmcs.h"
+#include "pcs_layout.h"
 #include "poseidon2.hip.h"
 #include "prover.h"
 
@@ -391,86 +392,43 @@ int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint
 // transcript follows the test oracle's verifier (stark.c:216-294) generalised to the call's dimensions: opened values observed
 // round -> matrix -> point -> column, alpha sampled, and per query
 //   ro = sum over (matrix, point) pairs in that order, over columns c:  alpha^k (opened_k - row[c]) / (z - x),  k running on.
-// Every size of the query section follows from the arguments: no loop bound or offset is read from the proof.
-// salt_words > 0: HidingFriPcs::verify over the MerkleTreeHidingMmcs (the test oracle's hiding verifier, stark_hiding.c:380-457, generalised
-// likewise): log_h is the COMMITTED log height, each input BatchOpening carries one salt per matrix behind the values and hashes to the
-// leaf row m0 || s0 || m1 || s1 ... (stark_hiding.c:300-322), each commit-phase opening carries its salt (FriCheck).
-static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
-                          size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
-                          size_t len, Challenger* chal, std::string* why, uint32_t salt_words, size_t max_mats,
-                          const unsigned* log_heights = nullptr) {
+// Everything that is a function of the SHAPE comes from pcs_layout (pcs_layout.h), which the device batch verifier reads too: the gates on
+// the arguments and their messages, each matrix's class, each round's tree depth, the classes with a point, each pair's matrix, place among
+// the opened values and alpha exponent, where the final polynomial lies.  Left here: what depends on a member's VALUES (canonical points off
+// the LDE coset, at most PCS_MAX_POINTS distinct; canonical opened values), the transcript, and the walk, which reads with Reader and
+// compares every count, width, depth and salt-length word with the layout's: nothing is followed.
+// hiding: HidingFriPcs::verify over the MerkleTreeHidingMmcs (the test oracle's hiding verifier, stark_hiding.c:380-457, generalised
+// likewise): log_h is the CALLER's log height, each input BatchOpening carries its matrices' salts (read_opening; stark_hiding.c:300-322),
+// each commit-phase opening its salt (FriCheck).  log_heights: mixed heights (pcs_layout.h), the tallest matrix's class starts the walk.
+static int pcs_verify_any(int hash, bool hiding, const FriParams& fp, uint32_t log_h, const unsigned* log_heights, const uint32_t* roots,
+                          const size_t* mats_per_round, const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points,
+                          const uint32_t* opened, const uint8_t* proof, size_t len, Challenger* chal, std::string* why) {
     auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
     if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
-    if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return bad("pcs verify: unknown hash configuration");
-    if (chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
-    // mixed heights (log_heights: one per matrix, round -> matrix): log_h is the tallest matrix's.  lh[] is filled either way, and
-    // everything below reads the heights from it: with all heights equal the two entries run the same checks on the same numbers.
-    std::vector<uint32_t> lh;
-    if (log_heights) {
-        if (n_rounds == 0) return bad("pcs verify: zero rounds");
-        if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
-        size_t nm = 0;
-        for (size_t r = 0; r < n_rounds; r++) {
-            if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
-            if (mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
-            nm += mats_per_round[r];
-        }
-        lh.assign(log_heights, log_heights + nm);
-        log_h = *std::max_element(lh.begin(), lh.end());
-        // (log_h and log_blowup bounded alone: lh + log_blowup indexes the per-class tables below and must not wrap)
-        if (*std::min_element(lh.begin(), lh.end()) < 1 || log_h > bb::TWO_ADICITY || fp.log_blowup > bb::TWO_ADICITY)
-            return bad("pcs verify: LDE height outside [2^2, 2^27]");
-    }
-    if (log_h < 1 || fp.log_blowup < 1 || log_h + fp.log_blowup > bb::TWO_ADICITY) return bad("pcs verify: LDE height outside [2^2, 2^27]");
-    if (fp.log_final_poly_len >= log_h) return bad("pcs verify: log_final_poly_len must be below the matrices' log height");
-    if (fp.proof_of_work_bits > 30) return bad("pcs verify: proof_of_work_bits too large");
-    if (fp.num_queries == 0) return bad("pcs verify: num_queries must be positive");
-    if (n_rounds == 0) return bad("pcs verify: zero rounds");
-    if (n_rounds > PCS_MAX_ROUNDS) return bad("pcs verify: " + std::to_string(n_rounds) + " rounds, at most " + std::to_string(PCS_MAX_ROUNDS));
-    const uint32_t log_big = log_h + fp.log_blowup;
-    struct Pair { Ext z; uint32_t width; };
-    std::vector<Pair> pairs;                   // round -> matrix -> point
-    std::vector<uint32_t> mat_pairs;           // per matrix: how many pairs
-    Ext zs[PCS_MAX_POINTS];
-    size_t n_points = 0, total = 0, mi = 0, pi = 0, row_max = 0;
-    if (!log_heights) for (size_t r = 0; r < n_rounds; r++) lh.insert(lh.end(), std::min(mats_per_round[r], max_mats), log_h);
-    bool class_has_point[bb::TWO_ADICITY + 1] = {false};  // by log_big_c
-    uint32_t round_log_big[PCS_MAX_ROUNDS] = {0};         // the round's tallest LDE: its tree's depth
-    for (size_t r = 0; r < n_rounds; r++) {
-        if (mats_per_round[r] == 0) return bad("pcs verify: round " + std::to_string(r) + " has zero matrices");
-        if (mats_per_round[r] > max_mats) return bad("pcs verify: round " + std::to_string(r) + " has more than " + std::to_string(max_mats) + " matrices");
-        size_t row = 0;
-        for (size_t m = 0; m < mats_per_round[r]; m++, mi++) {
-            const std::string who = "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m);
-            if (widths[mi] < 1 || widths[mi] > PCS_MAX_COLS) return bad(who + ": width must be in [1, " + std::to_string(PCS_MAX_COLS) + "]");
-            if (points_per_mat[mi] > PCS_MAX_POINTS) return bad(who + ": more than " + std::to_string(PCS_MAX_POINTS) + " opening points");
-            if (lh[mi] < fp.log_final_poly_len)
-                return bad(who + " has height 2^" + std::to_string(lh[mi]) + ", below the final polynomial's 2^" + std::to_string(fp.log_final_poly_len));
-            round_log_big[r] = std::max(round_log_big[r], lh[mi] + fp.log_blowup);
-            if (points_per_mat[mi]) class_has_point[lh[mi] + fp.log_blowup] = true;
-            row += widths[mi];
-            mat_pairs.push_back((uint32_t)points_per_mat[mi]);
-            for (size_t p = 0; p < points_per_mat[mi]; p++, pi++) {
+    // (a hash that is neither is pcs_layout's to name, as it was named before this: a challenger's kind is always one of the two)
+    if ((hash == HASH_POSEIDON2 || hash == HASH_KECCAK) && chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
+    PLayout L;
+    const PcsShape shape{log_h, n_rounds, mats_per_round, widths, points_per_mat, 0, nullptr, log_heights};
+    if (int rc = pcs_layout(hash, hiding, fp, shape, &L, nullptr, why)) return rc;
+    const uint32_t log_big = L.log_big, salt_words = L.salt;
+    const size_t total = L.total;
+    Ext zs[PCS_MAX_POINTS];  // the distinct points; pair_slot: which of them a pair is opened at
+    size_t n_points = 0, pi = 0;
+    for (uint32_t r = 0; r < L.n_in; r++)
+        for (uint32_t m = 0; m < L.nm[r]; m++)
+            for (uint32_t p = 0; p < L.np[L.mat0[r] + m]; p++, pi++) {
                 const uint32_t* z = points + 4 * pi;
-                const std::string pw = who + " point " + std::to_string(p);
-                for (int c = 0; c < 4; c++) if (z[c] >= bb::P) return bad(pw + " is not a canonical field element");
-                if (pcs_point_on_lde_coset(z, log_big)) return bad(pw + " lies on the LDE coset GENERATOR * <g_big>");
+                auto pw = [&] { return "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m) + " point " + std::to_string(p); };
+                for (int c = 0; c < 4; c++) if (z[c] >= bb::P) return bad(pw() + " is not a canonical field element");
+                if (pcs_point_on_lde_coset(z, log_big)) return bad(pw() + " lies on the LDE coset GENERATOR * <g_big>");
                 size_t k = 0;
                 while (k < n_points && memcmp(zs[k].c, z, 16)) k++;
                 if (k == n_points) {
-                    if (n_points == PCS_MAX_POINTS) return bad(pw + ": more than " + std::to_string(PCS_MAX_POINTS) + " distinct opening points");
+                    if (n_points == PCS_MAX_POINTS) return bad(pw() + ": more than " + std::to_string(PCS_MAX_POINTS) + " distinct opening points");
                     memcpy(zs[n_points++].c, z, 16);
                 }
-                pairs.push_back(Pair{zs[k], (uint32_t)widths[mi]});
-                total += widths[mi];
-                if (total > PCS_MAX_COLS) return bad(pw + ": more than " + std::to_string(PCS_MAX_COLS) + " batched columns");
+                L.pair_slot[pi] = (uint8_t)k;
             }
-        }
-        row_max = std::max(row_max, row);
-    }
-    if (total == 0) return bad("pcs verify: no opening point");
-    if (!class_has_point[log_big])
-        return bad("pcs verify: no matrix of the tallest height 2^" + std::to_string(log_h) + " has an opening point: the FRI input would be missing");
     for (size_t i = 0; i < 4 * total; i++) if (opened[i] >= bb::P) return bad("pcs verify: opened value word " + std::to_string(i) + " is not a canonical field element");
     Challenger& ch = *chal;
     std::vector<Ext> ov(total), alp(total);
@@ -482,85 +440,58 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
     FriCheck fri{hash, fp, log_big, salt_words, why};
     if (int rc = fri.commit_phase(rd, ch)) return rc;
     const size_t qstart = rd.pos;
-    {   // the query section's length: per query the rounds' BatchOpenings, then the FRI walk
-        size_t qbytes = 4;
-        mi = 0;
-        for (size_t r = 0; r < n_rounds; r++) {
-            qbytes += 4;
-            for (size_t m = 0; m < mats_per_round[r]; m++, mi++) qbytes += 4 + 4 * widths[mi] + (salt_words ? 4 + 4 * (size_t)salt_words : 0);
-            qbytes += 4 + 32 * (size_t)round_log_big[r];
-        }
-        qbytes += 4;
-        for (uint32_t r = 0; r < fri.n_rounds; r++) qbytes += 16 + (salt_words ? 4 + 4 * (size_t)salt_words : 0) + 4 + 32 * (size_t)(log_big - 1 - r);
-        const size_t all = qbytes * fp.num_queries;
-        if (all > len - rd.pos) return reject(why, 9, "truncated proof");
-        rd.pos += all;
-    }
+    // the final polynomial lies behind the queries: PLayout::fpl_off, in 64 bits (its own holds a proof of less than 2^32 bytes)
+    const uint64_t fpl_off = (uint64_t)L.q_base + (uint64_t)L.q_len * L.nq;
+    if (4 * fpl_off > len) return reject(why, 9, "truncated proof");
+    rd.pos = (size_t)(4 * fpl_off);
     if (int rc = fri.final_poly(rd, ch)) return rc;
     rd.pos = qstart;
-    std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(row_max), leaf(row_max + PCS_MAX_MATS * salt_words), salts(PCS_MAX_MATS * salt_words);
-    std::vector<size_t> hh(2 * PCS_MAX_MATS, (size_t)1 << log_big), lw(2 * PCS_MAX_MATS);
+    static_assert(PCS_HIDING_MAX_MATS <= MAX_MATS && PCS_SALT <= MAX_SALT, "a salted round fits the opening reader's buffers");
+    std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(L.row_words), leaf(L.row_words + PCS_MAX_MATS * salt_words);
+    std::vector<size_t> hh(2 * PCS_MAX_MATS), lw(2 * PCS_MAX_MATS);
+    size_t leaf_len = 0;
     const uint32_t gen = bb::to_monty(bb::GEN);
-    // one reduced opening and one alpha counter per class (by log_big_c); the tallest class is the walk's start, the others roll in
+    // one reduced opening per class (by log_big_c); the tallest class is the walk's start, the others roll in
     Ext ro_c[bb::TWO_ADICITY + 1];
     uint32_t xi_c[bb::TWO_ADICITY + 1];
-    size_t cnt_c[bb::TWO_ADICITY + 1];
     std::vector<std::pair<uint32_t, Ext>> rolls;
     for (uint32_t q = 0; q < fp.num_queries; q++) {
         const size_t index = ch.sample_bits(log_big);
         for (uint32_t lb = 0; lb <= log_big; lb++) {
-            if (!class_has_point[lb]) continue;
-            ro_c[lb] = bb::ext_zero(); cnt_c[lb] = 0;
+            if (!((L.class_mask >> lb) & 1u)) continue;
+            ro_c[lb] = bb::ext_zero();
             xi_c[lb] = bb::mul(gen, bb::pow(bb::two_adic_generator(lb), rev_bits_host(index >> (log_big - lb), lb)));
         }
-        if (rd.u32() != n_rounds) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
-        size_t k = 0, pair = 0;
-        mi = 0;
-        for (size_t r = 0; r < n_rounds; r++) {
-            const size_t nm = mats_per_round[r], m0 = mi;
-            const uint32_t log_big_r = round_log_big[r];  // this round's tree
+        if (rd.u32() != L.n_in) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
+        size_t pair = 0;
+        for (uint32_t r = 0; r < L.n_in; r++) {
+            const size_t nm = L.nm[r], m0 = L.mat0[r];
+            const uint32_t log_big_r = L.log_big_r[r];  // this round's tree
             const size_t index_r = index >> (log_big - log_big_r);
-            for (size_t m = 0; m < nm; m++) hh[salt_words ? 2 * m : m] = hh[salt_words ? 2 * m + 1 : m] = (size_t)1 << (lh[m0 + m] + fp.log_blowup);
-            if (rd.u32() != nm) return reject(why, 12, "query shape");
-            size_t off = 0;
-            for (size_t m = 0; m < nm; m++) {
-                if (rd.u32() != widths[m0 + m]) return reject(why, 12, "query shape");
-                rd.felts(row.data() + off, widths[m0 + m]);
-                off += widths[m0 + m];
-            }
-            for (size_t m = 0; salt_words && m < nm; m++) {
-                if (rd.u32() != salt_words) return reject(why, 12, "query shape");
-                rd.felts(salts.data() + m * salt_words, salt_words);
-            }
-            if (rd.u32() != log_big_r) return reject(why, 12, "query shape");
-            rd.digests(hash, path.data(), log_big_r);
+            if (!read_opening(rd, hash, (uint32_t)nm, L.width + m0, salt_words, log_big_r, row.data(), leaf.data(), &leaf_len, path.data()))
+                return reject(why, 12, "query shape");
             if (rd.bad) return reject(why, 9, "truncated proof");
-            if (salt_words) {  // the salts as width-4 matrices, each behind its matrix
-                size_t p = 0;
-                off = 0;
-                for (size_t m = 0; m < nm; m++) {
-                    const size_t w = widths[m0 + m];
-                    memcpy(leaf.data() + p, row.data() + off, w * 4); p += w; off += w;
-                    memcpy(leaf.data() + p, salts.data() + m * salt_words, (size_t)salt_words * 4); p += salt_words;
-                    lw[2 * m] = w; lw[2 * m + 1] = salt_words;
-                }
-                if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), 2 * nm, index_r, leaf.data(), path.data(), log_big_r, nullptr, false) != 0)
-                    return reject(why, 13, "input opening");
-            } else if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), widths + m0, nm, index_r, row.data(), path.data(), log_big_r, nullptr, false) != 0)
+            size_t n = 0;  // the salts as width-4 matrices, each behind its matrix
+            for (size_t m = m0; m < m0 + nm; m++) {
+                hh[n] = (size_t)1 << L.log_big_m[m]; lw[n++] = L.width[m];
+                if (salt_words) { hh[n] = hh[n - 1]; lw[n++] = salt_words; }
+            }
+            if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), n, index_r, leaf.data(), path.data(), log_big_r, nullptr, false) != 0)
                 return reject(why, 13, "input opening");
-            off = 0;
-            for (size_t m = 0; m < nm; m++, mi++) {
-                const uint32_t lb = lh[mi] + fp.log_blowup;
-                for (uint32_t p = 0; p < mat_pairs[mi]; p++, pair++) {
-                    const Ext dz = bb::inv(bb::sub(pairs[pair].z, bb::ext_from_base(xi_c[lb])));
-                    for (size_t c = 0; c < widths[mi]; c++, k++)
-                        ro_c[lb] = bb::add(ro_c[lb], bb::mul(alp[cnt_c[lb]++], bb::mul(bb::sub(ov[k], bb::ext_from_base(row[off + c])), dz)));
+            size_t off = 0;
+            for (size_t mi = m0; mi < m0 + nm; mi++) {
+                const uint32_t lb = L.log_big_m[mi];
+                for (uint32_t p = 0; p < L.np[mi]; p++, pair++) {
+                    const Ext dz = bb::inv(bb::sub(zs[L.pair_slot[pair]], bb::ext_from_base(xi_c[lb])));
+                    const Ext *a_k = &alp[L.pair_aoff[pair]], *o_k = &ov[L.pair_off[pair]];  // the pair's alpha powers (its class's counter) and opened values
+                    for (size_t c = 0; c < L.width[mi]; c++)
+                        ro_c[lb] = bb::add(ro_c[lb], bb::mul(a_k[c], bb::mul(bb::sub(o_k[c], bb::ext_from_base(row[off + c])), dz)));
                 }
-                off += widths[mi];
+                off += L.width[mi];
             }
         }
         rolls.clear();
-        for (uint32_t lb = 0; lb < log_big; lb++) if (class_has_point[lb]) rolls.emplace_back(lb, ro_c[lb]);
+        for (uint32_t lb = 0; lb < log_big; lb++) if ((L.class_mask >> lb) & 1u) rolls.emplace_back(lb, ro_c[lb]);
         if (int rc = fri.query(rd, index, ro_c[log_big], path.data(), rolls)) return rc;
     }
     if (why) why->clear();
@@ -570,15 +501,13 @@ static int pcs_verify_any(int hash, const FriParams& fp, uint32_t log_h, const u
 int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
                size_t len, Challenger* chal, std::string* why) {
-    return pcs_verify_any(hash, fp, log_h, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why, 0,
-                          PCS_MAX_MATS);
+    return pcs_verify_any(hash, false, fp, log_h, nullptr, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why);
 }
 int pcs_verify_mixed(int hash, const FriParams& fp, const unsigned* log_heights, const uint32_t* roots, const size_t* mats_per_round,
                      const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened,
                      const uint8_t* proof, size_t len, Challenger* chal, std::string* why) {
     if (!log_heights) { if (why) *why = "pcs verify: null argument"; return (int)ERR_BAD_ARG; }
-    return pcs_verify_any(hash, fp, 0, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why, 0,
-                          PCS_MAX_MATS, log_heights);
+    return pcs_verify_any(hash, false, fp, 0, log_heights, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why);
 }
 int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
                       size_t n_rounds, const size_t* points_per_mat, const uint32_t* points, const uint32_t* opened, const uint8_t* proof,
@@ -587,8 +516,7 @@ int pcs_verify_hiding(int hash, const FriParams& fp, uint32_t log_h, const uint3
         if (why) *why = "pcs verify: log_h must be in [1, " + std::to_string(bb::TWO_ADICITY - 1) + "] (the caller's log height; the committed polynomials have degree < 2^(log_h + 1))";
         return (int)ERR_BAD_ARG;
     }
-    return pcs_verify_any(hash, fp, log_h + 1, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why,
-                          PCS_SALT, PCS_HIDING_MAX_MATS);
+    return pcs_verify_any(hash, true, fp, log_h, nullptr, roots, mats_per_round, widths, n_rounds, points_per_mat, points, opened, proof, len, chal, why);
 }
 
 }  // namespace p3

@@ -26,6 +26,7 @@
 #include "prover.h"
 #include "verifier_dev.h"
 #include "verifier_dev_common.hip.h"
+#include "verifier_dev_host.h"
 
 namespace p3 {
 
@@ -398,33 +399,15 @@ int fib_proof_len(int hash, bool hiding, uint32_t log_n, const FriParams& fp, si
     return OK;
 }
 
-struct FibVerifierDev::Impl {
+struct FibVerifierDev::Impl : VerifierDevHost {
     VLayout L;
-    int device = -1;  // none until init has a context
-    size_t max_proofs = 0;
     VState* st = nullptr;
-    uint32_t* idx = nullptr;
-    uint32_t* evs = nullptr;
+    uint32_t *idx = nullptr, *evs = nullptr, *d_pis = nullptr;  // d_pis: staging of the host entry
     unsigned long long* key = nullptr;
-    // the host entry's staging: allocated by its first call (the device entry never needs it)
-    uint8_t* d_proofs = nullptr;
-    uint32_t *d_lens = nullptr, *d_pis = nullptr, *d_status = nullptr;
-    hipStream_t stream = nullptr;
-    bool staging_ready = false;
-    ~Impl() {
-        for (void* p : {(void*)st, (void*)idx, (void*)evs, (void*)key, (void*)d_proofs, (void*)d_lens, (void*)d_pis, (void*)d_status})
-            if (p) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 FibVerifierDev::FibVerifierDev() : im(new Impl()) {}
-FibVerifierDev::~FibVerifierDev() {
-    if (im->device < 0) { delete im; return; }  // init refused before anything was allocated: no device to visit
-    DeviceScope ds(im->device);
-    (void)ds.enter();
-    delete im;
-}
+FibVerifierDev::~FibVerifierDev() { delete im; }
 size_t FibVerifierDev::proof_len() const { return 4 * (size_t)im->L.proof_words; }
 size_t FibVerifierDev::max_proofs() const { return im->max_proofs; }
 int FibVerifierDev::device() const { return im->device; }
@@ -439,19 +422,14 @@ int FibVerifierDev::init(int hash, bool hiding, uint32_t log_n, const FriParams&
     if (int rc = get_context(&cx)) return rc;
     im->device = cx->device;
     im->max_proofs = max_proofs;
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->st), max_proofs * sizeof(VState)));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->idx), max_proofs * L.nq * 4));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->evs), max_proofs * L.nq * (size_t)L.n_rounds * 32));
-    P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->key), max_proofs * 8));
-    return OK;
+    return im->alloc({Impl::buf(&im->st, max_proofs * sizeof(VState)), Impl::buf(&im->idx, max_proofs * L.nq * 4),
+                      Impl::buf(&im->evs, max_proofs * L.nq * (size_t)L.n_rounds * 32), Impl::buf(&im->key, max_proofs * 8)});
 }
 
 int FibVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_pis, size_t n,
                                uint32_t* d_status, uint32_t* d_rejected, hipStream_t stream) {
     const VLayout& L = im->L;
-    if (n > im->max_proofs) return fail(ERR_BAD_ARG, "fib_verifier_verify_dev: more proofs than the verifier was created for");
-    if (n && (!d_proofs || !d_pis || !d_status)) return fail(ERR_BAD_ARG, "fib_verifier_verify_dev: null argument");
-    if (n && ((stride & 3u) || stride < proof_len())) return fail(ERR_BAD_ARG, "fib_verifier_verify_dev: the stride must be a multiple of 4 and at least the proof length");
+    if (int rc = im->check_batch("fib_verifier_verify_dev", n, !d_proofs || !d_pis || !d_status, stride, proof_len())) return rc;
     if (reinterpret_cast<uintptr_t>(d_proofs) & 3u) return fail(ERR_BAD_ARG, "fib_verifier_verify_dev: d_proofs must be 4-byte aligned");
     DeviceScope ds(im->device);
     if (int rc = ds.enter()) return rc;
@@ -477,33 +455,18 @@ int FibVerifierDev::verify_host(size_t n, const uint8_t* const* proofs, const si
     DeviceScope ds(im->device);
     if (int rc = ds.enter()) return rc;
     const size_t plen = proof_len(), cap = im->max_proofs;
-    if (!im->staging_ready) {  // each piece is made once (a call that failed half way is resumed by the next), the flag is set last
-        if (!im->stream) P3_HIP(hipStreamCreateWithFlags(&im->stream, hipStreamNonBlocking));
-        if (!im->d_proofs) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_proofs), cap * plen));
-        if (!im->d_lens) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_lens), cap * 4));
-        if (!im->d_pis) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_pis), cap * 12));
-        if (!im->d_status) P3_HIP(hipMalloc(reinterpret_cast<void**>(&im->d_status), cap * 4));
-        im->staging_ready = true;
-    }
-    std::vector<uint32_t> hl(cap), hp(3 * cap);
+    if (int rc = im->stage(plen, {Impl::buf(&im->d_pis, cap * 12)})) return rc;
+    std::vector<uint32_t> hp(3 * cap);
     for (size_t base = 0; base < n; base += cap) {
         const size_t m = std::min(cap, n - base);
+        if (int rc = im->upload("fib_verifier_verify", m, proofs + base, lens + base, plen)) return rc;
         for (size_t k = 0; k < m; k++) {
-            const size_t g = base + k;
-            if (lens[g] == plen) {
-                if (!proofs[g]) return fail(ERR_BAD_ARG, "fib_verifier_verify: null proof");
-                P3_HIP(hipMemcpyAsync(im->d_proofs + k * plen, proofs[g], plen, hipMemcpyHostToDevice, im->stream));
-                hl[k] = (uint32_t)plen;
-            } else {
-                hl[k] = lens[g] > 0xfffffffeull ? 0xffffffffu : (uint32_t)lens[g];  // a wrong length is rejected unread: nothing is uploaded
-            }
-            const uint64_t v[3] = {a[g], b[g], x[g]};
+            const uint64_t v[3] = {a[base + k], b[base + k], x[base + k]};
             for (int j = 0; j < 3; j++) hp[3 * k + j] = bb::to_monty((uint32_t)(v[j] % bb::P));
         }
-        P3_HIP(hipMemcpyAsync(im->d_lens, hl.data(), m * 4, hipMemcpyHostToDevice, im->stream));
         P3_HIP(hipMemcpyAsync(im->d_pis, hp.data(), m * 12, hipMemcpyHostToDevice, im->stream));
         if (int rc = verify_dev(im->d_proofs, plen, im->d_lens, im->d_pis, m, im->d_status, nullptr, im->stream)) return rc;
-        P3_HIP(hipMemcpyAsync(status_out + base, im->d_status, m * 4, hipMemcpyDeviceToHost, im->stream));
+        if (int rc = im->download_status(status_out + base, m)) return rc;
         P3_HIP(hipStreamSynchronize(im->stream));
     }
     return OK;
