@@ -4,6 +4,7 @@
 // exactly as in the reference, and is not a fallback for any device kernel.  Written against the wire format
 // of prover.hip; independent of the test oracle.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -43,9 +44,6 @@ size_t rev_bits_host(size_t x, unsigned bits) { size_t y = 0; for (unsigned i = 
 
 int reject(std::string* why, int code, const char* msg) { if (why) *why = msg; return code; }
 
-// the widest opening: the hiding quotient's four chunk matrices of 4 columns, each with a 4-word salt (a leaf of 32 words)
-constexpr uint32_t MAX_MATS = 4, MAX_SALT = 4, MAX_LEAF = MAX_MATS * (4 + MAX_SALT);
-
 // The parameter gates both verifiers share, as the provers' inits state them: nothing below may shift by >= 32 or leave the two-adic
 // subgroup.  log_height: the committed trace's log height; the two messages are each wire format's own.
 int check_parameters(int hash, uint32_t log_n, uint32_t log_height, const FriParams& fp, std::string* why, const char* lde_msg,
@@ -59,10 +57,10 @@ int check_parameters(int hash, uint32_t log_n, uint32_t log_height, const FriPar
 }
 
 // Reads one BatchOpening — n_mats (width, values) pairs, then one salt per matrix when salt_words > 0, then the sibling path — and
-// assembles the leaf row it hashes to: m0 || s0 || m1 || s1 ...  False on a shape mismatch (the caller checks the path: verify_opening).
+// assembles the leaf row it hashes to: m0 || s0 || m1 || s1 ...  False on a shape mismatch (the caller checks the path).
 bool read_opening(Reader& rd, int hash, uint32_t n_mats, const uint32_t* widths, uint32_t salt_words, unsigned depth, uint32_t* vals,
                   uint32_t* leaf, size_t* leaf_len, uint32_t* path) {
-    uint32_t salts[MAX_MATS * MAX_SALT];
+    uint32_t salts[PCS_HIDING_MAX_MATS * PCS_SALT];  // a salted round has at most PCS_HIDING_MAX_MATS matrices (pcs_layout's gate)
     if (rd.u32() != n_mats) return false;
     size_t off = 0;
     for (uint32_t m = 0; m < n_mats; m++) {
@@ -131,7 +129,7 @@ struct FriCheck {
         for (uint32_t r = 0; r < n_rounds; r++) {
             const uint32_t lfh = log_big - 1 - r;
             Ext sib = rd.ext();
-            uint32_t row[8 + MAX_SALT];
+            uint32_t row[8 + PCS_SALT];
             if (salt_words) {
                 if (rd.u32() != salt_words) return reject(why, 12, "query shape");
                 rd.felts(row + 8, salt_words);
@@ -160,306 +158,75 @@ struct FriCheck {
     }
 };
 
-}  // namespace
+// What the three callers of pcs_walk answer differently for the same bytes.  Nobody chose these differences; the recordings under
+// tests/golden pin them (fib_verify_codes.json, verifier_noncanonical_codes.json, pcs_verify_codes.json), so they are kept, in one place.
+struct Dialect {
+    const char* round_name[PCS_MAX_ROUNDS];  // the message that names an input round, in proof order
+    uint32_t named;                          // bit c: code c (of 9, 12, 13 at an input opening) carries round_name, not the general message
+    bool stop_on_flag;  // a reader flagged (truncated, or a word >= P) right after an input opening rejects with 9 before the path is hashed
+    enum { LAYOUT_CHECKED, LAYOUT, COUNTS } final_at;  // the final polynomial lies where the layout says, a shorter proof being a 9
+                                                       // (CHECKED) or final_poly's own 7; or where skip_queries_by_counts ends
+};
+constexpr Dialect DIALECT_PCS{{}, 0, true, Dialect::LAYOUT_CHECKED};
+constexpr Dialect DIALECT_FIB1{{"trace opening", "quotient opening"}, 1u << 13, false, Dialect::COUNTS};
+constexpr Dialect DIALECT_FIB2{{"randomization opening", "trace opening", "quotient opening"}, 1u << 9 | 1u << 12 | 1u << 13, true, Dialect::LAYOUT};
 
-// check_parameters for either wire format, with that format's own messages (the device verifier refuses what these refuse)
-int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriParams& fp, std::string* why) {
-    if (hiding)
-        return check_parameters(hash, log_n, log_n + 1, fp, why, "bad parameters: LDE height outside the two-adic subgroup",
-                                "bad parameters: log_final_poly_len must be below the randomized trace's log height");
-    return check_parameters(hash, log_n, log_n, fp, why, "bad parameters: LDE height outside [2^2, 2^27]",
-                            "bad parameters: log_final_poly_len must be below the trace's log height");
-}
-
-// 0 = accept; otherwise a positive code naming the failed check (same numbering as the error strings below).
-int verify_fib_air(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
-                   const FriParams& fp, std::string* why, int hash) {
-    if (int rc = verify_check_parameters(hash, false, log_n, fp, why)) return rc;
-    Reader rd{proof, len};
-    const uint32_t log_big = log_n + fp.log_blowup;
-    const uint64_t n = 1ull << log_n;
-    const uint32_t gen = bb::to_monty(bb::GEN);
-    if (rd.u32() != 0x42463350u || rd.u32() != 1) return reject(why, 1, "bad header");
-    if (rd.u32() != log_n) return reject(why, 2, "degree_bits mismatch");
-    uint32_t root_t[8], root_q[8];
-    rd.digests(hash, root_t, 1); rd.digests(hash, root_q, 1);
-    Ext t_loc[2], t_nxt[2], q_z[4];
-    if (rd.u32() != 2) return reject(why, 3, "opened values shape");
-    for (auto& e : t_loc) e = rd.ext();
-    if (rd.u32() != 2) return reject(why, 3, "opened values shape");
-    for (auto& e : t_nxt) e = rd.ext();
-    if (rd.u32() != 1 || rd.u32() != 4) return reject(why, 3, "opened values shape");
-    for (auto& e : q_z) e = rd.ext();
-    if (rd.bad) return reject(why, 4, "truncated proof");
-    uint32_t pis[3] = {bb::to_monty((uint32_t)(a_pub % bb::P)), bb::to_monty((uint32_t)(b_pub % bb::P)), bb::to_monty((uint32_t)(x_pub % bb::P))};
-    Challenger ch(hash);
-    ch.observe(bb::to_monty(log_n)); ch.observe(bb::to_monty(log_n));
-    ch.observe_digest(root_t); ch.observe_n(pis, 3);
-    Ext alpha = ch.sample_ext();
-    ch.observe_digest(root_q);
-    Ext zeta = ch.sample_ext();
-    const uint32_t g_n = bb::two_adic_generator(log_n);
-    Ext zeta_next = bb::scale(zeta, g_n);
-    {   // constraints at zeta (FibonacciAir, fib_air.rs:232-264) against the opened quotient
-        Ext zh = bb::sub(bb::pow(zeta, n), bb::ext_one());
-        Ext ginv = bb::ext_from_base(bb::inv(g_n));
-        Ext first = bb::mul(zh, bb::inv(bb::sub(zeta, bb::ext_one())));
-        Ext last = bb::mul(zh, bb::inv(bb::sub(zeta, ginv)));
-        Ext trans = bb::sub(zeta, ginv);
-        Ext c[5] = {bb::mul(first, bb::sub(t_loc[0], bb::ext_from_base(pis[0]))), bb::mul(first, bb::sub(t_loc[1], bb::ext_from_base(pis[1]))),
-                    bb::mul(trans, bb::sub(t_loc[1], t_nxt[0])), bb::mul(trans, bb::sub(bb::add(t_loc[0], t_loc[1]), t_nxt[1])),
-                    bb::mul(last, bb::sub(t_loc[1], bb::ext_from_base(pis[2])))};
-        Ext folded = bb::ext_zero();
-        for (auto& ck : c) folded = bb::add(bb::mul(folded, alpha), ck);
-        Ext quot = bb::ext_zero();
-        for (int e = 0; e < 4; e++) { Ext be = bb::ext_zero(); be.c[e] = bb::ONE; quot = bb::add(quot, bb::mul(be, q_z[e])); }
-        if (!bb::eq(bb::mul(folded, bb::inv(zh)), quot)) return reject(why, 10, "OodEvaluationMismatch");
-    }
-    for (auto& e : t_loc) ch.observe_ext(e);
-    for (auto& e : t_nxt) ch.observe_ext(e);
-    for (auto& e : q_z) ch.observe_ext(e);
-    Ext al = ch.sample_ext();
-    Ext alp[8]; alp[0] = bb::ext_one();
-    for (int k = 1; k < 8; k++) alp[k] = bb::mul(alp[k - 1], al);
-    FriCheck fri{hash, fp, log_big, 0, why};
-    if (int rc = fri.commit_phase(rd, ch)) return rc;
-    const size_t qstart = rd.pos;
-    for (uint32_t q = 0; q < fp.num_queries && !rd.bad; q++) {  // skip to the final polynomial
-        if (rd.u32() != 2) rd.bad = true;
-        for (int m = 0; m < 2 && !rd.bad; m++) { rd.u32(); uint32_t w = rd.u32(); rd.pos += 4 * (size_t)w; uint32_t pl = rd.u32(); rd.pos += 32 * (size_t)pl; }
+// Wire format 1 finds its final polynomial by FOLLOWING the queries' count words (widths, path lengths, round counts), as its first
+// verifier did, not from the shape: a tampered count moves the final polynomial and the proof is a 7 (or 8) there, before the query walk
+// compares that word with the layout and would say 12.  One matrix a round and no salts: format 1's shape.  A count may carry pos far past
+// len; the next u32 flags that (pos is 64 bits: 2^32 counts of 2^37 bytes do not wrap it).
+void skip_queries_by_counts(Reader& rd, const PLayout& L) {
+    for (uint32_t q = 0; q < L.nq && !rd.bad; q++) {
+        if (rd.u32() != L.n_in) rd.bad = true;
+        for (uint32_t r = 0; r < L.n_in && !rd.bad; r++) { rd.u32(); uint32_t w = rd.u32(); rd.pos += 4 * (size_t)w; uint32_t pl = rd.u32(); rd.pos += 32 * (size_t)pl; }
         uint32_t nr = rd.u32();
         for (uint32_t r = 0; r < nr && !rd.bad; r++) { rd.pos += 16; uint32_t pl = rd.u32(); rd.pos += 32 * (size_t)pl; }
     }
-    if (int rc = fri.final_poly(rd, ch)) return rc;
-    rd.pos = qstart;
-    std::vector<uint32_t> path((size_t)(log_big + 1) * 8);
-    const uint32_t w_t = 2, w_q = 4;
-    for (uint32_t q = 0; q < fp.num_queries; q++) {
-        const size_t index = ch.sample_bits(log_big);
-        uint32_t trow[2], qrow[4], leaf[MAX_LEAF];
-        size_t leaf_len = 0;
-        if (rd.u32() != 2) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
-        if (!read_opening(rd, hash, 1, &w_t, 0, log_big, trow, leaf, &leaf_len, path.data())) return reject(why, 12, "query shape");
-        if (!verify_opening(hash, root_t, index, leaf, leaf_len, path.data(), log_big)) return reject(why, 13, "trace opening");
-        if (!read_opening(rd, hash, 1, &w_q, 0, log_big, qrow, leaf, &leaf_len, path.data())) return reject(why, 12, "query shape");
-        if (!verify_opening(hash, root_q, index, leaf, leaf_len, path.data(), log_big)) return reject(why, 13, "quotient opening");
-        const uint32_t xi = bb::mul(gen, bb::pow(bb::two_adic_generator(log_big), rev_bits_host(index, log_big)));
-        Ext d0 = bb::inv(bb::sub(zeta, bb::ext_from_base(xi))), d1 = bb::inv(bb::sub(zeta_next, bb::ext_from_base(xi)));
-        Ext ro = bb::ext_zero();
-        int k = 0;
-        for (int j = 0; j < 2; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(t_loc[j], bb::ext_from_base(trow[j])), d0)));
-        for (int j = 0; j < 2; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(t_nxt[j], bb::ext_from_base(trow[j])), d1)));
-        for (int j = 0; j < 4; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(q_z[j], bb::ext_from_base(qrow[j])), d0)));
-        if (int rc = fri.query(rd, index, ro, path.data())) return rc;
-    }
-    if (why) why->clear();
-    return 0;
 }
 
-
-// ---- verifier of HIDING proofs (wire format version 2; prover_hiding.hip.inc): p3_uni_stark::verify with SC::Pcs::ZK over
-// HidingFriPcs + MerkleTreeHidingMmcs as the reference configures them (native/src/fib_air.rs:40-72).  Leaves are the
-// opened values followed by their salts, matrix by matrix; the quotient is recomposed from the four blinded chunks
-// (the blinding cancels in sum_c zps_c(zeta) chunk_c(zeta)); every opened column, the random ones included, enters the
-// FRI batch.  [UPSTREAM-RECALL] in structure, parity unpinned.
-namespace {
-constexpr uint32_t VH_NRC = 4, VH_SALT = 4, VH_D = 4, VH_TW = 2 + VH_NRC, VH_RW = VH_NRC + VH_D, VH_CH = 4;
-constexpr uint32_t VH_OPEN = VH_RW + 2 * VH_TW + VH_CH * VH_D;
-static_assert(VH_CH <= MAX_MATS && VH_SALT <= MAX_SALT && VH_CH * (VH_D + VH_SALT) <= MAX_LEAF && VH_RW + VH_SALT <= MAX_LEAF,
-              "hiding openings fit the opening reader's buffers");
-}  // namespace
-
-int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
-                          const FriParams& fp, std::string* why, int hash) {
-    const uint32_t log_ext = log_n + 1, log_big = log_ext + fp.log_blowup;
-    if (int rc = verify_check_parameters(hash, true, log_n, fp, why)) return rc;
-    Reader rd{proof, len};
-    const uint64_t h = 1ull << log_n;
-    const uint32_t gen = bb::to_monty(bb::GEN);
-    if (rd.u32() != 0x42463350u || rd.u32() != 2) return reject(why, 1, "bad header");
-    if (rd.u32() != log_n) return reject(why, 2, "degree_bits mismatch");
-    uint32_t root_t[8], root_q[8], root_r[8];
-    rd.digests(hash, root_t, 1); rd.digests(hash, root_q, 1); rd.digests(hash, root_r, 1);
-    Ext opened[VH_OPEN];  // random (8), trace @ zeta (6), trace @ zeta g (6), chunks (4 x 4)
-    {
-        uint32_t k = 0;
-        if (rd.u32() != VH_RW) return reject(why, 3, "opened values shape");
-        for (uint32_t i = 0; i < VH_RW; i++) opened[k++] = rd.ext();
-        if (rd.u32() != VH_TW) return reject(why, 3, "opened values shape");
-        for (uint32_t i = 0; i < VH_TW; i++) opened[k++] = rd.ext();
-        if (rd.u32() != VH_TW) return reject(why, 3, "opened values shape");
-        for (uint32_t i = 0; i < VH_TW; i++) opened[k++] = rd.ext();
-        if (rd.u32() != VH_CH) return reject(why, 3, "opened values shape");
-        for (uint32_t c = 0; c < VH_CH; c++) {
-            if (rd.u32() != VH_D) return reject(why, 3, "opened values shape");
-            for (uint32_t i = 0; i < VH_D; i++) opened[k++] = rd.ext();
-        }
-    }
-    if (rd.bad) return reject(why, 4, "truncated proof");
-    const Ext* t_z = opened + VH_RW;
-    const Ext* t_zn = t_z + VH_TW;
-    const Ext* q_z = t_zn + VH_TW;
-    uint32_t pis[3] = {bb::to_monty((uint32_t)(a_pub % bb::P)), bb::to_monty((uint32_t)(b_pub % bb::P)), bb::to_monty((uint32_t)(x_pub % bb::P))};
-    Challenger ch(hash);
-    ch.observe(bb::to_monty(log_ext)); ch.observe(bb::to_monty(log_n));
-    ch.observe_digest(root_t); ch.observe_n(pis, 3);
-    Ext alpha = ch.sample_ext();
-    ch.observe_digest(root_q);
-    ch.observe_digest(root_r);
-    Ext zeta = ch.sample_ext();
-    const uint32_t g_h = bb::two_adic_generator(log_n);
-    Ext zeta_next = bb::scale(zeta, g_h);
-    {   // constraints at zeta against the quotient recomposed from the blinded chunks
-        Ext zh_pow = bb::pow(zeta, h);
-        Ext zh = bb::sub(zh_pow, bb::ext_one());
-        Ext ginv = bb::ext_from_base(bb::inv(g_h));
-        Ext first = bb::mul(zh, bb::inv(bb::sub(zeta, bb::ext_one())));
-        Ext last = bb::mul(zh, bb::inv(bb::sub(zeta, ginv)));
-        Ext trans = bb::sub(zeta, ginv);
-        Ext c[5] = {bb::mul(first, bb::sub(t_z[0], bb::ext_from_base(pis[0]))), bb::mul(first, bb::sub(t_z[1], bb::ext_from_base(pis[1]))),
-                    bb::mul(trans, bb::sub(t_z[1], t_zn[0])), bb::mul(trans, bb::sub(bb::add(t_z[0], t_z[1]), t_zn[1])),
-                    bb::mul(last, bb::sub(t_z[1], bb::ext_from_base(pis[2])))};
-        Ext folded = bb::ext_zero();
-        for (auto& ck : c) folded = bb::add(bb::mul(folded, alpha), ck);
-        // chunk cosets D_c = s_c <g_h>: s_c^h = GENERATOR^h w4^c; zps_c(zeta) = prod_{j != c} (zeta^h - s_j^h) / (s_c^h - s_j^h)
-        uint32_t sh[VH_CH];
-        { uint32_t gh = bb::pow(gen, h), w4 = bb::two_adic_generator(2), p = bb::ONE;
-          for (uint32_t k = 0; k < VH_CH; k++) { sh[k] = bb::mul(gh, p); p = bb::mul(p, w4); } }
-        Ext quot = bb::ext_zero();
-        for (uint32_t ci = 0; ci < VH_CH; ci++) {
-            uint32_t kc = bb::ONE;
-            Ext zp = bb::ext_one();
-            for (uint32_t j = 0; j < VH_CH; j++)
-                if (j != ci) { kc = bb::mul(kc, bb::sub(sh[ci], sh[j])); zp = bb::mul(zp, bb::sub(zh_pow, bb::ext_from_base(sh[j]))); }
-            zp = bb::scale(zp, bb::inv(kc));
-            Ext v = bb::ext_zero();
-            for (int e = 0; e < 4; e++) { Ext be = bb::ext_zero(); be.c[e] = bb::ONE; v = bb::add(v, bb::mul(be, q_z[ci * VH_D + e])); }
-            quot = bb::add(quot, bb::mul(zp, v));
-        }
-        if (!bb::eq(bb::mul(folded, bb::inv(zh)), quot)) return reject(why, 10, "OodEvaluationMismatch");
-    }
-    for (uint32_t k = 0; k < VH_OPEN; k++) ch.observe_ext(opened[k]);
-    Ext al = ch.sample_ext();
-    Ext alp[VH_OPEN]; alp[0] = bb::ext_one();
-    for (uint32_t k = 1; k < VH_OPEN; k++) alp[k] = bb::mul(alp[k - 1], al);
-    FriCheck fri{hash, fp, log_big, VH_SALT, why};
-    if (int rc = fri.commit_phase(rd, ch)) return rc;
-    const size_t qstart = rd.pos;
-    {   // every query has the same length: skip to the final polynomial
-        const uint32_t nm[3] = {1, 1, VH_CH}, wsum[3] = {VH_RW, VH_TW, VH_CH * VH_D};
-        size_t qlen = 4 + 4;
-        for (int k = 0; k < 3; k++) qlen += 4 + 4 * (size_t)(nm[k] + wsum[k]) + 4 * (size_t)nm[k] * (1 + VH_SALT) + 4 + 32 * (size_t)log_big;
-        for (uint32_t r = 0; r < fri.n_rounds; r++) qlen += 16 + 4 + 4 * VH_SALT + 4 + 32 * (size_t)(log_big - 1 - r);
-        rd.pos += qlen * fp.num_queries;
-        if (rd.pos > len) rd.bad = true;
-    }
-    if (int rc = fri.final_poly(rd, ch)) return rc;
-    rd.pos = qstart;
-    std::vector<uint32_t> path((size_t)(log_big + 1) * 8);
-    const uint32_t w_r[1] = {VH_RW}, w_t[1] = {VH_TW}, w_q[VH_CH] = {VH_D, VH_D, VH_D, VH_D};
-    for (uint32_t q = 0; q < fp.num_queries; q++) {
-        const size_t index = ch.sample_bits(log_big);
-        uint32_t rrow[VH_RW], trow[VH_TW], qrow[VH_CH * VH_D];
-        // one salted BatchOpening: a truncated or non-canonical read rejects before the path is hashed
-        auto open = [&](const uint32_t* root, uint32_t n_mats, const uint32_t* widths, uint32_t* vals, const char* what) -> int {
-            uint32_t leaf[MAX_LEAF];
-            size_t leaf_len = 0;
-            if (!read_opening(rd, hash, n_mats, widths, VH_SALT, log_big, vals, leaf, &leaf_len, path.data())) return reject(why, 12, what);
-            if (rd.bad) return reject(why, 9, what);
-            if (!verify_opening(hash, root, index, leaf, leaf_len, path.data(), log_big)) return reject(why, 13, what);
-            return 0;
-        };
-        if (rd.u32() != 3) return reject(why, 12, "query shape");
-        if (int rc = open(root_r, 1, w_r, rrow, "randomization opening")) return rc;
-        if (int rc = open(root_t, 1, w_t, trow, "trace opening")) return rc;
-        if (int rc = open(root_q, VH_CH, w_q, qrow, "quotient opening")) return rc;
-        const uint32_t xi = bb::mul(gen, bb::pow(bb::two_adic_generator(log_big), rev_bits_host(index, log_big)));
-        Ext d0 = bb::inv(bb::sub(zeta, bb::ext_from_base(xi))), d1 = bb::inv(bb::sub(zeta_next, bb::ext_from_base(xi)));
-        Ext ro = bb::ext_zero();
-        uint32_t k = 0;
-        for (uint32_t j = 0; j < VH_RW; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(rrow[j])), d0)));
-        for (uint32_t j = 0; j < VH_TW; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(trow[j])), d0)));
-        for (uint32_t j = 0; j < VH_TW; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(trow[j])), d1)));
-        for (uint32_t j = 0; j < VH_CH * VH_D; j++, k++) ro = bb::add(ro, bb::mul(alp[k], bb::mul(bb::sub(opened[k], bb::ext_from_base(qrow[j])), d0)));
-        if (int rc = fri.query(rd, index, ro, path.data())) return rc;
-    }
-    if (why) why->clear();
-    return 0;
-}
-
-// ---- Pcs::verify of TwoAdicFriPcs over caller matrices (the prover half: pcs.hip.inc), host only.  The opened values arrive beside
-// the proof bytes (the FriProof section of the wire format); the FRI half is FriCheck, shared with the two fib verifiers.  The
-// transcript follows the test oracle's verifier (stark.c:216-294) generalised to the call's dimensions: opened values observed
-// round -> matrix -> point -> column, alpha sampled, and per query
-//   ro = sum over (matrix, point) pairs in that order, over columns c:  alpha^k (opened_k - row[c]) / (z - x),  k running on.
-// Everything that is a function of the SHAPE comes from pcs_layout (pcs_layout.h), which the device batch verifier reads too: the gates on
-// the arguments and their messages, each matrix's class, each round's tree depth, the classes with a point, each pair's matrix, place among
-// the opened values and alpha exponent, where the final polynomial lies.  Left here: what depends on a member's VALUES (canonical points off
-// the LDE coset, at most PCS_MAX_POINTS distinct; canonical opened values), the transcript, and the walk, which reads with Reader and
-// compares every count, width, depth and salt-length word with the layout's: nothing is followed.
-// hiding: HidingFriPcs::verify over the MerkleTreeHidingMmcs (the test oracle's hiding verifier, stark_hiding.c:380-457, generalised
-// likewise): log_h is the CALLER's log height, each input BatchOpening carries its matrices' salts (read_opening; stark_hiding.c:300-322),
-// each commit-phase opening its salt (FriCheck).  log_heights: mixed heights (pcs_layout.h), the tallest matrix's class starts the walk.
-static int pcs_verify_any(int hash, bool hiding, const FriParams& fp, uint32_t log_h, const unsigned* log_heights, const uint32_t* roots,
-                          const size_t* mats_per_round, const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points,
-                          const uint32_t* opened, const uint8_t* proof, size_t len, Challenger* chal, std::string* why) {
-    auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
-    if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
-    // (a hash that is neither is pcs_layout's to name, as it was named before this: a challenger's kind is always one of the two)
-    if ((hash == HASH_POSEIDON2 || hash == HASH_KECCAK) && chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
-    PLayout L;
-    const PcsShape shape{log_h, n_rounds, mats_per_round, widths, points_per_mat, 0, nullptr, log_heights};
-    if (int rc = pcs_layout(hash, hiding, fp, shape, &L, nullptr, why)) return rc;
+// Pcs::verify behind the gates: the walk over a finished layout.  zs: the distinct points (L.pair_slot indexes them), ov: the L.total
+// opened values in observation order, roots: one per input round, proof: the FriProof section.  The transcript follows the test oracle's
+// verifier (stark.c:216-294) generalised to the layout: opened values observed round -> matrix -> point -> column, alpha sampled, and per query
+//   ro = sum over (matrix, point) pairs in that order, over columns c:  alpha^k (opened_k - row[c]) / (z - x),  k running on
+// per class (by log_big_c); the tallest class starts the FRI walk, the others roll in.  Every count, width, depth and salt-length word is
+// compared with the layout's: nothing is followed (but Dialect::COUNTS).  Hiding: each input BatchOpening carries its matrices' salts
+// (read_opening; stark_hiding.c:300-322, 380-457), each commit-phase opening its salt (FriCheck).
+int pcs_walk(const PLayout& L, const FriParams& fp, const Dialect& d, const Ext* zs, const Ext* ov, const uint32_t* roots, const uint8_t* proof,
+             size_t len, Challenger& ch, std::string* why) {
     const uint32_t log_big = L.log_big, salt_words = L.salt;
     const size_t total = L.total;
-    Ext zs[PCS_MAX_POINTS];  // the distinct points; pair_slot: which of them a pair is opened at
-    size_t n_points = 0, pi = 0;
-    for (uint32_t r = 0; r < L.n_in; r++)
-        for (uint32_t m = 0; m < L.nm[r]; m++)
-            for (uint32_t p = 0; p < L.np[L.mat0[r] + m]; p++, pi++) {
-                const uint32_t* z = points + 4 * pi;
-                auto pw = [&] { return "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m) + " point " + std::to_string(p); };
-                for (int c = 0; c < 4; c++) if (z[c] >= bb::P) return bad(pw() + " is not a canonical field element");
-                if (pcs_point_on_lde_coset(z, log_big)) return bad(pw() + " lies on the LDE coset GENERATOR * <g_big>");
-                size_t k = 0;
-                while (k < n_points && memcmp(zs[k].c, z, 16)) k++;
-                if (k == n_points) {
-                    if (n_points == PCS_MAX_POINTS) return bad(pw() + ": more than " + std::to_string(PCS_MAX_POINTS) + " distinct opening points");
-                    memcpy(zs[n_points++].c, z, 16);
-                }
-                L.pair_slot[pi] = (uint8_t)k;
-            }
-    for (size_t i = 0; i < 4 * total; i++) if (opened[i] >= bb::P) return bad("pcs verify: opened value word " + std::to_string(i) + " is not a canonical field element");
-    Challenger& ch = *chal;
-    std::vector<Ext> ov(total), alp(total);
-    for (size_t i = 0; i < total; i++) { memcpy(ov[i].c, opened + 4 * i, 16); ch.observe_ext(ov[i]); }
+    auto at_round = [&](int code, uint32_t r, const char* general) { return reject(why, code, (d.named >> code) & 1u ? d.round_name[r] : general); };
+    std::vector<Ext> alp(total);
+    for (size_t i = 0; i < total; i++) ch.observe_ext(ov[i]);
     const Ext al = ch.sample_ext();
     alp[0] = bb::ext_one();
     for (size_t k = 1; k < total; k++) alp[k] = bb::mul(alp[k - 1], al);
     Reader rd{proof, len};
-    FriCheck fri{hash, fp, log_big, salt_words, why};
+    FriCheck fri{L.hash, fp, log_big, salt_words, why};
     if (int rc = fri.commit_phase(rd, ch)) return rc;
     const size_t qstart = rd.pos;
-    // the final polynomial lies behind the queries: PLayout::fpl_off, in 64 bits (its own holds a proof of less than 2^32 bytes)
-    const uint64_t fpl_off = (uint64_t)L.q_base + (uint64_t)L.q_len * L.nq;
-    if (4 * fpl_off > len) return reject(why, 9, "truncated proof");
-    rd.pos = (size_t)(4 * fpl_off);
+    if (d.final_at == Dialect::COUNTS) skip_queries_by_counts(rd, L);
+    else {  // behind the queries: PLayout::fpl_off, in 64 bits (its own holds a proof of less than 2^32 bytes)
+        const uint64_t fpl_off = (uint64_t)L.q_base + (uint64_t)L.q_len * L.nq;
+        if (d.final_at == Dialect::LAYOUT_CHECKED && 4 * fpl_off > len) return reject(why, 9, "truncated proof");
+        rd.pos = (size_t)(4 * fpl_off);
+    }
     if (int rc = fri.final_poly(rd, ch)) return rc;
     rd.pos = qstart;
-    static_assert(PCS_HIDING_MAX_MATS <= MAX_MATS && PCS_SALT <= MAX_SALT, "a salted round fits the opening reader's buffers");
     std::vector<uint32_t> path((size_t)(log_big + 1) * 8), row(L.row_words), leaf(L.row_words + PCS_MAX_MATS * salt_words);
     std::vector<size_t> hh(2 * PCS_MAX_MATS), lw(2 * PCS_MAX_MATS);
     size_t leaf_len = 0;
     const uint32_t gen = bb::to_monty(bb::GEN);
-    // one reduced opening per class (by log_big_c); the tallest class is the walk's start, the others roll in
-    Ext ro_c[bb::TWO_ADICITY + 1];
-    uint32_t xi_c[bb::TWO_ADICITY + 1];
+    // per class (by log_big_c): its reduced opening, its point x, and 1 / (z - x) of each distinct point, inverted when a pair first asks
+    Ext ro_c[bb::TWO_ADICITY + 1], dz_c[bb::TWO_ADICITY + 1][PCS_MAX_POINTS];
+    uint32_t xi_c[bb::TWO_ADICITY + 1], have_c[bb::TWO_ADICITY + 1];
     std::vector<std::pair<uint32_t, Ext>> rolls;
     for (uint32_t q = 0; q < fp.num_queries; q++) {
         const size_t index = ch.sample_bits(log_big);
         for (uint32_t lb = 0; lb <= log_big; lb++) {
             if (!((L.class_mask >> lb) & 1u)) continue;
             ro_c[lb] = bb::ext_zero();
+            have_c[lb] = 0;
             xi_c[lb] = bb::mul(gen, bb::pow(bb::two_adic_generator(lb), rev_bits_host(index >> (log_big - lb), lb)));
         }
         if (rd.u32() != L.n_in) return reject(why, 12, "query shape");  // one BatchOpening per commitment round
@@ -468,21 +235,23 @@ static int pcs_verify_any(int hash, bool hiding, const FriParams& fp, uint32_t l
             const size_t nm = L.nm[r], m0 = L.mat0[r];
             const uint32_t log_big_r = L.log_big_r[r];  // this round's tree
             const size_t index_r = index >> (log_big - log_big_r);
-            if (!read_opening(rd, hash, (uint32_t)nm, L.width + m0, salt_words, log_big_r, row.data(), leaf.data(), &leaf_len, path.data()))
-                return reject(why, 12, "query shape");
-            if (rd.bad) return reject(why, 9, "truncated proof");
+            if (!read_opening(rd, L.hash, (uint32_t)nm, L.width + m0, salt_words, log_big_r, row.data(), leaf.data(), &leaf_len, path.data()))
+                return at_round(12, r, "query shape");
+            if (d.stop_on_flag && rd.bad) return at_round(9, r, "truncated proof");
             size_t n = 0;  // the salts as width-4 matrices, each behind its matrix
             for (size_t m = m0; m < m0 + nm; m++) {
                 hh[n] = (size_t)1 << L.log_big_m[m]; lw[n++] = L.width[m];
                 if (salt_words) { hh[n] = hh[n - 1]; lw[n++] = salt_words; }
             }
-            if (mmcs_verify_batch(hash, roots + 8 * r, hh.data(), lw.data(), n, index_r, leaf.data(), path.data(), log_big_r, nullptr, false) != 0)
-                return reject(why, 13, "input opening");
+            if (mmcs_verify_batch(L.hash, roots + 8 * r, hh.data(), lw.data(), n, index_r, leaf.data(), path.data(), log_big_r, nullptr, false) != 0)
+                return at_round(13, r, "input opening");
             size_t off = 0;
             for (size_t mi = m0; mi < m0 + nm; mi++) {
                 const uint32_t lb = L.log_big_m[mi];
                 for (uint32_t p = 0; p < L.np[mi]; p++, pair++) {
-                    const Ext dz = bb::inv(bb::sub(zs[L.pair_slot[pair]], bb::ext_from_base(xi_c[lb])));
+                    const uint32_t s = L.pair_slot[pair];
+                    if (!((have_c[lb] >> s) & 1u)) { dz_c[lb][s] = bb::inv(bb::sub(zs[s], bb::ext_from_base(xi_c[lb]))); have_c[lb] |= 1u << s; }
+                    const Ext dz = dz_c[lb][s];
                     const Ext *a_k = &alp[L.pair_aoff[pair]], *o_k = &ov[L.pair_off[pair]];  // the pair's alpha powers (its class's counter) and opened values
                     for (size_t c = 0; c < L.width[mi]; c++)
                         ro_c[lb] = bb::add(ro_c[lb], bb::mul(a_k[c], bb::mul(bb::sub(o_k[c], bb::ext_from_base(row[off + c])), dz)));
@@ -496,6 +265,168 @@ static int pcs_verify_any(int hash, bool hiding, const FriParams& fp, uint32_t l
     }
     if (why) why->clear();
     return 0;
+}
+
+}  // namespace
+
+// check_parameters for either wire format, with that format's own messages (the device verifier refuses what these refuse)
+int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriParams& fp, std::string* why) {
+    if (hiding)
+        return check_parameters(hash, log_n, log_n + 1, fp, why, "bad parameters: LDE height outside the two-adic subgroup",
+                                "bad parameters: log_final_poly_len must be below the randomized trace's log height");
+    return check_parameters(hash, log_n, log_n, fp, why, "bad parameters: LDE height outside [2^2, 2^27]",
+                            "bad parameters: log_final_poly_len must be below the trace's log height");
+}
+
+// ---- the fib_air verifiers: p3_uni_stark::verify for FibonacciAir over TwoAdicFriPcs (wire format 1, prover.hip) and, with SC::Pcs::ZK,
+// over HidingFriPcs + MerkleTreeHidingMmcs as the reference configures them (wire format 2, prover_hiding.hip.inc;
+// native/src/fib_air.rs:40-72; [UPSTREAM-RECALL] in structure, parity unpinned).  A fib_air proof is a PCS proof of a fixed shape behind a
+// header: magic, version, log_n, the roots, the opened values.  What the two formats do not share is this table; verify_fib does the rest.
+namespace {
+constexpr uint32_t FIB_MAX_ROUNDS = 3, FIB_MAX_MATS = 6, FIB_MAX_OPENED = 36, FIB_MAX_CHUNKS = 4;
+struct FibFormat {
+    uint32_t version;
+    bool hiding;        // the salted MMCS, the trace committed at twice its height: the transcript opens with log_n + 1, then log_n
+    uint32_t n_rounds;  // the header's roots: trace, quotient[, randomization], observed in that order: the first, the public values,
+                        // alpha, then the others, zeta
+    // the commitment rounds in PROOF order as a PcsShape: each round's root among the header's, its matrices, their widths, each
+    // matrix's points and each (matrix, point) pair's slot (0: zeta, 1: zeta g)
+    uint32_t root_of[FIB_MAX_ROUNDS];
+    size_t mats[FIB_MAX_ROUNDS], widths[FIB_MAX_MATS], points[FIB_MAX_MATS];
+    uint32_t slots[FIB_MAX_MATS + 1];
+    // the header's opened values, in the proof's (and the transcript's) order: n > 0 is the count word n and n extension elements behind
+    // it, n < 0 the bare count word -n; 0 ends
+    int grammar[9];
+    uint32_t t_loc, t_nxt, chunks, log_chunks;  // among the opened values: the trace at zeta and at zeta g, the 2^log_chunks quotient chunks
+    Dialect dialect;
+};
+// format 1: trace (2 columns) at zeta and zeta g, the quotient (one chunk, 4 columns: an extension element's coordinates) at zeta
+constexpr FibFormat FIB_PLAIN{1, false, 2, {0, 1}, {1, 1}, {2, 4}, {2, 1}, {0, 1, 0}, {2, 2, -1, 4}, 0, 2, 4, 0, DIALECT_FIB1};
+// format 2, 4 random codewords: the randomization round (4 + 4 columns) first, the trace with its 4 random columns, 4 blinded chunks
+constexpr FibFormat FIB_HIDING{2, true, 3, {2, 0, 1}, {1, 1, 4}, {8, 6, 4, 4, 4, 4}, {1, 2, 1, 1, 1, 1}, {0, 0, 1, 0, 0, 0, 0},
+                               {8, 6, 6, -4, 4, 4, 4, 4}, 8, 14, 20, 2, DIALECT_FIB2};
+constexpr uint32_t opened_of(const FibFormat& f) { uint32_t n = 0; for (int g : f.grammar) if (g > 0) n += (uint32_t)g; return n; }
+static_assert(opened_of(FIB_PLAIN) == 8 && opened_of(FIB_HIDING) == FIB_MAX_OPENED && (1u << FIB_HIDING.log_chunks) <= FIB_MAX_CHUNKS &&
+              FIB_MAX_ROUNDS <= PCS_MAX_ROUNDS, "what a grammar reads fits verify_fib's arrays");
+
+// The FibonacciAir constraints at zeta (fib_air.rs:232-264), folded with alpha, against the quotient recomposed from its chunks:
+// sum_c zps_c(zeta) chunk_c(zeta) (the blinding of format 2 cancels in the sum).  Chunk cosets D_c = s_c <g_n> with s_c^n = GENERATOR^n w^c,
+// w of order n_chunks; zps_c(zeta) = prod_{j != c} (zeta^n - s_j^n) / (s_c^n - s_j^n): with one chunk the product is empty.
+bool fib_constraints_hold(const Ext* t_loc, const Ext* t_nxt, const Ext* chunks, uint32_t log_chunks, const uint32_t pis[3], Ext alpha, Ext zeta,
+                          uint32_t log_n) {
+    const uint64_t n = 1ull << log_n;
+    const uint32_t n_chunks = 1u << log_chunks;
+    const Ext zn = bb::pow(zeta, n), zh = bb::sub(zn, bb::ext_one());
+    const Ext ginv = bb::ext_from_base(bb::inv(bb::two_adic_generator(log_n)));
+    const Ext first = bb::mul(zh, bb::inv(bb::sub(zeta, bb::ext_one())));
+    const Ext last = bb::mul(zh, bb::inv(bb::sub(zeta, ginv)));
+    const Ext trans = bb::sub(zeta, ginv);
+    const Ext c[5] = {bb::mul(first, bb::sub(t_loc[0], bb::ext_from_base(pis[0]))), bb::mul(first, bb::sub(t_loc[1], bb::ext_from_base(pis[1]))),
+                      bb::mul(trans, bb::sub(t_loc[1], t_nxt[0])), bb::mul(trans, bb::sub(bb::add(t_loc[0], t_loc[1]), t_nxt[1])),
+                      bb::mul(last, bb::sub(t_loc[1], bb::ext_from_base(pis[2])))};
+    Ext folded = bb::ext_zero();
+    for (auto& ck : c) folded = bb::add(bb::mul(folded, alpha), ck);
+    uint32_t sn[FIB_MAX_CHUNKS];
+    { uint32_t gn = bb::pow(bb::to_monty(bb::GEN), n), w = bb::two_adic_generator(log_chunks), p = bb::ONE;
+      for (uint32_t k = 0; k < n_chunks; k++) { sn[k] = bb::mul(gn, p); p = bb::mul(p, w); } }
+    Ext quot = bb::ext_zero();
+    for (uint32_t ci = 0; ci < n_chunks; ci++) {
+        uint32_t kc = bb::ONE;
+        Ext zp = bb::ext_one();
+        for (uint32_t j = 0; j < n_chunks; j++)
+            if (j != ci) { kc = bb::mul(kc, bb::sub(sn[ci], sn[j])); zp = bb::mul(zp, bb::sub(zn, bb::ext_from_base(sn[j]))); }
+        zp = bb::scale(zp, bb::inv(kc));
+        Ext v = bb::ext_zero();  // the chunk's 4 columns are an extension element's coordinates
+        for (int e = 0; e < 4; e++) { Ext be = bb::ext_zero(); be.c[e] = bb::ONE; v = bb::add(v, bb::mul(be, chunks[ci * 4 + e])); }
+        quot = bb::add(quot, bb::mul(zp, v));
+    }
+    return bb::eq(bb::mul(folded, bb::inv(zh)), quot);
+}
+
+// 0 = accept; otherwise a positive code naming the failed check (1-4 the header, 10 the constraints, the others pcs_walk's and FriCheck's).
+int verify_fib(const FibFormat& f, const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
+               const FriParams& fp, std::string* why, int hash) {
+    if (int rc = verify_check_parameters(hash, f.hiding, log_n, fp, why)) return rc;
+    // pcs_layout's gates are verify_check_parameters' over again and refuse nothing it admits (before the first byte is read, so that
+    // any bytes show it: test_no_pcs_refusal_leaks_out_of_a_fib_verifier)
+    PLayout L;
+    if (int rc = pcs_layout(hash, f.hiding, fp, PcsShape{log_n, f.n_rounds, f.mats, f.widths, f.points, 2, f.slots, nullptr}, &L, nullptr, why)) return rc;
+    Reader rd{proof, len};
+    if (rd.u32() != 0x42463350u || rd.u32() != f.version) return reject(why, 1, "bad header");
+    if (rd.u32() != log_n) return reject(why, 2, "degree_bits mismatch");
+    uint32_t hdr_roots[FIB_MAX_ROUNDS][8], roots[FIB_MAX_ROUNDS * 8];
+    for (uint32_t r = 0; r < f.n_rounds; r++) rd.digests(hash, hdr_roots[r], 1);
+    Ext opened[FIB_MAX_OPENED];
+    uint32_t k = 0;
+    for (const int* g = f.grammar; *g; g++) {
+        if (rd.u32() != (uint32_t)std::abs(*g)) return reject(why, 3, "opened values shape");
+        for (int i = 0; i < *g; i++) opened[k++] = rd.ext();
+    }
+    if (rd.bad) return reject(why, 4, "truncated proof");
+    const uint32_t pis[3] = {bb::to_monty((uint32_t)(a_pub % bb::P)), bb::to_monty((uint32_t)(b_pub % bb::P)), bb::to_monty((uint32_t)(x_pub % bb::P))};
+    Challenger ch(hash);
+    ch.observe(bb::to_monty(log_n + f.hiding)); ch.observe(bb::to_monty(log_n));
+    ch.observe_digest(hdr_roots[0]); ch.observe_n(pis, 3);
+    const Ext alpha = ch.sample_ext();
+    for (uint32_t r = 1; r < f.n_rounds; r++) ch.observe_digest(hdr_roots[r]);
+    const Ext zeta = ch.sample_ext();
+    if (!fib_constraints_hold(opened + f.t_loc, opened + f.t_nxt, opened + f.chunks, f.log_chunks, pis, alpha, zeta, log_n))
+        return reject(why, 10, "OodEvaluationMismatch");
+    // The PCS half, entered below pcs_verify_any's gates on the points: zeta comes from the proof's own bytes, and where it lies is no
+    // argument of this call.
+    const Ext zs[2] = {zeta, bb::scale(zeta, bb::two_adic_generator(log_n))};
+    for (uint32_t r = 0; r < f.n_rounds; r++) memcpy(roots + 8 * r, hdr_roots[f.root_of[r]], 32);
+    return pcs_walk(L, fp, f.dialect, zs, opened, roots, proof + rd.pos, len - rd.pos, ch, why);
+}
+}  // namespace
+
+int verify_fib_air(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n, const FriParams& fp,
+                   std::string* why, int hash) {
+    return verify_fib(FIB_PLAIN, proof, len, a_pub, b_pub, x_pub, log_n, fp, why, hash);
+}
+int verify_fib_air_hiding(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n, const FriParams& fp,
+                          std::string* why, int hash) {
+    return verify_fib(FIB_HIDING, proof, len, a_pub, b_pub, x_pub, log_n, fp, why, hash);
+}
+
+// ---- Pcs::verify of TwoAdicFriPcs / HidingFriPcs over caller matrices (the prover half: pcs.hip.inc, pcs_hiding.hip.inc), host only.  The
+// opened values arrive beside the proof bytes (the FriProof section of the wire format).  Everything that is a function of the SHAPE comes
+// from pcs_layout (pcs_layout.h), which the device batch verifier reads too: the gates on the arguments and their messages, each matrix's
+// class, each round's tree depth, the classes with a point, each pair's matrix, place among the opened values and alpha exponent, where
+// the final polynomial lies.  Here: the gates on the arguments and on a member's VALUES (canonical points off the LDE coset, at most
+// PCS_MAX_POINTS distinct; canonical opened values); then pcs_walk.  hiding: log_h is the CALLER's log height.  log_heights: mixed
+// heights (pcs_layout.h).
+static int pcs_verify_any(int hash, bool hiding, const FriParams& fp, uint32_t log_h, const unsigned* log_heights, const uint32_t* roots,
+                          const size_t* mats_per_round, const size_t* widths, size_t n_rounds, const size_t* points_per_mat, const uint32_t* points,
+                          const uint32_t* opened, const uint8_t* proof, size_t len, Challenger* chal, std::string* why) {
+    auto bad = [&](const std::string& msg) { if (why) *why = msg; return (int)ERR_BAD_ARG; };
+    if (!roots || !mats_per_round || !widths || !points_per_mat || !points || !opened || !proof || !chal) return bad("pcs verify: null argument");
+    // (a hash that is neither is pcs_layout's to name, as it was named before this: a challenger's kind is always one of the two)
+    if ((hash == HASH_POSEIDON2 || hash == HASH_KECCAK) && chal->kind != hash) return bad("pcs verify: the challenger belongs to another hash configuration");
+    PLayout L;
+    const PcsShape shape{log_h, n_rounds, mats_per_round, widths, points_per_mat, 0, nullptr, log_heights};
+    if (int rc = pcs_layout(hash, hiding, fp, shape, &L, nullptr, why)) return rc;
+    Ext zs[PCS_MAX_POINTS];  // the distinct points; pair_slot: which of them a pair is opened at
+    size_t n_points = 0, pi = 0;
+    for (uint32_t r = 0; r < L.n_in; r++)
+        for (uint32_t m = 0; m < L.nm[r]; m++)
+            for (uint32_t p = 0; p < L.np[L.mat0[r] + m]; p++, pi++) {
+                const uint32_t* z = points + 4 * pi;
+                auto pw = [&] { return "pcs verify: round " + std::to_string(r) + " matrix " + std::to_string(m) + " point " + std::to_string(p); };
+                for (int c = 0; c < 4; c++) if (z[c] >= bb::P) return bad(pw() + " is not a canonical field element");
+                if (pcs_point_on_lde_coset(z, L.log_big)) return bad(pw() + " lies on the LDE coset GENERATOR * <g_big>");
+                size_t k = 0;
+                while (k < n_points && memcmp(zs[k].c, z, 16)) k++;
+                if (k == n_points) {
+                    if (n_points == PCS_MAX_POINTS) return bad(pw() + ": more than " + std::to_string(PCS_MAX_POINTS) + " distinct opening points");
+                    memcpy(zs[n_points++].c, z, 16);
+                }
+                L.pair_slot[pi] = (uint8_t)k;
+            }
+    for (size_t i = 0; i < 4 * (size_t)L.total; i++) if (opened[i] >= bb::P) return bad("pcs verify: opened value word " + std::to_string(i) + " is not a canonical field element");
+    std::vector<Ext> ov(L.total);
+    memcpy(ov.data(), opened, 16 * (size_t)L.total);
+    return pcs_walk(L, fp, DIALECT_PCS, zs, ov.data(), roots, proof, len, *chal, why);
 }
 
 int pcs_verify(int hash, const FriParams& fp, uint32_t log_h, const uint32_t* roots, const size_t* mats_per_round, const size_t* widths,
