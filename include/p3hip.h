@@ -122,12 +122,16 @@ int p3hip_fib_trace_dev(uint64_t a, uint64_t b, size_t n, uint32_t *d_out, void 
 /* n independent width-16 states, in place. */
 int p3hip_poseidon2_permute_dev(uint32_t *d_states, size_t n, void *stream);
 int p3hip_poseidon2_permute(uint32_t *states, size_t n);
-/* The permutation exists in two arithmetic forms that must agree word for word: int32 Montgomery (variant 0) and exact
- * integer arithmetic in fp64 (variant 1: what the large tree layers run).  Diagnostics / tests:
- *   _variant_dev  the chosen form on n states in place;
- *   _f64_probe    the fp64 form on integer-valued DOUBLES (16 per state) of any magnitude its contract allows, canonical
+/* The permutation exists in four forms that must agree word for word: int32 Montgomery, one state per lane (variant 0); exact
+ * integer arithmetic in fp64, one state per lane (variant 1: what the large tree layers run); the fp64 arithmetic with one state
+ * per DPP quad (variant 2: layers of 2^12 .. 2^15 digests under the latency profile); int32 with one state per 16-lane row (variant
+ * 3: layers below 2^12, tree tops, the transcript).  Diagnostics / tests:
+ *   _variant_dev  the chosen form on n <= 2^26 states in place, all sixteen words of each; the idle quads / rows of the last
+ *                 workgroup run the permutation on zeros, as the tree kernels do;
+ *   _f64_probe    the fp64 forms on integer-valued DOUBLES (16 per state) of any magnitude the contract allows, canonical
  *                 Montgomery words out — mode 0: whole permutation (|v| <= 2^33), 1: the 13 internal rounds (|v| <= 2^37),
- *                 2: the modular reduction alone. */
+ *                 2: the modular reduction alone, 3: whole permutation, one state per quad (the contract of mode 0).
+ * Both refuse an unknown variant / mode with P3HIP_ERR_BAD_ARG; n = 0 is a no-op. */
 int p3hip_poseidon2_permute_variant_dev(uint32_t *d_states, size_t n, int variant, void *stream);
 int p3hip_poseidon2_f64_probe_dev(const double *d_in, uint32_t *d_out, size_t n, int mode, void *stream);
 
@@ -176,6 +180,11 @@ int p3hip_poseidon2_f64_probe_dev(const double *d_in, uint32_t *d_out, size_t n,
  *  41  mulm(a, a * pinv, b, ..)     a, b                        1        as 40, aP formed on the device
  *  42  word_centered(r)             r                           1 word   integer |r| <= P/2 + 2^22; = r mod P in [0, P)
  *  43  word_any(x, ..)              x                           1 word   integer |x| < 2^43; = x mod P in [0, P)
+ *  48  add_scaled_pow2(tot, x, m)   tot, x, m                   1        the integer multipliers of the quad form's diagonal: m in
+ *                                                                        {-2, 1, 2, 3, 4, -3, -4, -15, 15}, integers |tot| <= P/2 + 1,
+ *                                                                        |x| <= 15^3 35 (P/2 + 2^9) + 241 (P/2 + 1) < 2^47; = tot + m x
+ *  49  sbox7(x, ..)                 x                           1        integer |x| <= 35 (P - 1) + P < 2^37 (the first round's
+ *                                                                        inputs on canonical states); |result| <= P/2 + 2^9
  * The uniform operands the fp64 functions take besides (".." above: the magic-number pair, -(P - 1), 1 / P, -1/2 + 2^-33) are formed
  * as the kernels form them.  tests/field_ref.py holds the reference of every op and the exact model of every fp64 one. */
 #define P3HIP_FP_ADD 1
@@ -210,6 +219,8 @@ int p3hip_poseidon2_f64_probe_dev(const double *d_in, uint32_t *d_out, size_t n,
 #define P3HIP_FP_MULM_DEV 41
 #define P3HIP_FP_WORD_CENTERED 42
 #define P3HIP_FP_WORD_ANY 43
+#define P3HIP_FP_ADD_SCALED_INT 48
+#define P3HIP_FP_SBOX7_WIDE 49
 int p3hip_field_probe_dev(int op, const void *d_in, void *d_out, size_t n, void *stream);
 int p3hip_field_probe_host(int op, const void *in, void *out, size_t n);
 
@@ -302,6 +313,19 @@ int p3hip_mmcs_commit_into_dev(int hash, const uint32_t *const *d_mats, const si
                                size_t n_mats, uint32_t *d_layers, p3hip_tree_t **tree_out, void *stream);
 /* KeccakF::permute_mut on n independent [u64; 25] states in device memory (p3-keccak's KeccakF, fib_air.rs:32) */
 int p3hip_keccak_f_dev(uint64_t *d_states, size_t n, void *stream);
+/* Diagnostics / tests: the three formulations of Keccak-f on n <= 2^24 states of 25 words, in place.  variant 0: one state per lane,
+ * all 25 words (what p3hip_keccak_f_dev runs); 1: the digest form every leaf and compression runs (first round peeled, the last
+ * computes row 0 only) — words 0..3 of each state are written, words 4..24 of the buffer stay as they were; 2: the lane-cooperative
+ * form, one state per wave, all 25 words.  An unknown variant is refused with P3HIP_ERR_BAD_ARG; n = 0 is a no-op. */
+int p3hip_keccak_f_variant_dev(uint64_t *d_states, size_t n, int variant, void *stream);
+/* Diagnostics / tests: ONE 2-to-1 compression layer through the PRODUCTION kernel of a named form, launched unchanged with the
+ * geometry a commitment gives it: d_in = 2 n_out digests of 8 words, d_out = n_out digests.  hash 0 (Poseidon2): variant 0 = int32 per
+ * lane (the injected layers' kernel, without injection), 1 = fp64 per lane, 2 = fp64 per quad, 3 = one level of the 16-lane levels
+ * kernel.  hash 1 (Keccak): 0 = per lane (no injection), 1 = one level of the per-lane levels kernel, 2 = one level of the per-wave
+ * levels kernel.  The entry stages the two layers back to back in a 16-byte-aligned buffer of its own and synchronises `stream`.
+ * Refused with P3HIP_ERR_BAD_ARG: an unknown hash or variant, a null pointer, n_out > 2^24, and for the levels kernels an n_out that is
+ * not a power of two or exceeds 2^15 (nothing is padded).  n_out = 0 is a no-op. */
+int p3hip_compress_layer_variant_dev(int hash, int variant, const uint32_t *d_in, uint32_t *d_out, size_t n_out, void *stream);
 
 /* ---- fib_air prover: p3_uni_stark::prove(&config, &FibonacciAir{}, trace, &pis) as called at
  *      native/src/fib_air.rs:70, for StarkConfig<TwoAdicFriPcs<BabyBear, Dft, Poseidon2 Mmcs, ExtensionMmcs>,

@@ -317,7 +317,10 @@ int p3hip_poseidon2_permute(uint32_t* states, size_t n) {
 int p3hip_poseidon2_permute_variant_dev(uint32_t* d_states, size_t n, int variant, void* stream) {
     return guarded([&]() -> int {
         if (n && !d_states) return fail(ERR_BAD_ARG, "null state pointer");
-        if (variant != 0 && variant != 1) return fail(ERR_BAD_ARG, "poseidon2 variant: 0 = int32, 1 = fp64");
+        if (variant < 0 || variant > 3)
+            return fail(ERR_BAD_ARG, "poseidon2 variant: 0 = int32, 1 = fp64, 2 = fp64 one state per quad, 3 = int32 one state per 16 lanes");
+        if (n > ((size_t)1 << 26)) return fail(ERR_BAD_ARG, "poseidon2 variant: at most 2^26 states per call");
+        if (!n) return OK;
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -327,7 +330,10 @@ int p3hip_poseidon2_permute_variant_dev(uint32_t* d_states, size_t n, int varian
 int p3hip_poseidon2_f64_probe_dev(const double* d_in, uint32_t* d_out, size_t n, int mode, void* stream) {
     return guarded([&]() -> int {
         if (n && (!d_in || !d_out)) return fail(ERR_BAD_ARG, "null pointer");
-        if (mode < 0 || mode > 2) return fail(ERR_BAD_ARG, "probe mode: 0 = permutation, 1 = internal rounds, 2 = reduce");
+        if (mode < 0 || mode > 3)
+            return fail(ERR_BAD_ARG, "probe mode: 0 = permutation, 1 = internal rounds, 2 = reduce, 3 = permutation, one state per quad");
+        if (n > ((size_t)1 << 26)) return fail(ERR_BAD_ARG, "probe: at most 2^26 states per call");
+        if (!n) return OK;
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -400,6 +406,29 @@ int p3hip_keccak_f_dev(uint64_t* d_states, size_t n, void* stream) {
         int rc = get_context(&cx);
         if (rc) return rc;
         return keccak_f_states((hipStream_t)stream, d_states, n);
+    });
+}
+// test / diagnostics entries of the three formulations of Keccak-f and of the compression layers' production kernels
+int p3hip_keccak_f_variant_dev(uint64_t* d_states, size_t n, int variant, void* stream) {
+    return guarded([&]() -> int {
+        if (!d_states && n) return fail(ERR_BAD_ARG, "keccak_f variant: null states");
+        if (variant < 0 || variant > 2) return fail(ERR_BAD_ARG, "keccak_f variant: 0 = permute, 1 = permute_digest, 2 = f_coop");
+        if (n > ((size_t)1 << 24)) return fail(ERR_BAD_ARG, "keccak_f variant: at most 2^24 states per call");
+        if (!n) return OK;
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        return keccak_f_states_variant((hipStream_t)stream, d_states, n, variant);
+    });
+}
+int p3hip_compress_layer_variant_dev(int hash, int variant, const uint32_t* d_in, uint32_t* d_out, size_t n_out, void* stream) {
+    return guarded([&]() -> int {
+        int rc = compress_layer_variant_check(hash, variant, d_in, d_out, n_out);  // refused before the thread's device context is looked up
+        if (rc || !n_out) return rc;
+        Context* cx;
+        rc = get_context(&cx);
+        if (rc) return rc;
+        return compress_layer_variant((hipStream_t)stream, hash, variant, d_in, d_out, n_out);
     });
 }
 int p3hip_mmcs_root(const p3hip_tree_t* tree, uint32_t root_out[8], void* stream) {

@@ -32,7 +32,8 @@ constexpr OpInfo OPS[] = {
     {P3HIP_FP_MULMOD_M_DEV, "mulmod_m (aP on device)", 2, 1, true}, {P3HIP_FP_ADD_SCALED_POW2, "add_scaled_pow2", 3, 1, true},
     {P3HIP_FP_SBOX7, "sbox7", 1, 1, true}, {P3HIP_FP_STORE_ELEM, "store_elem", 1, 1, true}, {P3HIP_FP_MULM, "mulm", 3, 1, true},
     {P3HIP_FP_MULM_DEV, "mulm (aP on device)", 2, 1, true}, {P3HIP_FP_WORD_CENTERED, "word_centered", 1, 1, true},
-    {P3HIP_FP_WORD_ANY, "word_any", 1, 1, true},
+    {P3HIP_FP_WORD_ANY, "word_any", 1, 1, true}, {P3HIP_FP_ADD_SCALED_INT, "add_scaled_pow2 (integer multiplier)", 3, 1, true},
+    {P3HIP_FP_SBOX7_WIDE, "sbox7 (first-round inputs)", 1, 1, true},
 };
 const OpInfo* find_op(int op) {
     for (const OpInfo& o : OPS)
@@ -89,6 +90,8 @@ __device__ __forceinline__ double probe_f64(int op, const double* a, const p2f::
     case P3HIP_FP_MULM_DEV: return narrow64::mulm(a[0], a[0] * un.pinv, a[1], nk, un.npm1);
     case P3HIP_FP_WORD_CENTERED: return (double)narrow64::word_centered(a[0]);
     case P3HIP_FP_WORD_ANY: return (double)narrow64::word_any(a[0], un);
+    case P3HIP_FP_ADD_SCALED_INT: return p2f::add_scaled_pow2(a[0], a[1], a[2]);  // the same functions, at the operands p2q gives them
+    case P3HIP_FP_SBOX7_WIDE: return p2f::sbox7(a[0], mk, npm1, pinv);
     default: return 0.0;
     }
 }

@@ -64,5 +64,9 @@ int poseidon2_permute_states(hipStream_t stream, uint32_t* d_states, uint64_t n)
 int poseidon2_f64_probe(hipStream_t stream, const double* d_in, uint32_t* d_out, uint64_t n, int mode);
 int poseidon2_permute_states_variant(hipStream_t stream, uint32_t* d_states, uint64_t n, int variant);
 int keccak_f_states(hipStream_t stream, uint64_t* d_states, uint64_t n);
+int keccak_f_states_variant(hipStream_t stream, uint64_t* d_states, uint64_t n, int variant);
+// one compression layer through the production kernel of a named form (test entry, mmcs.hip)
+int compress_layer_variant_check(int kind, int variant, const uint32_t* d_in, const uint32_t* d_out, uint64_t n_out);  // arguments only: no GPU call
+int compress_layer_variant(hipStream_t stream, int kind, int variant, const uint32_t* d_in, uint32_t* d_out, uint64_t n_out);
 
 }  // namespace p3

@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) leaf_hash_f64_kernel(const uint32_t* mat,
             if (k + i < width) s[i] = p2f::load_elem(row[k + i]);
         p2f::permute(s);
         if (k + 8 < width) {
-            // keep magnitudes small between absorptions (the next permutation assumes |s| <= 2^33)
+            // keep magnitudes small between absorptions (the next permutation assumes |s| <= 2^32)
 #pragma unroll
             for (int i = 0; i < 16; i++) s[i] = p2f::reduce(s[i]);
         }
@@ -396,7 +396,7 @@ __global__ void poseidon2_permute_f64_kernel(uint32_t* states, uint64_t n) {
 }
 
 // Test probe of the fp64 arithmetic: integer-valued doubles in (any magnitude the contract of the probed part allows),
-// canonical Montgomery words out.  mode 0: the whole permutation (|v| <= 2^33); mode 1: the 13 internal rounds only
+// canonical Montgomery words out.  mode 0: the whole permutation (|v| <= 2^33: see p2f::permute); mode 1: the 13 internal rounds only
 // (|v| <= 2^37 — the magnitudes the external layer can hand them, which no u32 input of the permutation reaches
 // deterministically); mode 2: reduce() alone, lane by lane (rounding ties of the quotient estimate).
 __global__ void poseidon2_f64_probe_kernel(const double* in, uint32_t* out, uint64_t n, int mode) {
@@ -414,16 +414,67 @@ __global__ void poseidon2_f64_probe_kernel(const double* in, uint32_t* out, uint
 #pragma unroll
     for (int k = 0; k < 16; k++) out[i * 16 + k] = p2f::store_elem(s[k]);
 }
+// mode 3 of the probe: p2q::permute on the same doubles, lane q of a quad holding elements 4q .. 4q+3 (the mode-0 contract).  Idle
+// quads of the last workgroup run the permutation on zeros, as in compress_layer_q4_kernel.
+__global__ void __launch_bounds__(256) poseidon2_q4_probe_kernel(const double* in, uint32_t* out, uint64_t n) {
+    const uint32_t q = threadIdx.x & 3u;
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const bool act = i < n;
+    const p2q::LaneConsts lc = p2q::lane_consts(q);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) s[k] = in[i * 16 + 4 * q + k];
+    }
+    p2q::permute(s, lc, q == 0);
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) out[i * 16 + 4 * q + k] = p2f::store_elem(s[k]);
+    }
+}
 int poseidon2_f64_probe(hipStream_t stream, const double* d_in, uint32_t* d_out, uint64_t n, int mode) {
     if (!n) return OK;
-    hipLaunchKernelGGL(poseidon2_f64_probe_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_in, d_out, n, mode);
+    if (mode == 3) hipLaunchKernelGGL(poseidon2_q4_probe_kernel, dim3((uint32_t)((n * 4 + 255) / 256)), dim3(256), 0, stream, d_in, d_out, n);
+    else hipLaunchKernelGGL(poseidon2_f64_probe_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_in, d_out, n, mode);
     P3_HIP(hipGetLastError());
     return OK;
 }
-// variant: 0 = int32 Montgomery form, 1 = fp64 form (the two must agree word for word)
+// Test forms of the two lane-sharing permutations on whole states, all sixteen words written back: one state per DPP quad
+// (p2q::permute, variant 2) and one per 16-lane row (p2c::permute, variant 3).  The idle quads / rows of the last workgroup run the
+// permutation on zeros, as the tree kernels do: every lane takes part in the exchanges.
+__global__ void __launch_bounds__(256) poseidon2_permute_q4_kernel(uint32_t* states, uint64_t n) {
+    const uint32_t q = threadIdx.x & 3u;
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const bool act = i < n;
+    const p2q::LaneConsts lc = p2q::lane_consts(q);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    uint4* mine = reinterpret_cast<uint4*>(states + (act ? i : 0) * 16 + 4 * q);
+    if (act) {
+        const uint4 w = *mine;
+        s[0] = p2f::load_elem(w.x); s[1] = p2f::load_elem(w.y); s[2] = p2f::load_elem(w.z); s[3] = p2f::load_elem(w.w);
+    }
+    p2q::permute(s, lc, q == 0);
+    if (act) {
+        const p2f::MagicRegs smk = p2f::magic_regs();
+        *mine = make_uint4(p2f::store_elem(s[0], smk), p2f::store_elem(s[1], smk), p2f::store_elem(s[2], smk), p2f::store_elem(s[3], smk));
+    }
+}
+__global__ void __launch_bounds__(256) poseidon2_permute_coop_kernel(uint32_t* states, uint64_t n) {
+    const uint32_t lane16 = threadIdx.x & 15;
+    const p2c::LaneConst lc = p2c::lane_constants(lane16);
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const bool act = i < n;
+    uint32_t v = act ? states[i * 16 + lane16] : 0u;
+    v = p2c::permute(v, lc);
+    if (act) states[i * 16 + lane16] = v;
+}
+// variant: 0 = int32 Montgomery form, 1 = fp64 form, 2 = fp64 one state per quad, 3 = int32 one state per 16-lane row (all four must
+// agree word for word)
 int poseidon2_permute_states_variant(hipStream_t stream, uint32_t* d_states, uint64_t n, int variant) {
     if (!n) return OK;
-    if (variant == 1) hipLaunchKernelGGL(poseidon2_permute_f64_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    if (variant == 3) hipLaunchKernelGGL(poseidon2_permute_coop_kernel, dim3((uint32_t)((n * 16 + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    else if (variant == 2) hipLaunchKernelGGL(poseidon2_permute_q4_kernel, dim3((uint32_t)((n * 4 + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    else if (variant == 1) hipLaunchKernelGGL(poseidon2_permute_f64_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
     else hipLaunchKernelGGL(poseidon2_permute_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
     P3_HIP(hipGetLastError());
     return OK;
@@ -704,10 +755,92 @@ __global__ void keccak_f_kernel(uint64_t* states, uint64_t n) {
 #pragma unroll
     for (int k = 0; k < 25; k++) states[i * 25 + k] = st[k];
 }
-int keccak_f_states(hipStream_t stream, uint64_t* d_states, uint64_t n) {
+// Test forms of the other two formulations on whole states.  permute_digest defines words 0..3 only: the kernel writes those four and
+// leaves words 4..24 of the buffer as they were.  f_coop: one state per wave, lane x + 8y holds word x + 5y.
+__global__ void keccak_f_digest_kernel(uint64_t* states, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t st[25];
+#pragma unroll
+    for (int k = 0; k < 25; k++) st[k] = states[i * 25 + k];
+    kk::permute_digest(st);
+#pragma unroll
+    for (int k = 0; k < 4; k++) states[i * 25 + k] = st[k];
+}
+__global__ void __launch_bounds__(256) keccak_f_coop_kernel(uint64_t* states, uint64_t n) {
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (i >= n) return;  // uniform over the wave
+    const uint32_t idx = kk::coop_index();
+    uint64_t a = idx < 25u ? states[i * 25 + idx] : 0ull;
+    a = kk::f_coop(a);
+    if (idx < 25u) states[i * 25 + idx] = a;
+}
+// variant: 0 = kk::permute, 1 = kk::permute_digest (words 0..3), 2 = kk::f_coop
+int keccak_f_states_variant(hipStream_t stream, uint64_t* d_states, uint64_t n, int variant) {
     if (!n) return OK;
-    hipLaunchKernelGGL(keccak_f_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    if (variant == 2) hipLaunchKernelGGL(keccak_f_coop_kernel, dim3((uint32_t)((n * 64 + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    else if (variant == 1) hipLaunchKernelGGL(keccak_f_digest_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
+    else hipLaunchKernelGGL(keccak_f_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_states, n);
     P3_HIP(hipGetLastError());
+    return OK;
+}
+int keccak_f_states(hipStream_t stream, uint64_t* d_states, uint64_t n) { return keccak_f_states_variant(stream, d_states, n, 0); }
+
+// Test entry: ONE compression layer through the PRODUCTION kernel of a named form, launched with the geometry mmcs_commit gives it.
+// d_in: 2 n_out digests, d_out: n_out digests.  The layers are staged back to back in a 16-byte-aligned buffer of the entry's own (the
+// multi-level kernels write the next layer right behind the current one), so the caller's pointers need no alignment.  Synchronises.
+//   Poseidon2: 0 compress_layer_kernel (no injection), 1 compress_layer_f64_kernel, 2 compress_layer_q4_kernel,
+//              3 tree_levels_coop_kernel (one level)
+//   Keccak:    0 keccak_compress_kernel (no injection), 1 keccak_tree_levels_kernel, 2 keccak_tree_levels_coop_kernel (one level each)
+// The multi-level kernels split a layer into power-of-two chunks: n_out must be a power of two there.  Nothing is padded.
+int compress_layer_variant_check(int kind, int variant, const uint32_t* d_in, const uint32_t* d_out, uint64_t n_out) {
+    if (kind != HASH_POSEIDON2 && kind != HASH_KECCAK) return fail(ERR_BAD_ARG, "compress_layer_variant: unknown hash configuration");
+    if (variant < 0 || variant > (kind == HASH_POSEIDON2 ? 3 : 2))
+        return fail(ERR_BAD_ARG, "compress_layer_variant: Poseidon2 forms 0 = int32, 1 = fp64, 2 = quad, 3 = 16-lane levels; Keccak forms 0 = "
+                                 "per lane, 1 = per-lane levels, 2 = per-wave levels");
+    if (!n_out) return OK;
+    if (!d_in || !d_out) return fail(ERR_BAD_ARG, "compress_layer_variant: null pointer");
+    if (n_out > (1ull << 24)) return fail(ERR_BAD_ARG, "compress_layer_variant: at most 2^24 digests out");
+    const bool levels_kernel = kind == HASH_POSEIDON2 ? variant == 3 : variant != 0;
+    if (levels_kernel && !is_pow2(n_out)) return fail(ERR_BAD_ARG, "compress_layer_variant: this form takes a power-of-two layer only");
+    if (levels_kernel && n_out > (1ull << 15)) return fail(ERR_BAD_ARG, "compress_layer_variant: this form takes at most 2^15 digests out");
+    return OK;
+}
+int compress_layer_variant(hipStream_t stream, int kind, int variant, const uint32_t* d_in, uint32_t* d_out, uint64_t n_out) {
+    const int bad = compress_layer_variant_check(kind, variant, d_in, d_out, n_out);
+    if (bad || !n_out) return bad;
+    const uint64_t n_in = 2 * n_out;
+    uint32_t* buf = nullptr;
+    P3_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(n_in + n_out) * 32));
+    struct Free { uint32_t* p; ~Free() { (void)hipFree(p); } } guard{buf};
+    uint32_t* next = buf + n_in * 8;
+    P3_HIP(hipMemcpyAsync(buf, d_in, (size_t)n_in * 32, hipMemcpyDeviceToDevice, stream));
+    const dim3 lane_grid((uint32_t)((n_out + 255) / 256)), b256(256);
+    const RowSet none{};
+    if (kind == HASH_POSEIDON2) {
+        if (variant == 0) hipLaunchKernelGGL(compress_layer_kernel, lane_grid, b256, 0, stream, buf, next, n_out, none, 0u);
+        else if (variant == 1) hipLaunchKernelGGL(compress_layer_f64_kernel, lane_grid, b256, 0, stream, buf, next, n_out);
+        else if (variant == 2) hipLaunchKernelGGL(compress_layer_q4_kernel, dim3((uint32_t)((n_out * 4 + 255) / 256)), b256, 0, stream, buf, next, n_out, 1u);
+        else {
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 32);
+            hipLaunchKernelGGL(tree_levels_coop_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk * 8)), 0, stream, buf,
+                               (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
+        }
+    } else {
+        if (variant == 0) hipLaunchKernelGGL(keccak_compress_kernel, lane_grid, b256, 0, stream, buf, next, n_out, none, 0u);
+        else if (variant == 1) {
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 128);
+            hipLaunchKernelGGL(keccak_tree_levels_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk / 2)), (size_t)chunk * 32,
+                               stream, buf, (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
+        } else {
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 16);
+            hipLaunchKernelGGL(keccak_tree_levels_coop_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk * 32)), 0, stream, buf,
+                               (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
+        }
+    }
+    P3_HIP(hipGetLastError());
+    P3_HIP(hipMemcpyAsync(d_out, next, (size_t)n_out * 32, hipMemcpyDeviceToDevice, stream));
+    P3_HIP(hipStreamSynchronize(stream));
     return OK;
 }
 

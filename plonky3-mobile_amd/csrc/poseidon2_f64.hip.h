@@ -37,6 +37,9 @@ __device__ __forceinline__ double reduce(double x) {  // |result| <= P/2 + eps
 // tot + x * 2^-K (mod P), K <= 8, for integers |x| < 2^44, |tot| < 2^40: xt = tot + x / 2^K is exact (K fractional
 // bits), fract(xt) = (x mod 2^K) / 2^K because tot is an integer, and xt - fract * P = tot + (x - (x mod 2^K) P) / 2^K
 // is an integer (P = 1 mod 2^K) below 2^45: three exact ops.  inv = +-2^-K.
+// With an INTEGER multiplier inv = m (the quad form passes -2, 1, 2, 3, 4, -3, -4, -15, 15 through here too) xt = tot + m x is an
+// integer, fract(xt) = 0 and the result is xt itself: exact while |tot + m x| < 2^53, whatever |x| (the quad form reaches
+// |x| = 2^46.8 on the x15 lanes before a fold; tests/poseidon2_sched_ref.py).
 __device__ __forceinline__ double add_scaled_pow2(double tot, double x, double inv) {
     double xt = __fma_rn(x, inv, tot);
     double fr = __builtin_amdgcn_fract(xt);
@@ -47,8 +50,12 @@ __device__ __forceinline__ double add_scaled_pow2(double tot, double x, double i
 //   c  = fma(-qb, P - 1, M * P)  = M - q (P - 1)                             (exact: a multiple of 2^27 below 2^71 plus M; M * P is a double)
 //   t  = fma(a, b, c)            = M + (ab - qP) + q                         (exact: M plus an integer below 2^40)
 //   t - qb                       = ab - qP                                   (exact difference of two integers below 2^53)
-// Valid for |b * aP| < 2^51 and |ab| < 2^76, i.e. for every product of the permutation (the largest S-box input is
-// 35 (P/2 + 1) < 2^36).  One op less than mulmod_p, two less than mulmod: the S-box drops from 23 to 19 fp64 ops.
+// Valid for |b * aP| < 2^51 and |ab| < 2^76, i.e. for every product of the permutation on canonical inputs: the largest S-box
+// input is the FIRST round's, 35 (P - 1) + rc < 2^36.1 (states of words in [0, P)); the later rounds see 35 (P/2 + 2^9) + rc < 2^35.2.
+// Under an entry bound |s_i| <= 2^32 it is 35 * 2^32 + P < 2^37.2 and x * x < 2^76 still holds; at 2^33 it is 2^38.14 and x * x =
+// 2^76.3 is past the bound stated here.  The algebra has room left (c stays a double while |q| (P - 1) < 2^80) and the exact model
+// is right at those operands (tests/test_poseidon2_sched_host.py), but only |ab| < 2^76 is pinned class by class on the device.
+// One op less than mulmod_p, two less than mulmod: the S-box drops from 23 to 19 fp64 ops.
 constexpr double MAGIC = 6755399441055744.0;                 // 1.5 * 2^52
 constexpr double MAGIC_P = 6755399441055744.0 * 2013265921.0;  // 45 * 2^78 + 3 * 2^51: exactly representable
 // Operand placement matters: a VOP3 fp64 op reads at most ONE scalar / literal operand on gfx950, and hipcc turns
@@ -120,7 +127,7 @@ __device__ __forceinline__ void external_linear(double (&s)[16]) {
     for (int i = 0; i < 16; i++) s[i] += t[i & 3];
 }
 
-// The 13 internal rounds.  Entry: integers |s_i| <= 2^37 (what the fourth external round leaves: 35 (P/2 + 1) < 2^36).
+// The 13 internal rounds.  Entry: integers |s_i| <= 2^37 (what the fourth external round leaves: 35 (P/2 + 2^9) < 2^35.1).
 // V = [-2, 1, 2, 1/2, 3, 4, -1/2, -3, -4, 2^-8, 1/4, 1/8, 2^-27, -2^-8, -1/16, -2^-27]; 2^-27 = -15 (mod P)
 // because P - 1 = 15 * 2^27.  The integer-multiplier lanes grow up to 15x per round: fold them back after
 // every fourth round (15^4 * 2^37 < 2^53: still exact integers); the fractional lanes stay below their entry bound.
@@ -163,16 +170,19 @@ __device__ __forceinline__ void internal_rounds(double (&s)[16], const MagicRegs
     fold_integer_lanes();
 }
 
-// |s_i| <= 2^33 on entry (canonical inputs or compress inputs < P); every intermediate stays below 2^53.
+// Entry: integers |s_i| <= 2^32.  That is what the S-box's stated contract (mulmod_m: |ab| < 2^76) supports: the first round's
+// x = 35 s + rc gives x * x < 2^74.3.  Every caller is far inside it: words in [0, P) from load_elem, or |s_i| <= P/2 + eps after the
+// reduce between two absorptions.  (This comment used to say 2^33: every intermediate still stays below 2^53 there and the exact
+// model agrees with the integers, the probe's modes 0 and 3 run it, but x * x = 2^76.3 is outside what mulmod_m states.)
 __device__ __forceinline__ void permute(double (&s)[16]) {
     const MagicRegs mk = magic_regs();
     const double npm1 = d_c.neg_pm1, pinv = d_c.pinv;
-    external_linear(s);  // <= 35 * 2^33 < 2^39
+    external_linear(s);  // <= 35 * 2^32 < 2^38
     _Pragma("clang loop unroll(disable)")
     for (int r = 0; r < 4; r++) {
 #pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = sbox7(s[i] + d_c.ext[r][i], mk, npm1, pinv);  // |.| <= P/2 + 1
-        external_linear(s);                                                // <= 35 (P/2 + 1) < 2^36
+        for (int i = 0; i < 16; i++) s[i] = sbox7(s[i] + d_c.ext[r][i], mk, npm1, pinv);  // |.| <= P/2 + 2^9
+        external_linear(s);                                                // <= 35 (P/2 + 2^9) < 2^35.1
     }
     internal_rounds(s, mk);
     _Pragma("clang loop unroll(disable)")

@@ -8,8 +8,14 @@
 //                   lane), the four-block column sums by two quad_perm exchanges per element;
 //   internal layer: x^7 on element 0 computed by every lane and kept by lane 0, the sum of the sixteen elements by an in-lane
 //                   sum and two exchanges, the diagonal as `tot + x * V` in the three-operation form that is exact for the
-//                   integer multipliers and for the 2^-k ones alike (p2f::add_scaled_pow2; V per lane in registers).
-// Same values as p2f::permute for every input (exact integer arithmetic, only the grouping of the additions differs).
+//                   integer multipliers and for the 2^-k ones alike (p2f::add_scaled_pow2; V per lane in registers).  The
+//                   integer lanes take it OUTSIDE the |x| < 2^44 it states for the fractional forms: up to 15^3 35 (P/2 + 1) =
+//                   2^46.8 on the x15 lanes before a fold.  That is exact all the same: tot + m x is an integer below 2^50.7, its
+//                   fract is 0 and the third operation returns it unchanged.  The three lanes that compute x^7 only to discard it
+//                   feed sbox7 the same 2^46.8: finite garbage, never selected.
+// Same values as p2f::permute for every input (exact integer arithmetic, only the grouping of the additions and the fold schedule
+// differ: all sixteen elements are folded after every fourth internal round, not the integer lanes alone).  Pinned state by state,
+// at the largest magnitudes canonical words can reach, by tests/test_gpu_permutation_forms.py.
 #pragma once
 #include "poseidon2_f64.hip.h"
 
@@ -57,7 +63,7 @@ __device__ __forceinline__ void external_linear(double (&s)[4]) {
     for (int i = 0; i < 4; i++) s[i] += quad_sum(s[i]);
 }
 
-// s: this lane's four elements (integers |s_i| <= 2^33 on entry, as p2f::permute); every lane of the quad must be active.
+// s: this lane's four elements (integers |s_i| <= 2^32 on entry, as p2f::permute); every lane of the quad must be active.
 __device__ __forceinline__ void permute(double (&s)[4], const LaneConsts& c, bool lane0) {
     const p2f::MagicRegs mk = p2f::magic_regs();
     const double npm1 = p2f::d_c.neg_pm1, pinv = p2f::d_c.pinv;

@@ -44,6 +44,36 @@ def keccak_f(states):
     return d.cpu().numpy().view(np.uint64).reshape(a.shape)
 
 
+def poseidon2_permute_variant(states, variant):
+    """Test / diagnostics: one FORM of the permutation on a torch device tensor of n x 16 words, in place.  0 = int32 per lane, 1 = fp64
+    per lane, 2 = fp64 per quad, 3 = int32 per 16-lane row (include/p3hip.h)."""
+    assert _is_torch(states) and states.is_cuda and states.is_contiguous() and states.shape[-1] == 16 and states.element_size() == 4
+    _lib.check(_lib.lib().p3hip_poseidon2_permute_variant_dev(C.c_void_p(states.data_ptr()), states.numel() // 16, variant, _stream_ptr()))
+    return states
+
+
+def keccak_f_variant(states, variant):
+    """Test / diagnostics: one FORM of Keccak-f on a torch device int64 tensor of n x 25 words, in place.  0 = permute, 1 = permute_digest
+    (words 0..3 written, the rest left as they were), 2 = f_coop (one state per wave)."""
+    assert _is_torch(states) and states.is_cuda and states.is_contiguous() and states.shape[-1] == 25 and states.element_size() == 8
+    _lib.check(_lib.lib().p3hip_keccak_f_variant_dev(C.c_void_p(states.data_ptr()), states.numel() // 25, variant, _stream_ptr()))
+    return states
+
+
+def compress_layer_variant(hash, variant, layer):
+    """Test / diagnostics: one 2-to-1 compression layer through the production kernel of a named form.  layer: torch device tensor of
+    2 n x 8 words; returns a new n x 8 tensor.  hash: "poseidon2" | "keccak"; variant as in include/p3hip.h."""
+    import torch
+    assert _is_torch(layer) and layer.is_cuda and layer.is_contiguous() and layer.shape[-1] == 8 and layer.element_size() == 4
+    n_in = layer.numel() // 8
+    assert n_in % 2 == 0
+    out = torch.zeros((n_in // 2, 8), dtype=layer.dtype, device=layer.device)
+    kind = {"poseidon2": HASH_POSEIDON2, "keccak": HASH_KECCAK}[hash]
+    _lib.check(_lib.lib().p3hip_compress_layer_variant_dev(kind, variant, C.c_void_p(layer.data_ptr()), C.c_void_p(out.data_ptr()), n_in // 2,
+                                                           _stream_ptr()))
+    return out
+
+
 class MerkleTree:
     """Prover data of one commitment: device digest layers + the committed matrices (kept alive)."""
 

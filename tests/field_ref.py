@@ -47,6 +47,7 @@ OPS = {
     "mulmod": (32, 2, 1, True), "mulmod_p": (33, 3, 1, True), "mulmod_p_dev": (34, 2, 1, True), "mulmod_m": (35, 3, 1, True),
     "mulmod_m_dev": (36, 2, 1, True), "add_scaled_pow2": (37, 3, 1, True), "sbox7": (38, 1, 1, True), "store_elem": (39, 1, 1, True),
     "mulm": (40, 3, 1, True), "mulm_dev": (41, 2, 1, True), "word_centered": (42, 1, 1, True), "word_any": (43, 1, 1, True),
+    "add_scaled_int": (48, 3, 1, True), "sbox7_wide": (49, 1, 1, True),
 }
 INT_OPS = [n for n, o in OPS.items() if not o[3]]
 F64_OPS = [n for n, o in OPS.items() if o[3]]
@@ -341,7 +342,7 @@ MODELS = {
     "mulmod": m_mulmod, "mulmod_p": m_mulmod_p, "mulmod_p_dev": lambda a, b: m_mulmod_p(a, b, fmul(a, PINV)),
     "mulmod_m": m_mulmod_m, "mulmod_m_dev": lambda a, b: m_mulmod_m(a, b, fmul(a, PINV)), "add_scaled_pow2": m_add_scaled_pow2,
     "sbox7": m_sbox7, "store_elem": m_store_elem, "mulm": m_mulm, "mulm_dev": lambda a, b: m_mulm(a, fmul(a, PINV), b),
-    "word_centered": m_word_centered, "word_any": m_word_any,
+    "word_centered": m_word_centered, "word_any": m_word_any, "add_scaled_int": m_add_scaled_pow2, "sbox7_wide": m_sbox7,
 }
 
 
@@ -368,6 +369,11 @@ SBOX_IN = 35 * (P // 2 + 1)    # the largest S-box input of the permutation befo
 NEAR_TIE = {"(P-1)/2": (P - 1) // 2, "(P+1)/2": (P + 1) // 2, "-(P-1)/2": -((P - 1) // 2), "(P-3)/2": (P - 3) // 2,
             "(P+3)/2": (P + 3) // 2}
 ASP_FORMS = ((1, 1), (1, -1), (8, 1), (2, 1), (3, 1), (8, -1), (4, -1))  # (K, sign of inv) of internal_rounds, lanes 3 6 9 10 11 13 14
+ASI_MULTIPLIERS = (-2, 1, 2, 3, 4, -3, -4, -15, 15)  # the integer entries of V: p2q::permute passes them through add_scaled_pow2
+# a x15 lane three rounds after the internal rounds are entered at b = 35 (P/2 + 2^9), every lane sum at t = P/2 + 1: 15^3 b + (15^2 + 15 + 1) t
+ASI_X = 15 ** 3 * 35 * (P // 2 + 2 ** 9) + 241 * (P // 2 + 1)
+ASI_TOT = P // 2 + 1                   # reduce's |result|
+SBOX_WIDE_IN = 35 * (P - 1) + P        # the first external round on a state of words in [0, P), + its round constant
 EXPONENTS = (0, 1, 2, P - 2, P - 1, 2 ** 32 - 1, 2 ** 63, 2 ** 64 - 1)
 
 
@@ -408,6 +414,8 @@ CLASSES = {
     "store_elem": ["edges", "uniform"] + ["v 2^32 = %s (mod P), v %s 0" % (t, s) for t in NEAR_TIE for s in "<>"],
     "word_centered": ["edges", "uniform"],
     "word_any": ["%s, k %s 0" % (o, s) for o in ("kP", "kP+1", "kP-1", "kP+(P-1)") for s in ("<", ">=")],
+    "add_scaled_int": ["m = %d" % m for m in ASI_MULTIPLIERS],
+    "sbox7_wide": ["edges", "above 35 (P/2 + 1) + P", "uniform up to 35 (P - 1) + P"],
 }
 assert sorted(CLASSES) == sorted(OPS)
 
@@ -684,6 +692,27 @@ def _lanes_sbox7(rng):
     return acc.done(np.float64)
 
 
+def _lanes_add_scaled_int(rng):
+    acc = _Acc()
+    for m in ASI_MULTIPLIERS:
+        rows = [(float(st * t), float(sx * x), float(m)) for t in (ASI_TOT, 0) for x in (ASI_X, 15 ** 3 * SBOX_IN, 0) for sx in (-1, 1) for st in (-1, 1)]
+        for i in range(512):  # the top binade of |x| at the largest |tot|, every sign pattern; then both uniform
+            x = int(rng.integers(ASI_X >> 1, ASI_X + 1)) if i < 256 else int(rng.integers(0, ASI_X + 1))
+            t = ASI_TOT - int(rng.integers(0, 4)) if i < 256 else int(rng.integers(0, ASI_TOT + 1))
+            rows.append((float((1, -1)[i & 1] * t), float((1, -1)[i >> 1 & 1] * x), float(m)))
+        acc.add("m = %d" % m, rows)
+    return acc.done(np.float64)
+
+
+def _lanes_sbox7_wide(rng):
+    acc = _Acc()
+    top, old = SBOX_WIDE_IN, SBOX_IN + P
+    acc.add("edges", [top, -top, top - 1, 1 - top, 35 * (P - 1), -35 * (P - 1), old + 1, -old - 1, 35 * ((P - 1) // 2) + P - 1, 1 << 36, -(1 << 36)])
+    acc.add("above 35 (P/2 + 1) + P", [int(v) * (1, -1)[i & 1] for i, v in enumerate(rng.integers(old + 1, top + 1, size=1024))])
+    acc.add("uniform up to 35 (P - 1) + P", rng.integers(-top, top + 1, size=1024).tolist())
+    return acc.done(np.float64)
+
+
 def _lanes_store_elem(rng):
     acc = _Acc()
     top = (1 << 37) - 1
@@ -785,6 +814,10 @@ def lanes(name):
         out = _lanes_word_centered(rng)
     elif name == "word_any":
         out = _lanes_word_any(rng)
+    elif name == "add_scaled_int":
+        out = _lanes_add_scaled_int(rng)
+    elif name == "sbox7_wide":
+        out = _lanes_sbox7_wide(rng)
     else:
         raise KeyError(name)
     x, lab = out

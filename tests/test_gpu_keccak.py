@@ -15,7 +15,7 @@ def test_keccak_f_states(p3, oracle):
     st[0] = 0
     st[1] = np.uint64(0xFFFFFFFFFFFFFFFF)
     got = p3.keccak_f(st)
-    for i in list(range(8)) + [500, 999]:
+    for i in range(len(st)):
         assert np.array_equal(got[i], oracle.keccak_f(st[i])), i
     # the zero state's image begins with the well-known lane 0xF1258F7940E1DDE7
     assert int(got[0][0]) == 0xF1258F7940E1DDE7
