@@ -24,6 +24,28 @@
  *     a scratch slab that has to GROW is reallocated after a device synchronise, and so is the bounded table cache
  *     once a thread has used more than 256 distinct (shift, height) pairs.  A given stream must not be used from two
  *     threads at once with buffers that alias.
+ *   - BUFFER CONTRACT of the `*_dev` entries (the Rust side hands in pointers into the middle of allocations,
+ *     integration/native/src/hip_matrix.rs; tests/test_gpu_buffer_contract.py pins every line of it, DESIGN.md "Test strategy" has
+ *     the table pointer by pointer).  Unless an entry says otherwise:
+ *       ALIGNMENT  every device pointer needs the 4 bytes of its words and no more.  Where a kernel moves wider pieces it either
+ *                  checks the address and takes a word-wise kernel otherwise (any 4-byte alignment is in the contract, both sides
+ *                  are tested), or the entry STATES the alignment and refuses a pointer that lacks it with P3HIP_ERR_BAD_ARG and a
+ *                  message naming the argument, on the host, before anything is launched or drawn.
+ *       READ-ONLY  a `const` pointer is read in place: no copy is made and no word of it is written; the caller keeps it unchanged
+ *                  until the work that reads it has completed on the stream.
+ *       EXTENT     an output is written exactly over the words its comment gives (rows x width, n statuses, ...): not a word before
+ *                  the pointer and not a word past the last one, whatever the launch geometry rounds up to.
+ *       ALIASING   an input and an output must not share a word, with one exception: p3hip_dft_batch_bb31_dev and
+ *                  p3hip_idft_batch_bb31_dev accept d_out == d_in (the input is staged in the stream's scratch).  The six transform
+ *                  entries and p3hip_bit_reverse_rows_dev refuse two ranges that overlap without being identical, and all but dft /
+ *                  idft refuse identical ones (heights above one row), with P3HIP_ERR_BAD_ARG and nothing written.  For every other
+ *                  entry overlapping arguments are undefined.
+ *     Stated alignments (everything else: 4 bytes): p3hip_fib_trace_dev d_out 8; p3hip_fib_check_trace_dev,
+ *     p3hip_fib_prover_prove_trace_dev, p3hip_fib_prover_enqueue_trace_dev, p3hip_fib_batch_prove_traces_dev d_trace 8;
+ *     p3hip_keccak_f_dev, p3hip_keccak_f_variant_dev d_states 8; p3hip_poseidon2_permute_variant_dev d_states 16 (variant 3: 4);
+ *     p3hip_mmcs_commit_into_dev d_layers 16; p3hip_mmcs_verify_batch_many*_dev d_paths 16; p3hip_air_quotient_dev d_chunks_out[c]
+ *     16; p3hip_pcs_verifier_verify_dev d_chal_in, d_chal_out 8; the buffers of doubles of the diagnostic probes 8
+ *     (p3hip_poseidon2_f64_probe_dev d_in; p3hip_field_probe_dev d_in and d_out of the fp64 ops).
  */
 #ifndef P3HIP_H
 #define P3HIP_H
@@ -90,7 +112,11 @@ int p3hip_coset_lde_batch_bb31(const uint32_t *in, uint32_t *out, size_t height,
  * upload=..ms stages=..ms readback=..ms total=..ms gpu(stage=..ms copy_back=..ms total=..ms)" — for the calling thread's
  * last call (NULL before the first); with P3HIP_LOG_TIMING=1 it is also written to stderr like the reference's. */
 const char *p3hip_last_timing_line(void);
-/* device-resident forms — the reference's "kernel-only" view (backend_vulkan.rs:1428-1693) */
+/* device-resident forms — the reference's "kernel-only" view (backend_vulkan.rs:1428-1693).
+ * BUFFER CONTRACT (all six, and p3hip_bit_reverse_rows_dev): d_in / d_coeffs height x width words, read-only, any 4-byte alignment;
+ * d_out exactly (height, or height << added_bits) x width words, any 4-byte alignment (the three-launch plan of narrow LDEs moves
+ * 8-byte pieces and is taken only when both pointers are 8-byte aligned: the general plans serve the same shape otherwise).  dft and
+ * idft accept d_out == d_in; every other overlap of the two ranges is refused (conventions above). */
 int p3hip_dft_batch_bb31_dev(const uint32_t *d_in, uint32_t *d_out, size_t height, size_t width, void *stream);
 int p3hip_idft_batch_bb31_dev(const uint32_t *d_in, uint32_t *d_out, size_t height, size_t width, void *stream);
 int p3hip_coset_dft_batch_bb31_dev(const uint32_t *d_in, uint32_t *d_out, size_t height, size_t width,
@@ -110,16 +136,17 @@ int p3hip_coset_lde_from_coeffs_bb31_dev(const uint32_t *d_coeffs, uint32_t *d_o
  * *n_passes = kernel launches, stages_per_pass[i] = radix-2 stages pass i performs (their sum is log2 height; at most `cap` entries
  * are written).  Host-only: no GPU is touched. */
 int p3hip_dft_plan_bb31(size_t height, size_t width, uint32_t *stages_per_pass, size_t cap, size_t *n_passes);
-/* write_bit_reversed_rows_u32 (backend_vulkan.rs:1005-1026) on device */
+/* write_bit_reversed_rows_u32 (backend_vulkan.rs:1005-1026) on device; out of place only (any overlap of the ranges is refused) */
 int p3hip_bit_reverse_rows_dev(const uint32_t *d_in, uint32_t *d_out, size_t height, size_t width, void *stream);
 
 /* ---- FibonacciAir workload (native/src/fib_air.rs:224-306) --------------------------------------- */
 /* generate_trace_rows (fib_air.rs:266-284): n x 2 trace, row 0 = (a, b), row i = (right, left + right);
- * n must be a power of two (fib_air.rs:267). */
+ * n must be a power of two (fib_air.rs:267).  d_out: exactly 2 n words, 8-byte aligned (rows are stored as pairs; refused otherwise). */
 int p3hip_fib_trace_dev(uint64_t a, uint64_t b, size_t n, uint32_t *d_out, void *stream);
 
 /* ---- Poseidon2-BabyBear-16 (default_babybear_poseidon2_16, native/src/poseidon_cpu.rs:17-18) ----- */
-/* n independent width-16 states, in place. */
+/* n independent width-16 states, in place: exactly 16 n words are read and written.  d_states: any 4-byte alignment (16-byte-aligned
+ * states run the per-lane fp64 form, which moves 16-byte pieces; any other alignment the 16-lane form, which moves words). */
 int p3hip_poseidon2_permute_dev(uint32_t *d_states, size_t n, void *stream);
 int p3hip_poseidon2_permute(uint32_t *states, size_t n);
 /* The permutation exists in four forms that must agree word for word: int32 Montgomery, one state per lane (variant 0); exact
@@ -229,7 +256,9 @@ int p3hip_field_probe_host(int op, const void *in, void *out, size_t n);
 typedef struct p3hip_tree p3hip_tree_t;
 /* Mmcs::commit: matrices are device pointers (row-major, power-of-two heights); the tree keeps every
  * digest layer in HBM and BORROWS the matrices (they must outlive the tree).  root_out is a host buffer;
- * the call synchronises the stream before returning the root. */
+ * the call synchronises the stream before returning the root.  d_mats[m]: heights[m] x widths[m] words, read-only, any 4-byte
+ * alignment (of every p3hip_mmcs_commit*_dev entry; the salted Keccak leaf kernel of the hiding commit moves 16-byte rows and is
+ * taken only when the rows allow it). */
 int p3hip_mmcs_commit_dev(const uint32_t *const *d_mats, const size_t *heights, const size_t *widths,
                           size_t n_mats, uint32_t root_out[8], p3hip_tree_t **tree_out, void *stream);
 /* as above without the root download/synchronise (root readable later via p3hip_mmcs_root) */
@@ -264,7 +293,8 @@ int p3hip_mmcs_verify_batch(int hash, const uint32_t root[8], const size_t *heig
  * row_words (the rows of every matrix in matrix order, salts included on a hiding tree) and log_max_height x 8 words at d_paths +
  * i * log_max_height * 8.  d_indices: n 32-bit words in device memory; an index is MASKED into the tree (index mod the tallest
  * height), so whatever the buffer holds the gather stays inside the tree.  Enqueues only: no allocation, no copy to the host, no
- * synchronise (it can be captured).  d_paths must be 16-byte aligned for p3hip_mmcs_verify_batch_many_dev. */
+ * synchronise (it can be captured).  d_indices (read-only), d_rows, d_paths: any 4-byte alignment; exactly n x row_words and n x
+ * log_max_height x 8 words are written.  d_paths must be 16-byte aligned for p3hip_mmcs_verify_batch_many_dev. */
 size_t p3hip_mmcs_row_words(const p3hip_tree_t *tree);   /* sum of the widths, salts included on a hiding tree */
 int p3hip_mmcs_open_batch_many_dev(const p3hip_tree_t *tree, const uint32_t *d_indices, size_t n,
                                    uint32_t *d_rows /* n x row_words */, uint32_t *d_paths /* n x log_max_height x 8 */, void *stream);
@@ -274,7 +304,8 @@ int p3hip_mmcs_open_batch_many_dev(const p3hip_tree_t *tree, const uint32_t *d_i
  * path length is given by the dimensions); *d_rejected (device word, may be null) = how many are nonzero.  Enqueues only, allocates
  * nothing.  One opening per lane.  (A lane-cooperative form for small n exists — one opening per 16 lanes under Poseidon2, per wave
  * under Keccak — but this entry does not take it until it has been timed against the per-lane form: DESIGN.md section 4.2, and the
- * diagnostics below.)  Heights up to 2^31. */
+ * diagnostics below.)  Heights up to 2^31.  d_indices, d_rows: read-only, any 4-byte alignment; d_paths: read-only, 16-byte aligned
+ * (refused otherwise); exactly n words of d_status and one of d_rejected are written. */
 int p3hip_mmcs_verify_batch_many_dev(int hash, const uint32_t root[8] /* host, passed by value */,
                                      const size_t *heights, const size_t *widths, size_t n_mats,
                                      const uint32_t *d_indices, size_t n, const uint32_t *d_rows, const uint32_t *d_paths,
@@ -307,11 +338,13 @@ int p3hip_mmcs_commit_hash(int hash, const uint32_t *const *mats, const size_t *
                            size_t n_mats, uint32_t root_out[8], p3hip_tree_t **tree_out);
 /* Mmcs::commit into CALLER-PROVIDED digest-layer storage of p3hip_mmcs_layer_words(max height) 32-bit words (leaf layer
  * first, 8 words per digest): nothing is allocated and nothing synchronises — the call only enqueues.  The tree borrows the
- * storage and the matrices; read the root with p3hip_mmcs_root. */
+ * storage and the matrices; read the root with p3hip_mmcs_root.  d_layers: 16-byte aligned (every compression kernel moves digests as
+ * 16-byte pieces; refused otherwise), written exactly over those words. */
 size_t p3hip_mmcs_layer_words(size_t max_height);
 int p3hip_mmcs_commit_into_dev(int hash, const uint32_t *const *d_mats, const size_t *heights, const size_t *widths,
                                size_t n_mats, uint32_t *d_layers, p3hip_tree_t **tree_out, void *stream);
-/* KeccakF::permute_mut on n independent [u64; 25] states in device memory (p3-keccak's KeccakF, fib_air.rs:32) */
+/* KeccakF::permute_mut on n independent [u64; 25] states in device memory (p3-keccak's KeccakF, fib_air.rs:32), in place: exactly
+ * 25 n u64 words; d_states 8-byte aligned (refused otherwise; also by the variant entry below) */
 int p3hip_keccak_f_dev(uint64_t *d_states, size_t n, void *stream);
 /* Diagnostics / tests: the three formulations of Keccak-f on n <= 2^24 states of 25 words, in place.  variant 0: one state per lane,
  * all 25 words (what p3hip_keccak_f_dev runs); 1: the digest form every leaf and compression runs (first round peeled, the last
@@ -368,7 +401,8 @@ int p3hip_fib_prover_prove(p3hip_fib_prover_t *prover, uint64_t a, uint64_t b, c
  * into its own buffer and copies ONCE into `out` (what is saved are the caller-side copies — a Python bytes object and its copy
  * into the staging row).  Returns ERR_BAD_ARG when cap is too small, the needed size in *proof_len: checked BEFORE proving once
  * the prover has produced a proof (proofs of one prover have one length); on a first call that fails this way the proof has been
- * computed and discarded.  A retry returns the same bytes (the hiding prover restarts its streams from the seed for every proof). */
+ * computed and discarded.  A retry returns the same bytes (the hiding prover restarts its streams from the seed for every proof).
+ * `out` is HOST memory of any alignment: on success exactly *proof_len bytes are written, on any failure none. */
 int p3hip_fib_prover_prove_into(p3hip_fib_prover_t *prover, uint64_t a, uint64_t b, uint8_t *out, size_t cap, size_t *proof_len);
 /* The same in two halves, to keep the prover's stream busy across proofs: enqueue returns as soon as the proof's launches
  * are queued (nothing is waited for), finish waits for the OLDEST enqueued proof and returns its bytes (valid until the next
@@ -414,7 +448,7 @@ int p3hip_verify_fib_air_hiding(int hash, const uint8_t *proof, size_t len, uint
                                 unsigned log_n, const p3hip_fri_params_t *params);
 /* rand 0.9.2 `SmallRng::seed_from_u64(seed)` (xoshiro256++ behind SplitMix64) as a device-resident stream of BabyBear
  * elements (Montgomery words), exactly the sequence a host loop over `rng.random::<BabyBear>()` yields.  One stream is
- * used from one HIP stream at a time. */
+ * used from one HIP stream at a time.  p3hip_rng_fill_field_dev: d_out any 4-byte alignment, exactly n words written. */
 typedef struct p3hip_rng p3hip_rng_t;
 int p3hip_rng_create(uint64_t seed, p3hip_rng_t **out);
 int p3hip_rng_fill_field_dev(p3hip_rng_t *rng, uint32_t *d_out, size_t n, void *stream);
@@ -463,7 +497,8 @@ void p3hip_fib_batch_destroy(p3hip_fib_batch_t *batch);
  * not satisfy, still yields a proof, and the verifiers reject it for those pis.  For a Fibonacci trace with its own pis the bytes are
  * those of p3hip_fib_prover_prove(a, b).  Every prover and pool of the create functions above takes these entries (the hiding ones
  * too; the enqueue form, as p3hip_fib_prover_enqueue, the non-hiding prover only).
- * BUFFER CONTRACT of the _dev entries: d_trace is read in place (no copy).  The caller's writes to it must be complete, or ordered
+ * BUFFER CONTRACT of the _dev entries: d_trace is 8-byte aligned (rows are read as pairs; refused otherwise) and read in place (no copy, no
+ * word written).  The caller's writes to it must be complete, or ordered
  * on the prover's stream, before the call; the buffer must stay unchanged until the prove call returns, or, after an enqueue, until
  * finish has returned that proof.  A d_trace that hipPointerGetAttributes does not report as device memory of the prover's device,
  * or whose allocation ends before 2^log_n rows, is refused before anything is launched.
@@ -524,7 +559,8 @@ int p3hip_fib_verifier_create(int hash, int hiding, unsigned log_n, const p3hip_
  * p3hip_fib_proof_len bytes (a proof of another length is rejected without being read); d_pis: n x 3 Montgomery words [a, b, x] (the
  * convention of p3hip_fib_prover_prove_trace_dev); d_status: n codes; *d_rejected (may be NULL) = count of nonzero codes.  Enqueues
  * only (four launches and one 4-byte memset on `stream`): no allocation, no host copy, no synchronise; can be captured.  One call at
- * a time per verifier: the scratch is reused in stream order. */
+ * a time per verifier: the scratch is reused in stream order.  Every input is read-only; exactly n words of d_status and one of
+ * d_rejected are written, whatever max_proofs is. */
 int p3hip_fib_verifier_verify_dev(p3hip_fib_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,
                                   const uint32_t *d_pis, size_t n, uint32_t *d_status, uint32_t *d_rejected, void *stream);
 /* fib_air.rs:70-72, p3_uni_stark::verify: host convenience.  proofs[i] / lens[i]: host pointers (what p3hip_fib_batch_prove hands
@@ -585,7 +621,8 @@ typedef struct p3hip_pcs_data p3hip_pcs_data_t;
 int p3hip_pcs_create(int profile, int hash, const p3hip_fri_params_t *params, void *stream, int own_stream, p3hip_pcs_t **out);
 /* Pcs::commit: d_evals[m] = heights[m] x widths[m] evaluations (device memory, read in place) over domain_shifts[m] * <g_h> in
  * natural row order.  The LDE is coset_lde_batch(evals, log_blowup, GENERATOR / shift), bit-reversed by row; one Merkle tree covers
- * the LDEs of the call, in input order.  The prover data owns the LDEs.  One synchronisation: the root read-back. */
+ * the LDEs of the call, in input order.  The prover data owns the LDEs.  One synchronisation: the root read-back.  d_evals[m]: any
+ * 4-byte alignment, read-only (plain, mixed and hiding objects alike), unchanged by commit and by every later open. */
 int p3hip_pcs_commit_dev(p3hip_pcs_t *pcs, const uint32_t *const *d_evals, const size_t *heights, const size_t *widths,
                          const uint32_t *domain_shifts /* Montgomery, NULL = all 1 */, size_t n_mats,
                          uint32_t root_out[8], p3hip_pcs_data_t **data_out);
@@ -723,7 +760,8 @@ int p3hip_pcs_verifier_create(int hash, int hiding, const p3hip_fri_params_t *pa
  * transcript before verification (8-byte aligned, as d_chal_out; everything else 4-byte aligned); d_status: n codes; *d_rejected (may
  * be NULL) = count of nonzero codes; d_chal_out (may be NULL): of an ACCEPTED member the transcript as the host verifier leaves it
  * (of any other member undefined).  Enqueues only (four launches and one 4-byte memset on `stream`): no allocation, no host copy,
- * no synchronise; can be captured.  One call at a time per verifier: the scratch is reused in stream order. */
+ * no synchronise; can be captured.  One call at a time per verifier: the scratch is reused in stream order.  Every input is read-only;
+ * exactly n words of d_status, one of d_rejected and n x P3HIP_CHALLENGER_STATE_WORDS of d_chal_out are written. */
 int p3hip_pcs_verifier_verify_dev(p3hip_pcs_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,
                                   const uint32_t *d_roots, const uint32_t *d_points, const uint32_t *d_opened, const uint32_t *d_chal_in,
                                   size_t n, uint32_t *d_status, uint32_t *d_rejected, uint32_t *d_chal_out, void *stream);
@@ -809,8 +847,8 @@ int p3hip_air_info(const p3hip_air_t *air, p3hip_air_info_t *out);
  * domain GENERATOR * <g_qn> is the LDE's first qn rows: natural row i is LDE row bitrev(i, log qn), its next row is natural row (i + C)
  * mod qn, x_i = GENERATOR g_qn^i; selectors are selectors_on_coset (Z_H = x^n - 1, is_first_row = Z_H / (x - 1), is_last_row = Z_H / (x -
  * g_n^-1), is_transition = x - g_n^-1).  The quotient (sum_k alpha^(K-1-k) c_k(i)) / Z_H(x_i), four words, goes to C dense n x 4
- * matrices: d_chunks_out[c] row r = natural row r C + c (16-byte aligned device pointers in a HOST array; chunk c is committed with
- * domain shift GENERATOR g_qn^c).  pis: n_public Montgomery words, host memory.  log_blowup < log_quotient_degree is refused by name.
+ * matrices: d_chunks_out[c] row r = natural row r C + c (16-byte aligned device pointers in a HOST array, refused otherwise, exactly
+ * n x 4 words written each; d_lde any 4-byte alignment, read-only; chunk c is committed with domain shift GENERATOR g_qn^c).  pis: n_public Montgomery words, host memory.  log_blowup < log_quotient_degree is refused by name.
  * Enqueues on `stream` (one small upload and one launch; the first call at a log qn also builds that domain's root table) and does
  * not synchronise.  The per-call table (publics, alpha powers, chunk pointers) is the object's and is reused in stream order: calls on
  * ONE Air may follow each other without a synchronisation (the upload reads pinned staging that a later call rewrites only after an
@@ -819,7 +857,7 @@ int p3hip_air_info(const p3hip_air_t *air, p3hip_air_info_t *out);
 int p3hip_air_quotient_dev(p3hip_air_t *air, void *stream, const uint32_t *d_lde, unsigned log_n, unsigned log_blowup, const uint32_t *pis,
                            const uint32_t alpha[4], uint32_t *const *d_chunks_out);
 /* p3_uni_stark::check_constraints (debug builds of prove): the same program over the trace itself, d_trace 2^log_n rows of `width`
- * words in natural order; selectors i == 0, i == n - 1, i != n - 1; next is row i + 1 mod n.  *row_out, *constraint_out: the smallest
+ * words in natural order (any 4-byte alignment, read-only); selectors i == 0, i == n - 1, i != n - 1; next is row i + 1 mod n.  *row_out, *constraint_out: the smallest
  * (row, constraint) whose value is nonzero, or -1, -1.  One pass, one synchronisation. */
 int p3hip_air_check_trace_dev(p3hip_air_t *air, void *stream, const uint32_t *d_trace, unsigned log_n, const uint32_t *pis,
                               long long *row_out, int *constraint_out);

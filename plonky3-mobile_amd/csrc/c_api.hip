@@ -121,6 +121,15 @@ void p3hip_release_thread_context(void) { release_thread_contexts(); }
 // ---- TwoAdicSubgroupDft ------------------------------------------------------------------------
 enum DftOp { OP_DFT, OP_IDFT, OP_COSET_DFT, OP_COSET_LDE };
 
+// BUFFER CONTRACT (include/p3hip.h): an input and an output either coincide or are disjoint.  True when the two ranges share a word
+// without starting at the same one: no kernel defines what it reads then, so the entries refuse it before any launch.
+static bool partial_overlap(const uint32_t* in, size_t in_words, const uint32_t* out, size_t out_words) {
+    if (in == out) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    return a < b + out_words * 4 && b < a + in_words * 4;
+}
+static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
 static int dft_dev(DftOp op, const uint32_t* d_in, uint32_t* d_out, size_t h, size_t w, unsigned added_bits,
                    uint32_t shift, int br_out, hipStream_t stream) {
     return guarded([&]() -> int {
@@ -128,6 +137,8 @@ static int dft_dev(DftOp op, const uint32_t* d_in, uint32_t* d_out, size_t h, si
         if (!d_in || !d_out) return fail(ERR_BAD_ARG, "null matrix pointer");
         if (w > 0xffffffffull) return fail(ERR_BAD_ARG, "width too large");
         if (shift >= bb::P) return fail(ERR_BAD_ARG, "shift is not a reduced Montgomery word");
+        if (partial_overlap(d_in, h * w, d_out, (op == OP_COSET_LDE ? h << added_bits : h) * w))
+            return fail(ERR_BAD_ARG, "d_in and d_out overlap without being identical");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -240,6 +251,8 @@ int p3hip_coset_lde_from_coeffs_bb31_dev(const uint32_t* coeffs, uint32_t* out, 
     return guarded([&]() -> int {
         if (h == 0 || w == 0) return OK;
         if (!coeffs || !out || coeffs == out) return fail(ERR_BAD_ARG, "coset_lde_from_coeffs: null or aliased pointers");
+        if (partial_overlap(coeffs, h * w, out, (h << added_bits) * w))
+            return fail(ERR_BAD_ARG, "coset_lde_from_coeffs: d_coeffs and d_out overlap without being identical");
         if (w > 0xffffffffull) return fail(ERR_BAD_ARG, "width too large");
         if (shift >= bb::P) return fail(ERR_BAD_ARG, "shift is not a reduced Montgomery word");
         Context* cx;
@@ -269,6 +282,7 @@ int p3hip_bit_reverse_rows_dev(const uint32_t* in, uint32_t* out, size_t h, size
     return guarded([&]() -> int {
         if (h == 0 || w == 0) return OK;
         if (!in || !out || in == out) return fail(ERR_BAD_ARG, "bit_reverse_rows: null or aliased pointers");
+        if (partial_overlap(in, h * w, out, h * w)) return fail(ERR_BAD_ARG, "bit_reverse_rows: d_in and d_out overlap without being identical");
         return bit_reverse_rows((hipStream_t)stream, in, out, h, (uint32_t)w);
     });
 }
@@ -278,6 +292,7 @@ int p3hip_fib_trace_dev(uint64_t a, uint64_t b, size_t n, uint32_t* d_out, void*
     return guarded([&]() -> int {
         if (!n) return OK;
         if (!d_out) return fail(ERR_BAD_ARG, "fib_trace: null output");
+        if (misaligned(d_out, 8)) return fail(ERR_BAD_ARG, "fib_trace: d_out must be 8-byte aligned (rows of two words)");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -289,9 +304,13 @@ int p3hip_fib_trace_dev(uint64_t a, uint64_t b, size_t n, uint32_t* d_out, void*
 int p3hip_poseidon2_permute_dev(uint32_t* d_states, size_t n, void* stream) {
     return guarded([&]() -> int {
         if (n && !d_states) return fail(ERR_BAD_ARG, "null state pointer");
+        if (misaligned(d_states, 4)) return fail(ERR_BAD_ARG, "poseidon2_permute: d_states must be 4-byte aligned");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
+        // the per-lane forms move a state as four 16-byte pieces: states that are not 16-byte aligned take the 16-lane form, which moves
+        // single words (the same words out: tests/test_gpu_permutation_forms.py)
+        if (misaligned(d_states, 16)) return poseidon2_permute_states_variant((hipStream_t)stream, d_states, n, 3);
         return poseidon2_permute_states((hipStream_t)stream, d_states, n);
     });
 }
@@ -321,6 +340,8 @@ int p3hip_poseidon2_permute_variant_dev(uint32_t* d_states, size_t n, int varian
             return fail(ERR_BAD_ARG, "poseidon2 variant: 0 = int32, 1 = fp64, 2 = fp64 one state per quad, 3 = int32 one state per 16 lanes");
         if (n > ((size_t)1 << 26)) return fail(ERR_BAD_ARG, "poseidon2 variant: at most 2^26 states per call");
         if (!n) return OK;
+        if (misaligned(d_states, variant == 3 ? 4 : 16))
+            return fail(ERR_BAD_ARG, "poseidon2 variant: d_states must be 16-byte aligned (4-byte for variant 3)");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -334,6 +355,7 @@ int p3hip_poseidon2_f64_probe_dev(const double* d_in, uint32_t* d_out, size_t n,
             return fail(ERR_BAD_ARG, "probe mode: 0 = permutation, 1 = internal rounds, 2 = reduce, 3 = permutation, one state per quad");
         if (n > ((size_t)1 << 26)) return fail(ERR_BAD_ARG, "probe: at most 2^26 states per call");
         if (!n) return OK;
+        if (misaligned(d_in, 8)) return fail(ERR_BAD_ARG, "probe: d_in holds doubles and must be 8-byte aligned");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -389,6 +411,7 @@ int p3hip_mmcs_commit_into_dev(int hash, const uint32_t* const* d_mats, const si
                                uint32_t* d_layers, p3hip_tree_t** tree_out, void* stream) {
     return guarded([&]() -> int {
         if (!tree_out || !d_layers) return fail(ERR_BAD_ARG, "mmcs_commit_into: null argument");
+        if (misaligned(d_layers, 16)) return fail(ERR_BAD_ARG, "mmcs_commit_into: d_layers must be 16-byte aligned (digests move as 16-byte pieces)");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -402,6 +425,7 @@ int p3hip_mmcs_commit_into_dev(int hash, const uint32_t* const* d_mats, const si
 int p3hip_keccak_f_dev(uint64_t* d_states, size_t n, void* stream) {
     return guarded([&]() -> int {
         if (!d_states && n) return fail(ERR_BAD_ARG, "keccak_f: null states");
+        if (misaligned(d_states, 8)) return fail(ERR_BAD_ARG, "keccak_f: d_states must be 8-byte aligned (u64 lanes)");
         Context* cx;
         int rc = get_context(&cx);
         if (rc) return rc;
@@ -412,6 +436,7 @@ int p3hip_keccak_f_dev(uint64_t* d_states, size_t n, void* stream) {
 int p3hip_keccak_f_variant_dev(uint64_t* d_states, size_t n, int variant, void* stream) {
     return guarded([&]() -> int {
         if (!d_states && n) return fail(ERR_BAD_ARG, "keccak_f variant: null states");
+        if (misaligned(d_states, 8)) return fail(ERR_BAD_ARG, "keccak_f variant: d_states must be 8-byte aligned (u64 lanes)");
         if (variant < 0 || variant > 2) return fail(ERR_BAD_ARG, "keccak_f variant: 0 = permute, 1 = permute_digest, 2 = f_coop");
         if (n > ((size_t)1 << 24)) return fail(ERR_BAD_ARG, "keccak_f variant: at most 2^24 states per call");
         if (!n) return OK;
@@ -546,6 +571,7 @@ int p3hip_mmcs_commit_hash(int hash, const uint32_t* const* mats, const size_t* 
 // d_trace must be device memory of `device` (hipPointerGetAttributes) holding `rows` rows of two words from d_trace on
 static int check_device_trace(const uint32_t* d_trace, uint64_t rows, int device, const std::string& who) {
     if (!d_trace) return fail(ERR_BAD_ARG, who + ": null trace");
+    if (misaligned(d_trace, 8)) return fail(ERR_BAD_ARG, who + ": the trace must be 8-byte aligned (rows of two words)");
     hipPointerAttribute_t attr{};
     if (hipPointerGetAttributes(&attr, d_trace) != hipSuccess) {
         (void)hipGetLastError();

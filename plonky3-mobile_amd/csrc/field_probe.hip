@@ -139,6 +139,8 @@ int field_probe(hipStream_t stream, int op, const void* d_in, void* d_out, size_
     const OpInfo* o;
     int rc = check_probe_args("field_probe_dev", op, d_in, d_out, n, &o);
     if (rc || !n) return rc;  // a bad argument is refused before the thread's device context is looked up
+    if (o->f64 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 7u))
+        return fail(ERR_BAD_ARG, "field_probe_dev: d_in and d_out of an fp64 op hold doubles and must be 8-byte aligned");
     Context* cx;
     rc = get_context(&cx);
     if (rc) return rc;
