@@ -258,7 +258,10 @@ typedef struct p3hip_tree p3hip_tree_t;
  * digest layer in HBM and BORROWS the matrices (they must outlive the tree).  root_out is a host buffer;
  * the call synchronises the stream before returning the root.  d_mats[m]: heights[m] x widths[m] words, read-only, any 4-byte
  * alignment (of every p3hip_mmcs_commit*_dev entry; the salted Keccak leaf kernel of the hiding commit moves 16-byte rows and is
- * taken only when the rows allow it). */
+ * taken only when the rows allow it).  A matrix of width 0 is accepted, alone, inside a class and as an injected class: it adds
+ * nothing to its class's row, and an empty row hashes to the all-zero digest, as upstream's sponges do (its pointer is never
+ * read).  At most 64 matrices, at most 16 of one height: more are refused by name before anything is launched (the hiding commit:
+ * 32 and 8, before a salt is drawn). */
 int p3hip_mmcs_commit_dev(const uint32_t *const *d_mats, const size_t *heights, const size_t *widths,
                           size_t n_mats, uint32_t root_out[8], p3hip_tree_t **tree_out, void *stream);
 /* as above without the root download/synchronise (root readable later via p3hip_mmcs_root) */

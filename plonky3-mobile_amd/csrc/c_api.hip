@@ -913,6 +913,11 @@ int p3hip_mmcs_commit_hiding_dev(int hash, const uint32_t* const* d_mats, const 
         auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
         std::vector<const uint32_t*> mp;
         std::vector<size_t> hh, ww;
+        // the salted shape is refused here, before a salt is drawn: a refused commit leaves the rng's stream where it was
+        for (size_t i = 0; i < n_mats; i++) { hh.insert(hh.end(), {heights[i], heights[i]}); ww.insert(ww.end(), {widths[i], SALT}); }
+        if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return fail(ERR_BAD_ARG, "mmcs_commit: unknown hash configuration");
+        if (int rc = mmcs_check_shape(hh.data(), ww.data(), hh.size())) return rc;
+        hh.clear(); ww.clear();
         for (size_t i = 0; i < n_mats; i++) {
             void* salt = nullptr;
             if (hipMalloc(&salt, heights[i] * SALT * 4 + 16) != hipSuccess) { cleanup(); return fail(ERR_HIP, "hipMalloc failed"); }

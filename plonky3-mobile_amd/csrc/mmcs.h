@@ -30,6 +30,9 @@ struct Tree {
 int mmcs_commit(hipStream_t stream, const uint32_t* const* d_mats, const size_t* heights, const size_t* widths,
                 size_t n_mats, Tree** out, uint32_t* ext_layers = nullptr, uint32_t* root_copy = nullptr,
                 int kind = HASH_POSEIDON2, const size_t* strides = nullptr, int profile = PROFILE_LATENCY);
+// The shape checks of mmcs_commit alone (host only: nothing is launched, allocated or drawn): power-of-two heights, at most 64 matrices,
+// at most 16 of one height.  The hiding commit asks before it draws a salt, so that a refused shape leaves its rng where it was.
+int mmcs_check_shape(const size_t* heights, const size_t* widths, size_t n_mats);
 inline size_t mmcs_layer_words(uint64_t max_height) { return (size_t)(2 * max_height - 1) * 8; }
 int mmcs_root(hipStream_t stream, const Tree& t, uint32_t root_out[8]);
 int mmcs_open(hipStream_t stream, const Tree& t, uint64_t index, uint32_t* rows_out, uint32_t* path_out);

@@ -922,17 +922,28 @@ Tree::~Tree() {
     for (void* p : owned) (void)hipFree(p);
 }
 
+int mmcs_check_shape(const size_t* heights, const size_t* widths, size_t n_mats) {
+    if (!n_mats || !heights || !widths) return fail(ERR_BAD_ARG, "mmcs_commit: null/empty argument");
+    if (n_mats > 64) return fail(ERR_BAD_ARG, "mmcs_commit: at most 64 matrices per commitment");
+    for (size_t i = 0; i < n_mats; i++) {
+        if (!is_pow2(heights[i])) return fail(ERR_BAD_ARG, "mmcs_commit: heights must be powers of two");
+        if (widths[i] > 0xffffffffull) return fail(ERR_BAD_ARG, "mmcs_commit: width too large");
+    }
+    for (size_t i = 0; i < n_mats; i++) {
+        size_t cnt = 0;
+        for (size_t j = 0; j < n_mats; j++) cnt += heights[j] == heights[i];
+        if (cnt > MAX_CLASS_MATS) return fail(ERR_BAD_ARG, "mmcs_commit: more than 16 matrices of one height");
+    }
+    return OK;
+}
+
 int mmcs_commit(hipStream_t stream, const uint32_t* const* d_mats, const size_t* heights, const size_t* widths,
                 size_t n_mats, Tree** out, uint32_t* ext_layers, uint32_t* root_copy, int kind, const size_t* strides, int profile) {
     if (kind != HASH_POSEIDON2 && kind != HASH_KECCAK) return fail(ERR_BAD_ARG, "mmcs_commit: unknown hash configuration");
     if (!n_mats || !d_mats || !heights || !widths || !out) return fail(ERR_BAD_ARG, "mmcs_commit: null/empty argument");
-    if (n_mats > 64) return fail(ERR_BAD_ARG, "mmcs_commit: at most 64 matrices per commitment");
+    if (int rc = mmcs_check_shape(heights, widths, n_mats)) return rc;
     uint64_t maxh = 0;
-    for (size_t i = 0; i < n_mats; i++) {
-        if (!is_pow2(heights[i])) return fail(ERR_BAD_ARG, "mmcs_commit: heights must be powers of two");
-        if (widths[i] > 0xffffffffull) return fail(ERR_BAD_ARG, "mmcs_commit: width too large");
-        if (heights[i] > maxh) maxh = heights[i];
-    }
+    for (size_t i = 0; i < n_mats; i++) maxh = std::max<uint64_t>(maxh, heights[i]);
     std::unique_ptr<Tree> t(new Tree());
     t->kind = kind;
     for (size_t i = 0; i < n_mats; i++) {
@@ -942,12 +953,6 @@ int mmcs_commit(hipStream_t stream, const uint32_t* const* d_mats, const size_t*
         t->strides.push_back(st);
     }
     t->log_max_height = log2u(maxh);
-    for (uint64_t h = maxh; h >= 1; h >>= 1) {
-        size_t cnt = 0;
-        for (size_t i = 0; i < n_mats; i++) cnt += heights[i] == h;
-        if (cnt > MAX_CLASS_MATS) return fail(ERR_BAD_ARG, "mmcs_commit: more than 16 matrices of one height");
-        if (h == 1) break;
-    }
     size_t total_digests = 2 * maxh - 1;
     size_t staging_words = 0;
     for (size_t i = 0; i < n_mats; i++) staging_words += widths[i];
