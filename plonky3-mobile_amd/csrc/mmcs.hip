@@ -286,7 +286,9 @@ __global__ void __launch_bounds__(256) leaf_hash_f64_rowset_kernel(RowSet rs, ui
     for (int i = 0; i < 8; i++) d[i] = p2f::store_elem(s[i], smk);
     store_digest(digests + r * 8, d);
 }
-__global__ void __launch_bounds__(256) compress_layer_f64_kernel(const uint32_t* prev, uint32_t* next, uint64_t n_out) {
+// __launch_bounds__(256, 8): eight waves per SIMD, i.e. at most 64 VGPRs.  The permutation fits in 60; left to itself the scheduler spends 116 on the
+// unrolled internal rounds (p2f::internal_rounds) for no fewer instructions, and at four waves per SIMD the kernel loses what the shorter rounds gain.
+__global__ void __launch_bounds__(256, 8) compress_layer_f64_kernel(const uint32_t* prev, uint32_t* next, uint64_t n_out) {
     if (gridDim.x <= 512u) P3_LATENCY_BOUND_KERNEL();
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_out) return;
@@ -379,7 +381,8 @@ __global__ void poseidon2_permute_kernel(uint32_t* states, uint64_t n) {
 }
 
 
-__global__ void poseidon2_permute_f64_kernel(uint32_t* states, uint64_t n) {
+// __launch_bounds__(256, 8): see compress_layer_f64_kernel
+__global__ void __launch_bounds__(256, 8) poseidon2_permute_f64_kernel(uint32_t* states, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double s[16];

@@ -127,47 +127,83 @@ __device__ __forceinline__ void external_linear(double (&s)[16]) {
     for (int i = 0; i < 16; i++) s[i] += t[i & 3];
 }
 
+// The integer congruent (mod P) to a DYADIC FRACTION x = n / 2^F, F <= FRAC_BUDGET: fract(x) = (n mod 2^F) / 2^F is exact, and
+// x - fract(x) P = (n - (n mod 2^F) P) / 2^F is an integer because P = 1 (mod 2^27), congruent to n (2^F)^-1.  Two exact ops while
+// the result stays below 2^53: |result| < |x| + P.  For an integer x it returns x.
+__device__ __forceinline__ double fold_dyadic(double x) {
+    return __fma_rn(__builtin_amdgcn_fract(x), -PD, x);
+}
+
 // The 13 internal rounds.  Entry: integers |s_i| <= 2^37 (what the fourth external round leaves: 35 (P/2 + 2^9) < 2^35.1).
+// Exit: integers |s_i| < 2^37 (2^31.7 at most: a folded dyadic lane is below tot + its share of the entry + P).
 // V = [-2, 1, 2, 1/2, 3, 4, -1/2, -3, -4, 2^-8, 1/4, 1/8, 2^-27, -2^-8, -1/16, -2^-27]; 2^-27 = -15 (mod P)
-// because P - 1 = 15 * 2^27.  The integer-multiplier lanes grow up to 15x per round: fold them back after
-// every fourth round (15^4 * 2^37 < 2^53: still exact integers); the fractional lanes stay below their entry bound.
+// because P - 1 = 15 * 2^27.  EVERY lane update is one op, fma(s_i, V_i, tot):
+//   * the seven lanes with V_i = +-2^-k (3, 6, 9, 10, 11, 13, 14; k = 1, 1, 8, 2, 3, 8, 4) are carried as dyadic fractions: a double
+//     holds x 2^-k exactly, so the lane gains k fractional bits per round and is made an integer again (fold_dyadic) only after the
+//     round from which one more would pass FRAC_BUDGET = 16 bits, and after round 12.  Magnitudes shrink as the bits grow (a lane
+//     is below |entry| 2^-F + 2 |tot|), so magnitude + fraction stays inside 53 bits: 2^37 at F = 0 down to 2^31 at F = 16.
+//   * the round's lane sum is formed in two parts: ti over the nine integer lanes, tf over the seven dyadic ones (an integer over
+//     2^14 at most; |tf| < 2^39.9 in the first round, where F = 0, 2^37.6 in the second and falling: magnitude and fraction together
+//     stay below 48 bits at a sum); tot = reduce(ti + fold_dyadic(tf)).
+//   * the integer-multiplier lanes are folded (reduce) each by its own growth: x1, x2 (lanes 1, 2) after round 12 only (2^13 2^37
+//     = 2^50); x+-3, x+-4 (4, 5, 7, 8) after rounds 6 and 12 (4^7 2^37 = 2^51); x+-15 (12, 15) after rounds 3, 7 and 12 (15^4 2^37
+//     < 2^52.7, then 15^5 2^30 < 2^49.6).  |ti| < 2^50.3.
+// Operations outside the S-box: 13 x (8 + 6 adds, fold 2, add 1, reduce 3, 16 lanes) = 468, + 25 dyadic folds x 2 + 16 reduces x 3
+// = 566 (it was 13 x 48 + 96 = 720 with add_scaled_pow2 on the seven lanes every round and all eight integer lanes folded after
+// rounds 3, 7, 11, 12).  tests/poseidon2_dyadic_ref.py is the exact model of this schedule, step by step; the schedule differs from
+// round to round, so the thirteen rounds are unrolled (the folds below are compile-time decisions).
+constexpr int FRAC_BUDGET = 16;
+constexpr uint32_t dyadic_fold_rounds(int k) {  // bit r: fold the 2^-k lane after round r
+    uint32_t m = 0;
+    for (int r = 0, f = 0; r < 13; r++) {
+        f += k;
+        if (f + k > FRAC_BUDGET || r == 12) { m |= 1u << r; f = 0; }
+    }
+    return m;
+}
+constexpr uint32_t FOLD_K1 = dyadic_fold_rounds(1), FOLD_K2 = dyadic_fold_rounds(2), FOLD_K3 = dyadic_fold_rounds(3),
+                   FOLD_K4 = dyadic_fold_rounds(4), FOLD_K8 = dyadic_fold_rounds(8);
+constexpr uint32_t FOLD_X2 = 1u << 12, FOLD_X4 = (1u << 6) | (1u << 12), FOLD_X15 = (1u << 3) | (1u << 7) | (1u << 12);
+static_assert(FOLD_K1 == 0x1000 && FOLD_K2 == 0x1080 && FOLD_K3 == 0x1210 && FOLD_K4 == 0x1888 && FOLD_K8 == 0x1aaa, "fold schedule");
 __device__ __forceinline__ void internal_rounds(double (&s)[16], const MagicRegs& mk) {
     const double npm1 = d_c.neg_pm1, pinv = d_c.pinv;
     const double k3 = d_c.k3, k15 = d_c.k15, i4 = d_c.i4, i8 = d_c.i8, i16 = d_c.i16, i256 = d_c.i256;
+    // A lambda on purpose, as before: a lambda is a host-device function, and a __constant__ table that such a function reads is
+    // emitted as externally initialised, so its entries are LOADED (s_load into SGPR pairs, one VOP3 operand each).  Read from
+    // device functions only, d_c becomes a private constant of the translation unit whose values the compiler writes as literals:
+    // v_fmac + a v_mov_b64 copy of the addend per use (see MagicRegs), in every kernel that reads d_c, the quad form's included.
     auto internal_round = [&](int r) {
         s[0] = sbox7(s[0] + d_c.in[r], mk, npm1, pinv);
-        double tot = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])) +
-                     (((s[8] + s[9]) + (s[10] + s[11])) + ((s[12] + s[13]) + (s[14] + s[15])));
-        tot = reduce(tot);
+        const double ti = (((s[0] + s[1]) + (s[2] + s[4])) + ((s[5] + s[7]) + (s[8] + s[12]))) + s[15];
+        const double tf = ((s[3] + s[6]) + (s[9] + s[10])) + ((s[11] + s[13]) + s[14]);
+        const double tot = reduce(ti + fold_dyadic(tf));
         s[0] = __fma_rn(s[0], -2.0, tot);
         s[1] = tot + s[1];
         s[2] = __fma_rn(s[2], 2.0, tot);
-        s[3] = add_scaled_pow2(tot, s[3], 0.5);
+        s[3] = __fma_rn(s[3], 0.5, tot);
         s[4] = __fma_rn(s[4], k3, tot);
         s[5] = __fma_rn(s[5], 4.0, tot);
-        s[6] = add_scaled_pow2(tot, s[6], -0.5);
+        s[6] = __fma_rn(s[6], -0.5, tot);
         s[7] = __fma_rn(s[7], -k3, tot);
         s[8] = __fma_rn(s[8], -4.0, tot);
-        s[9] = add_scaled_pow2(tot, s[9], i256);
-        s[10] = add_scaled_pow2(tot, s[10], i4);
-        s[11] = add_scaled_pow2(tot, s[11], i8);
+        s[9] = __fma_rn(s[9], i256, tot);
+        s[10] = __fma_rn(s[10], i4, tot);
+        s[11] = __fma_rn(s[11], i8, tot);
         s[12] = __fma_rn(s[12], -k15, tot);
-        s[13] = add_scaled_pow2(tot, s[13], -i256);
-        s[14] = add_scaled_pow2(tot, s[14], -i16);
+        s[13] = __fma_rn(s[13], -i256, tot);
+        s[14] = __fma_rn(s[14], -i16, tot);
         s[15] = __fma_rn(s[15], k15, tot);
+        if (FOLD_K1 >> r & 1) { s[3] = fold_dyadic(s[3]); s[6] = fold_dyadic(s[6]); }
+        if (FOLD_K8 >> r & 1) { s[9] = fold_dyadic(s[9]); s[13] = fold_dyadic(s[13]); }
+        if (FOLD_K2 >> r & 1) s[10] = fold_dyadic(s[10]);
+        if (FOLD_K3 >> r & 1) s[11] = fold_dyadic(s[11]);
+        if (FOLD_K4 >> r & 1) s[14] = fold_dyadic(s[14]);
+        if (FOLD_X2 >> r & 1) { s[1] = reduce(s[1]); s[2] = reduce(s[2]); }
+        if (FOLD_X4 >> r & 1) { s[4] = reduce(s[4]); s[5] = reduce(s[5]); s[7] = reduce(s[7]); s[8] = reduce(s[8]); }
+        if (FOLD_X15 >> r & 1) { s[12] = reduce(s[12]); s[15] = reduce(s[15]); }
     };
-    auto fold_integer_lanes = [&]() {
-        s[1] = reduce(s[1]); s[2] = reduce(s[2]); s[4] = reduce(s[4]); s[5] = reduce(s[5]);
-        s[7] = reduce(s[7]); s[8] = reduce(s[8]); s[12] = reduce(s[12]); s[15] = reduce(s[15]);
-    };
-    _Pragma("clang loop unroll(disable)")
-    for (int blk = 0; blk < 3; blk++) {
-        _Pragma("clang loop unroll(disable)")
-        for (int r = 0; r < 4; r++) internal_round(4 * blk + r);
-        fold_integer_lanes();
-    }
-    internal_round(12);
-    fold_integer_lanes();
+#pragma unroll
+    for (int r = 0; r < 13; r++) internal_round(r);
 }
 
 // Entry: integers |s_i| <= 2^32.  That is what the S-box's stated contract (mulmod_m: |ab| < 2^76) supports: the first round's

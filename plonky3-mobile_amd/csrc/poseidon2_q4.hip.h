@@ -75,7 +75,9 @@ __device__ __forceinline__ void permute(double (&s)[4], const LaneConsts& c, boo
         external_linear(s);
     }
     // internal rounds: the integer-multiplier elements grow up to 15x per round and are folded back after every fourth round
-    // (15^4 2^37 < 2^53), exactly as in p2f::internal_rounds; folding the fractional-multiplier elements too is harmless
+    // (15^4 2^37 < 2^53); folding the fractional-multiplier elements too is harmless.  This is the quad form's OWN schedule (the one
+    // p2f::internal_rounds had until it took to carrying its 2^-k lanes as dyadic fractions and folding lane by lane): a lane here
+    // holds four elements with four different multipliers, so one three-op add_scaled_pow2 per element and a common fold stay
     _Pragma("clang loop unroll(disable)")
     for (int r = 0; r < 13; r++) {
         const double sb = p2f::sbox7(s[0] + p2f::d_c.in[r], mk, npm1, pinv);

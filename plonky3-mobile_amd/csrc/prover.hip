@@ -294,7 +294,8 @@ __global__ void __launch_bounds__(256) fri_fold_rollin_kernel(TwoLevelTable inv_
 // GrindingChallenger::grind: smallest canonical w with sample_bits(bits) == 0 after observe(w).  The sponge state
 // with the pending inputs comes from the device transcript; blocks whose whole range lies above a witness already
 // found return at once (the smallest one wins through atomicMin, as in a serial search).
-__global__ void __launch_bounds__(256) grind_kernel(DevState* ds, uint32_t mask, uint32_t base) {
+// __launch_bounds__(256, 8): see compress_layer_f64_kernel (mmcs.hip)
+__global__ void __launch_bounds__(256, 8) grind_kernel(DevState* ds, uint32_t mask, uint32_t base) {
     uint32_t w = base + blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= bb::P) return;
     if (base + blockIdx.x * blockDim.x > *(volatile uint32_t*)&ds->grind_result) return;
