@@ -868,6 +868,51 @@ int p3hip_air_check_trace_dev(p3hip_air_t *air, void *stream, const uint32_t *d_
  * is_last_row, is_transition at the point, 4 words each; out = sum_k alpha^(K-1-k) c_k by Horner's rule. */
 int p3hip_air_eval_ext(const p3hip_air_t *air, const uint32_t *local, const uint32_t *next, const uint32_t *pis, const uint32_t *sels,
                        const uint32_t alpha[4], uint32_t out[4]);
+/* DIAGNOSTIC: p3hip_air_eval_ext at n points in one launch, one lane per point (the interpreter core of the batch verifier's
+ * av_eval_kernel).  Device buffers, 4-byte aligned, read-only; per point width x 4 (d_local), width x 4 (d_next), n_public (d_pis; may be
+ * NULL when n_public == 0), 12 (d_sels) and 4 (d_alpha) Montgomery words, which the caller keeps canonical; exactly 4 n words of d_out
+ * are written.  Enqueues only; n = 0 is no operation; n > 2^20 is refused. */
+int p3hip_air_eval_ext_dev(p3hip_air_t *air, void *stream, const uint32_t *d_local, const uint32_t *d_next, const uint32_t *d_pis,
+                           const uint32_t *d_sels, const uint32_t *d_alpha, size_t n, uint32_t *d_out);
+/* p3_uni_stark::verify for a proof of an `air` of the caller's (the bytes plonky3-mobile_amd/air.py prove_air returns: the header —
+ * magic, 1, log_n, the trace and quotient roots, width and the local values, width and the next values, the chunk count C =
+ * 2^log_quotient_degree and per chunk 4 and its 16 words — then the PCS's FriProof section).  DESIGN.md section 5.4.
+ * p3hip_air_proof_len: the byte length every such proof has, 4 (3 + 16 + 2 (1 + 4 width) + 1 + 17 C) + p3hip_pcs_proof_len of the PCS
+ * shape log_h = log_n, two rounds of [1, C] matrices of widths [width, 4, .., 4], the trace opened at [zeta, zeta g_n], every chunk at
+ * [zeta].  Host only.  The gates and their messages are the PCS verifier's, plus 1 <= log_n <= 27 - log_quotient_degree and log_blowup >=
+ * log_quotient_degree, each named when it fails. */
+int p3hip_air_proof_len(const p3hip_air_t *air, int hash, unsigned log_n, const p3hip_fri_params_t *params, size_t *len_out);
+/* One proof on the host.  *reject_code = 0: accepted; 1 magic or version, 2 log_n, 3 a count that is not the AIR's, 4 a truncated header
+ * or a header field word >= P (the roots under Poseidon2 only), 10 OodEvaluationMismatch (the constraints at zeta, folded by Horner's
+ * rule, against quotient(zeta) Z_H(zeta)), else p3hip_pcs_verify's code for the shape above with the opened values in the order local,
+ * next, chunk 0 .. C - 1.  The transcript observes log_n twice, the trace root and the publics, samples alpha, observes the quotient root
+ * and samples zeta.  pis: n_public Montgomery words; one >= P is P3HIP_ERR_BAD_ARG, as is log_n outside 1 .. 27 - log_quotient_degree. */
+int p3hip_air_verify(const p3hip_air_t *air, int hash, unsigned log_n, const p3hip_fri_params_t *params, const uint8_t *proof, size_t len,
+                     const uint32_t *pis, int *reject_code);
+/* BATCHES of such proofs of ONE (air, hash, log_n, params) verified ON THE DEVICE; p3hip_air_verify is the specification and the
+ * contract is p3hip_fib_verifier_*'s.  create copies what it needs of the program (the air may be destroyed afterwards), owns all device
+ * scratch (a p3hip_pcs_verifier of the shape above included) and remembers the calling thread's current device: later calls are
+ * redirected to it.  REJECT CODES, with H = p3hip_air_verify's result for the member: status 0 exactly when H accepts; status = H when H
+ * is 10, 11, 13, 14 or 15 AND the proof has p3hip_air_proof_len bytes AND every count / width / depth word is the one the shape
+ * dictates, the FRI section's included, AND every field word of the proof and every public value is canonical.  Everything else is
+ * P3HIP_VERIFY_MALFORMED: H in 1..9 or 12, a wrong length, a word >= P, or what the host refuses for the member's values.  A member whose
+ * header values fail the OOD check AND whose FRI section is malformed is MALFORMED: the host stops at 10 there and never looks at the
+ * FRI section.
+ * verify_dev: n <= max_proofs members in device memory, proof i at d_proofs + i * stride_bytes (4-byte aligned; the stride a multiple
+ * of 4 and >= p3hip_air_proof_len); d_lens: n u32 byte lengths or NULL (a proof of another length is rejected unread); d_pis: n x
+ * n_public Montgomery words, may be NULL when n_public == 0.  Enqueues only (seven launches and one 4-byte memset on `stream`): no
+ * allocation, no host copy, no synchronise.  Every input is read-only; exactly n words of d_status and one of d_rejected (may be NULL)
+ * are written.  Batch-level faults are refused with P3HIP_ERR_BAD_ARG before any launch.  One call at a time per verifier.
+ * verify: host convenience; stages on a stream of its own (staging allocated by the first call), splits n > max_proofs into rounds,
+ * synchronises.  pis: n x n_public words of host memory. */
+typedef struct p3hip_air_verifier p3hip_air_verifier_t;
+int p3hip_air_verifier_create(const p3hip_air_t *air, int hash, unsigned log_n, const p3hip_fri_params_t *params, size_t max_proofs,
+                              p3hip_air_verifier_t **out);
+int p3hip_air_verifier_verify_dev(p3hip_air_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,
+                                  const uint32_t *d_pis, size_t n, uint32_t *d_status, uint32_t *d_rejected, void *stream);
+int p3hip_air_verifier_verify(p3hip_air_verifier_t *v, size_t n, const uint8_t *const *proofs, const size_t *lens, const uint32_t *pis,
+                              uint32_t *status_out);
+void p3hip_air_verifier_destroy(p3hip_air_verifier_t *v);
 
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */

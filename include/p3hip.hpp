@@ -555,9 +555,66 @@ class Air {
         return out;
     }
 
+    // eval_ext at n points in one launch (device buffers; enqueues only)
+    void eval_ext_dev(void* stream, const uint32_t* d_local, const uint32_t* d_next, const uint32_t* d_pis, const uint32_t* d_sels,
+                      const uint32_t* d_alpha, size_t n, uint32_t* d_out) {
+        check(p3hip_air_eval_ext_dev(h_, stream, d_local, d_next, d_pis, d_sels, d_alpha, n, d_out));
+    }
+
   private:
     p3hip_air_t* h_ = nullptr;
     p3hip_air_info_t info_{};
+};
+
+// p3_uni_stark::verify for proofs of a caller-defined AIR (p3hip.h p3hip_air_proof_len / p3hip_air_verify / p3hip_air_verifier_*).
+// The byte length every proof of (air, log_n, fp, hash) has; host only.
+inline size_t air_proof_len(const Air& air, unsigned log_n, FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2) {
+    p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+    size_t len = 0;
+    check(p3hip_air_proof_len(air.handle(), hash, log_n, &c, &len));
+    return len;
+}
+// One proof on the host: 0 = accept, else the failed check's code (1-4 header, 10 OodEvaluationMismatch, the PCS verifier's otherwise)
+inline int air_verify(const Air& air, const std::vector<uint8_t>& proof, const std::vector<uint32_t>& pis, unsigned log_n,
+                      FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2) {
+    if (pis.size() != air.info().n_public) throw Error(P3HIP_ERR_BAD_ARG, "air_verify: n_public public values");
+    p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+    int code = 0;
+    check(p3hip_air_verify(air.handle(), hash, log_n, &c, proof.data(), proof.size(), pis.data(), &code));
+    return code;
+}
+// Batches of such proofs on the device.  The Air may be destroyed once the verifier exists.
+class AirVerifier {
+  public:
+    AirVerifier(const Air& air, unsigned log_n, FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2, size_t max_proofs = 64)
+        : n_public_(air.info().n_public), proof_len_(air_proof_len(air, log_n, fp, hash)) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        check(p3hip_air_verifier_create(air.handle(), hash, log_n, &c, max_proofs, &h_));
+    }
+    AirVerifier(const AirVerifier&) = delete;
+    AirVerifier& operator=(const AirVerifier&) = delete;
+    ~AirVerifier() { p3hip_air_verifier_destroy(h_); }
+    size_t proof_len() const { return proof_len_; }
+    // pis: n_public Montgomery words per proof; one status per proof (0, 10, 11, 13, 14, 15 or P3HIP_VERIFY_MALFORMED)
+    std::vector<uint32_t> verify_many(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<uint32_t>& pis) {
+        const size_t n = proofs.size();
+        if (pis.size() != n * n_public_) throw Error(P3HIP_ERR_BAD_ARG, "AirVerifier: n_public public values per proof");
+        std::vector<const uint8_t*> ptrs(n);
+        std::vector<size_t> lens(n);
+        for (size_t i = 0; i < n; i++) { ptrs[i] = proofs[i].data(); lens[i] = proofs[i].size(); }
+        std::vector<uint32_t> status(n);
+        check(p3hip_air_verifier_verify(h_, n, ptrs.data(), lens.data(), pis.data(), status.data()));
+        return status;
+    }
+    // device-resident members: enqueues on `stream`, nothing is waited for
+    void verify_many_dev(const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens, const uint32_t* d_pis, size_t n, uint32_t* d_status,
+                         uint32_t* d_rejected, void* stream) {
+        check(p3hip_air_verifier_verify_dev(h_, d_proofs, stride_bytes, d_lens, d_pis, n, d_status, d_rejected, stream));
+    }
+
+  private:
+    p3hip_air_verifier_t* h_ = nullptr;
+    size_t n_public_ = 0, proof_len_ = 0;
 };
 
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"

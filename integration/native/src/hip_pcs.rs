@@ -238,6 +238,44 @@ extern "C" {
     fn p3hip_download(host_dst: *mut c_void, dev_src: *const c_void, bytes: usize) -> i32;
 }
 
+// include/p3hip.h "caller-defined AIRs": an AIR as a validated program, its proofs verified on the host (one) and on the device (batches).
+// Declarations only: what verifies the proofs p3hip_air_quotient_dev helped to make; no Rust type wraps them yet.
+#[repr(C)]
+pub struct p3hip_air_t {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct p3hip_air_verifier_t {
+    _private: [u8; 0],
+}
+#[allow(dead_code)]
+extern "C" {
+    fn p3hip_air_create(
+        width: usize, n_public: usize, code: *const u32, n_instr: usize, consts: *const u32, n_consts: usize, out: *mut *mut p3hip_air_t,
+    ) -> i32;
+    fn p3hip_air_destroy(air: *mut p3hip_air_t);
+    fn p3hip_air_proof_len(air: *const p3hip_air_t, hash: i32, log_n: u32, params: *const p3hip_fri_params_t, len_out: *mut usize) -> i32;
+    fn p3hip_air_verify(
+        air: *const p3hip_air_t, hash: i32, log_n: u32, params: *const p3hip_fri_params_t, proof: *const u8, len: usize, pis: *const u32,
+        reject_code: *mut i32,
+    ) -> i32;
+    fn p3hip_air_eval_ext_dev(
+        air: *mut p3hip_air_t, stream: *mut c_void, d_local: *const u32, d_next: *const u32, d_pis: *const u32, d_sels: *const u32,
+        d_alpha: *const u32, n: usize, d_out: *mut u32,
+    ) -> i32;
+    fn p3hip_air_verifier_create(
+        air: *const p3hip_air_t, hash: i32, log_n: u32, params: *const p3hip_fri_params_t, max_proofs: usize, out: *mut *mut p3hip_air_verifier_t,
+    ) -> i32;
+    fn p3hip_air_verifier_verify_dev(
+        v: *mut p3hip_air_verifier_t, d_proofs: *const u8, stride_bytes: usize, d_lens: *const u32, d_pis: *const u32, n: usize,
+        d_status: *mut u32, d_rejected: *mut u32, stream: *mut c_void,
+    ) -> i32;
+    fn p3hip_air_verifier_verify(
+        v: *mut p3hip_air_verifier_t, n: usize, proofs: *const *const u8, lens: *const usize, pis: *const u32, status_out: *mut u32,
+    ) -> i32;
+    fn p3hip_air_verifier_destroy(v: *mut p3hip_air_verifier_t);
+}
+
 // BabyBear is a transparent u32 holding the Montgomery word (the same reinterpretation backend_hip.rs makes of `shift`), and
 // BinomialExtensionField<Val, 4> is its four coefficients in order [UPSTREAM-RECALL]
 fn vals_from_monty_words(words: Vec<u32>) -> Vec<Val> {

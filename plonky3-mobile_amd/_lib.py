@@ -174,6 +174,14 @@ _SIGS = {
     "p3hip_air_quotient_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "p3hip_air_check_trace_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "p3hip_air_eval_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3hip_air_eval_ext_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "p3hip_air_proof_len": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "p3hip_air_verify": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
+    "p3hip_air_verifier_create": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "p3hip_air_verifier_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "p3hip_air_verifier_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_void_p, u32p]),
+    "p3hip_air_verifier_destroy": (None, [C.c_void_p]),
     "p3hip_pcs_destroy": (None, [C.c_void_p]),
 }
 

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .fib_air import VERIFY_MALFORMED, FriParameters, _hash_kind
 from .gpu_dft import P, _is_torch, _stream_ptr, dev_u32
 from .pcs import Challenger, PcsRejected, _words
 
@@ -294,6 +295,37 @@ class Air:
         _lib.check(_lib.lib().p3hip_air_eval_ext(self._h, vp(lo), vp(nx), pp, vp(s), vp(al), vp(out)))
         return out
 
+    def eval_ext_many(self, local, next, pis, sels, alpha, out=None):
+        """eval_ext at n points in one launch, one lane per point (p3hip_air_eval_ext_dev): contiguous 32-bit device tensors of n x
+        width x 4, n x width x 4, n x n_public (None when the AIR has no public values), n x 12 and n x 4 canonical Montgomery words ->
+        an (n, 4) int32 device tensor (or `out`, of which 4 n words are written).  Enqueued on torch's current stream, not
+        synchronised; at most 2^20 points a call."""
+        import torch
+        n = int(alpha.numel()) // 4
+        need = [(local, 4 * self.width * n), (next, 4 * self.width * n), (sels, 12 * n), (alpha, 4 * n)] + ([(pis, self.n_public * n)] if self.n_public else [])
+        for t, words in need:
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != words:
+                raise ValueError("eval_ext_many: contiguous device tensors of 32-bit words, one row per point")
+        if out is None:
+            out = torch.empty((max(n, 1), 4), dtype=torch.int32, device=alpha.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.element_size() != 4 or out.numel() < 4 * n:
+            raise ValueError("eval_ext_many: out must hold 4 words per point")
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().p3hip_air_eval_ext_dev(self._h, _stream_ptr(), ptr(local), ptr(next), ptr(pis) if self.n_public else None, ptr(sels),
+                                                     ptr(alpha), n, ptr(out)))
+        return out.reshape(-1, 4)[:n]
+
+    def verify(self, proof, pis, log_n, params, hash="poseidon2"):
+        """p3_uni_stark::verify for one proof, the library's host verifier (p3hip_air_verify): 0 = accept, else the code AirRejected
+        carries (1-4 header, 10 OodEvaluationMismatch, the PCS verifier's otherwise).  A refused argument raises P3HipError(-1)."""
+        p, pp = self._pis(pis)
+        buf = (C.c_uint8 * max(len(proof), 1)).from_buffer_copy(bytes(proof) or b"\0")
+        code = C.c_int()
+        _lib.check(_lib.lib().p3hip_air_verify(self._h, _hash_kind(hash), int(log_n), C.cast(params._c(), C.c_void_p), buf, len(proof), pp, C.byref(code)))
+        if code.value:
+            _lib.take_last_error()
+        return code.value
+
     def free(self):
         if self._h:
             _lib.lib().p3hip_air_destroy(self._h)
@@ -530,3 +562,78 @@ def verify_air(air, proof, pis, log_n, params, hash="poseidon2"):
         raise AirRejected(e.code, e.message)
     finally:
         ch.free()
+
+
+# ---- the library's verifiers: one proof on the host (Air.verify), batches on the device ----
+def air_proof_len(air, log_n, params, hash="poseidon2"):
+    """The byte length every prove_air proof of `air` at 2^log_n rows has (p3hip_air_proof_len; host only).  A refused gate raises
+    P3HipError(-1) naming it."""
+    out = C.c_size_t()
+    _lib.check(_lib.lib().p3hip_air_proof_len(air._h, _hash_kind(hash), int(log_n), C.cast(params._c(), C.c_void_p), C.byref(out)))
+    return out.value
+
+
+class AirVerifier:
+    """p3_uni_stark::verify for batches of prove_air proofs of ONE (air, log_n, params, hash) on the device (include/p3hip.h
+    p3hip_air_verifier_*).  The air may be freed once the verifier exists.  Statuses: 0 = accept, 10 OodEvaluationMismatch, the PCS
+    verifier's 11 / 13 / 14 / 15, or VERIFY_MALFORMED (16)."""
+
+    def __init__(self, air, log_n, params=None, hash="poseidon2", max_proofs=64):
+        self.params = params or FriParameters()
+        self.log_n, self.hash, self.max_proofs, self.n_public = int(log_n), hash, max_proofs, air.n_public
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p3hip_air_verifier_create(air._h, _hash_kind(hash), self.log_n, C.cast(self.params._c(), C.c_void_p), max_proofs,
+                                                        C.byref(self._h)))
+        self.proof_len = air_proof_len(air, log_n, self.params, hash)
+
+    def verify_many(self, proofs, pis):
+        """proofs: a list of bytes; pis: (n, n_public) Montgomery words (None or empty when the AIR has no public values).  Returns a
+        numpy uint32 array of statuses; batches larger than max_proofs are split."""
+        n = len(proofs)
+        status = np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return status
+        p = _words(pis if pis is not None else [], n * self.n_public)
+        ptrs = (C.c_char_p * n)(*[bytes(x) for x in proofs])
+        lens = (C.c_size_t * n)(*[len(x) for x in proofs])
+        _lib.check(_lib.lib().p3hip_air_verifier_verify(self._h, n, ptrs, lens, p.ctypes.data_as(C.c_void_p) if p.size else None,
+                                                        status.ctypes.data_as(_lib.u32p)))
+        return status
+
+    def verify_many_dev(self, proofs, pis, lens=None, n=None, stride=None, status=None, rejected=None):
+        """The device entry on torch tensors, enqueued on torch's current stream and not synchronised.  proofs: a contiguous uint8 /
+        int32 device tensor, proof i at byte i * stride (default: the row length of a 2-d tensor); pis: a contiguous 32-bit device
+        tensor of n x n_public words (None when the AIR has no public values); lens: n 32-bit byte lengths or None.  Returns (status,
+        rejected): int32 device tensors of n codes and one count (rejected=False: no count is written, None is returned)."""
+        import torch
+        if n is None:
+            n = proofs.shape[0] if proofs.dim() == 2 else (pis.numel() // self.n_public if self.n_public else 0)
+        if stride is None:
+            stride = proofs.stride(0) * proofs.element_size() if proofs.dim() == 2 else self.proof_len
+        for t, words in ([(pis, n * self.n_public)] if self.n_public else []) + ([(lens, n)] if lens is not None else []):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() < words:
+                raise ValueError("expected contiguous device tensors of 32-bit words, one row per member")
+        if not proofs.is_cuda or not proofs.is_contiguous():
+            raise ValueError("expected contiguous device tensors")
+        if n and proofs.numel() * proofs.element_size() < (n - 1) * stride + self.proof_len:
+            raise ValueError("the proofs tensor is shorter than n proofs")
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=proofs.device)
+        if rejected is None:
+            rejected = torch.empty(1, dtype=torch.int32, device=proofs.device)
+        _lib.check(_lib.lib().p3hip_air_verifier_verify_dev(
+            self._h, C.c_void_p(proofs.data_ptr()), stride, C.c_void_p(lens.data_ptr()) if lens is not None else None,
+            C.c_void_p(pis.data_ptr()) if self.n_public else None, n, C.c_void_p(status.data_ptr()),
+            C.c_void_p(rejected.data_ptr()) if rejected is not False else None, _stream_ptr()))
+        return status[:n], (rejected if rejected is not False else None)
+
+    def close(self):
+        if self._h:
+            _lib.lib().p3hip_air_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -34,6 +34,9 @@ struct Air {
     ~Air();
 };
 
+// makes the device copies of the program on the calling thread's current device (what the first device call of an Air does)
+int air_ensure_device(Air& a);
+
 }  // namespace p3
 
 struct p3hip_air {

@@ -306,6 +306,8 @@ int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la
 
 }  // namespace
 
+int air_ensure_device(Air& a) { return ensure_device(a); }
+
 Air::~Air() {
     if (d_code) (void)hipFree(d_code);  // waits for the device: an enqueued upload or kernel of this object has run when it returns
     if (h_pin) (void)hipHostFree(h_pin);

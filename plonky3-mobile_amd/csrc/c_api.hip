@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "air_verifier_dev.h"
 #include "bb31.hip.h"
 #include "challenger.h"
 #include "common.h"
@@ -1561,4 +1562,64 @@ int p3hip_pcs_verifier_verify(p3hip_pcs_verifier_t* v, size_t n, const uint8_t* 
 }
 int p3hip_pcs_verifier_wave_form(const p3hip_pcs_verifier_t* v) { return v && v->v.wave_form() ? 1 : 0; }
 void p3hip_pcs_verifier_destroy(p3hip_pcs_verifier_t* v) { delete v; }
+}  // extern "C"
+
+// ---- proofs of caller-defined AIRs verified on the host and, in batches, on the device (air_verifier_dev.hip) ----
+struct p3hip_air_verifier {
+    AirVerifierDev v;
+};
+extern "C" {
+int p3hip_air_proof_len(const p3hip_air_t* air, int hash, unsigned log_n, const p3hip_fri_params_t* params, size_t* len_out) {
+    return guarded([&]() -> int {
+        if (!air || !params || !len_out) return fail(ERR_BAD_ARG, "air_proof_len: null argument");
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        return air_proof_len(air->a, hash, log_n, fp, len_out);
+    });
+}
+int p3hip_air_verify(const p3hip_air_t* air, int hash, unsigned log_n, const p3hip_fri_params_t* params, const uint8_t* proof, size_t len,
+                     const uint32_t* pis, int* reject_code) {
+    return guarded([&]() -> int {
+        if (!air || !params || (!proof && len) || !reject_code || (!pis && air->a.n_public)) return fail(ERR_BAD_ARG, "air_verify: null argument");
+        *reject_code = 0;
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::string why;
+        const int rc = air_verify(air->a, hash, log_n, fp, proof, len, pis, &why);
+        if (rc < 0) return fail(rc, why);
+        if (rc > 0) { *reject_code = rc; set_error("air verification failed: " + why); }
+        return OK;
+    });
+}
+int p3hip_air_eval_ext_dev(p3hip_air_t* air, void* stream, const uint32_t* d_local, const uint32_t* d_next, const uint32_t* d_pis,
+                           const uint32_t* d_sels, const uint32_t* d_alpha, size_t n, uint32_t* d_out) {
+    return guarded([&]() -> int {
+        if (!air) return fail(ERR_BAD_ARG, "air_eval_ext_dev: null argument");
+        return air_eval_ext_dev(air->a, static_cast<hipStream_t>(stream), d_local, d_next, d_pis, d_sels, d_alpha, n, d_out);
+    });
+}
+int p3hip_air_verifier_create(const p3hip_air_t* air, int hash, unsigned log_n, const p3hip_fri_params_t* params, size_t max_proofs,
+                              p3hip_air_verifier_t** out) {
+    return guarded([&]() -> int {
+        if (!air || !params || !out) return fail(ERR_BAD_ARG, "air_verifier_create: null argument");
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        std::unique_ptr<p3hip_air_verifier> h(new p3hip_air_verifier());
+        if (int rc = h->v.init(air->a, hash, log_n, fp, max_proofs)) return rc;
+        *out = h.release();
+        return OK;
+    });
+}
+int p3hip_air_verifier_verify_dev(p3hip_air_verifier_t* v, const uint8_t* d_proofs, size_t stride_bytes, const uint32_t* d_lens,
+                                  const uint32_t* d_pis, size_t n, uint32_t* d_status, uint32_t* d_rejected, void* stream) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "air_verifier_verify_dev: null verifier");
+        return v->v.verify_dev(d_proofs, stride_bytes, d_lens, d_pis, n, d_status, d_rejected, static_cast<hipStream_t>(stream));
+    });
+}
+int p3hip_air_verifier_verify(p3hip_air_verifier_t* v, size_t n, const uint8_t* const* proofs, const size_t* lens, const uint32_t* pis,
+                              uint32_t* status_out) {
+    return guarded([&]() -> int {
+        if (!v) return fail(ERR_BAD_ARG, "air_verifier_verify: null verifier");
+        return v->v.verify_host(n, proofs, lens, pis, status_out);
+    });
+}
+void p3hip_air_verifier_destroy(p3hip_air_verifier_t* v) { delete v; }
 }  // extern "C"
