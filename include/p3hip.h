@@ -561,7 +561,7 @@ int p3hip_fib_verifier_create(int hash, int hiding, unsigned log_n, const p3hip_
  * 4-byte aligned, stride a multiple of 4, >= p3hip_fib_proof_len); d_lens: n u32 byte lengths, or NULL = every proof has
  * p3hip_fib_proof_len bytes (a proof of another length is rejected without being read); d_pis: n x 3 Montgomery words [a, b, x] (the
  * convention of p3hip_fib_prover_prove_trace_dev); d_status: n codes; *d_rejected (may be NULL) = count of nonzero codes.  Enqueues
- * only (four launches and one 4-byte memset on `stream`): no allocation, no host copy, no synchronise; can be captured.  One call at
+ * only (five launches and one 4-byte memset on `stream`): no allocation, no host copy, no synchronise; can be captured.  One call at
  * a time per verifier: the scratch is reused in stream order.  Every input is read-only; exactly n words of d_status and one of
  * d_rejected are written, whatever max_proofs is. */
 int p3hip_fib_verifier_verify_dev(p3hip_fib_verifier_t *v, const uint8_t *d_proofs, size_t stride_bytes, const uint32_t *d_lens,

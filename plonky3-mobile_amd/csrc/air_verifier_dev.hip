@@ -1,6 +1,6 @@
 // p3_uni_stark::verify for a caller-defined AIR (air.h): ONE proof on the host (air_verify: plonky3-mobile_amd/air.py verify_air
 // restated step for step, the specification of everything below) and BATCHES of proofs of one (AIR, log_n, FRI parameters, hash) on
-// the device (AirVerifierDev).  The structure is verifier_dev.hip's and pcs_verifier_dev.hip's; the PCS half IS pcs_verifier_dev.hip:
+// the device (AirVerifierDev).  The structure is verifier_dev.hip's (a front over the header); the PCS half IS pcs_verifier_dev.hip:
 // the object owns a PcsVerifierDev of the shape a prove_air proof has and hands it each member's roots, points, opened values and
 // challenger state in device memory.
 //
@@ -20,7 +20,7 @@
 //                         next | chunks), the exported challenger state, the length of the FRI section (0 when the whole length is
 //                         wrong: the PCS verifier then rejects the member unread) — and alpha.  A header-rejected member gets
 //                         all-zero roots, points, opened values and state (zero counters are in range).
-//   av_eval_kernel        one LANE per member, 64-lane workgroups: the selectors at zeta, the program over bb::Ext operands with
+//   av_eval_kernel        one LANE per member, 64-lane workgroups: the selectors at zeta (ood.hip.h), the program over bb::Ext operands with
 //                         Horner's fold by alpha (air_eval_core, air.hip's air_kernel restated for extension operands: program,
 //                         constants and opcode / kind dispatch wave-uniform, the value slots in dynamic LDS, slot-major, (slot 4 +
 //                         coefficient) 64 + lane, 1 KiB per slot), the quotient recomposed from its chunks; folded != quotient(zeta)
@@ -39,6 +39,7 @@
 #include "challenger.h"
 #include "common.h"
 #include "mmcs.h"
+#include "ood.hip.h"
 #include "pcs_layout.h"
 #include "pcs_verifier_dev.h"
 #include "verifier_dev_common.hip.h"
@@ -55,70 +56,7 @@ using namespace vdev;
 constexpr uint32_t AV_BLOCK = 64;  // lanes per workgroup of the evaluator: a value slot costs 4 x 64 x 4 = 1 KiB of LDS
 static_assert(P3HIP_AIR_MAX_SLOTS * 4 * AV_BLOCK * 4 <= 64 * 1024, "the slots of the largest program fit a workgroup's 64 KiB");
 constexpr uint32_t OPND_INDEX_MASK = (1u << P3HIP_AIR_KIND_SHIFT) - 1u;
-constexpr uint32_t PROOF_MAGIC = 0x42463350u, CODE_OOD = 10;
-constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;  // where the Keccak half of an exported challenger begins
 constexpr size_t EVAL_MANY_MAX = (size_t)1 << 20;
-
-// ---- what depends only on (AIR, log_n): the trace domain's generator and the quotient chunks' cosets D_j = s_j <g_n>, s_j =
-// GENERATOR g_qn^j.  ONE routine for the host verifier and the device layout. ----
-struct AirDomain {
-    uint32_t g_n, g_n_inv;
-    uint32_t sn[AIR_MAX_CHUNKS];       // s_j^n
-    uint32_t sn_inv[AIR_MAX_CHUNKS];   // its inverse: Z_{D_j}(x) = x^n / s_j^n - 1
-    uint32_t izd[AIR_MAX_CHUNKS][AIR_MAX_CHUNKS];  // [c][j] = 1 / Z_{D_j}(s_c), j != c
-};
-
-void air_domain(uint32_t log_n, uint32_t lqd, AirDomain* d) {
-    memset(d, 0, sizeof(*d));
-    const uint32_t C = 1u << lqd;
-    const uint64_t n = 1ull << log_n;
-    d->g_n = bb::two_adic_generator(log_n);
-    d->g_n_inv = bb::inv(d->g_n);
-    const uint32_t g_qn = bb::two_adic_generator(log_n + lqd);
-    uint32_t s = bb::to_monty(bb::GEN);
-    for (uint32_t j = 0; j < C; j++) {
-        d->sn[j] = bb::pow(s, n);
-        d->sn_inv[j] = bb::inv(d->sn[j]);
-        s = bb::mul(s, g_qn);
-    }
-    for (uint32_t c = 0; c < C; c++)
-        for (uint32_t j = 0; j < C; j++)
-            if (j != c) d->izd[c][j] = bb::inv(bb::sub(bb::mul(d->sn[c], d->sn_inv[j]), bb::ONE));
-}
-
-// ---- the arithmetic of the out-of-domain check, one statement for the host and the device ----
-// selectors_at_point on the trace domain: Z_H = zeta^n - 1, first = Z_H / (zeta - 1), last = Z_H / (zeta - g_n^-1), trans = zeta -
-// g_n^-1; inv(0) = 0 as bb::inv has it
-BB_HD void av_selectors(const Ext& zeta, uint32_t log_n, uint32_t g_n_inv, Ext& first, Ext& last, Ext& trans, Ext& zn, Ext& zh) {
-    zn = zeta;
-    for (uint32_t k = 0; k < log_n; k++) zn = bb::sqr(zn);
-    zh = bb::sub(zn, bb::ext_one());
-    trans = bb::sub(zeta, bb::ext_from_base(g_n_inv));
-    first = bb::mul(zh, bb::inv(bb::sub(zeta, bb::ext_one())));
-    last = bb::mul(zh, bb::inv(trans));
-}
-// folded == quotient(zeta) Z_H(zeta), quotient(zeta) = sum_c zps_c sum_e X^e chunk_c[e], zps_c = prod_{j != c} Z_{D_j}(zeta) / Z_{D_j}(s_c);
-// chunks: 16 words per chunk
-BB_HD bool av_quotient_matches(const AirDomain& d, uint32_t n_chunks, const Ext& zn, const Ext& zh, const Ext& folded, const uint32_t* chunks) {
-    Ext quot = bb::ext_zero();
-    for (uint32_t c = 0; c < n_chunks; c++) {
-        Ext zps = bb::ext_one();
-        for (uint32_t j = 0; j < n_chunks; j++) {
-            if (j == c) continue;
-            const Ext num = bb::sub(bb::scale(zn, d.sn_inv[j]), bb::ext_one());
-            zps = bb::mul(zps, bb::scale(num, d.izd[c][j]));
-        }
-        Ext val = bb::ext_zero();
-        for (uint32_t e = 0; e < 4; e++) {
-            Ext be = bb::ext_zero();
-            be.c[e] = bb::ONE;
-            const uint32_t* p = chunks + 16 * c + 4 * e;
-            val = bb::add(val, bb::mul(be, Ext{{p[0], p[1], p[2], p[3]}}));
-        }
-        quot = bb::add(quot, bb::mul(zps, val));
-    }
-    return bb::eq(folded, bb::mul(quot, zh));
-}
 
 // ---- the interpreter over extension operands (VerifierConstraintFolder).  Operands are read where they lie: local and next as 4
 // words per column, publics and constants lifted from base words, the selectors from registers.  `Slots` holds the value slots: LDS
@@ -183,7 +121,7 @@ struct AvLayout {
     uint32_t head_words, proof_words, total;  // total: opened extension elements of a member, 2 width + 4 n_chunks
     uint32_t root_off, local_off, next_off, chunk0_off;  // the roots are adjacent; chunk c's values at chunk0_off + 17 c
     uint32_t n_shape;  // entries of the table of dictated words
-    AirDomain dom;
+    OodDomain dom;
 };
 
 struct AvArgs {
@@ -251,12 +189,7 @@ __global__ void __launch_bounds__(64) av_transcript_kernel(AvArgs a, AvLayout L)
     const Ext alpha = ch.sample_ext();
     ch.observe_n(w + L.root_off + 8, 8);
     const Ext zeta = ch.sample_ext();
-    {   // the other configuration's half of the state is zero, as challenger_export leaves it
-        const uint32_t lo = L.hash == HASH_POSEIDON2 ? SW_KC : 0u, hi = L.hash == HASH_POSEIDON2 ? CHALLENGER_STATE_WORDS : SW_KC;
-        for (uint32_t j = lo + lane; j < hi; j += 64) chal[j] = 0u;
-        ch.ds = reinterpret_cast<DevState*>(chal);
-        ch.end();
-    }
+    export_challenger(ch, L.hash, chal, lane);
     if (lane == 0) {
         stx(points, 0, zeta);
         stx(points, 4, bb::scale(zeta, L.dom.g_n));
@@ -283,9 +216,9 @@ __global__ void __launch_bounds__(AV_BLOCK) av_eval_kernel(AvArgs a, AvLayout L)
     x.pis = a.pis + (size_t)i * L.n_public;
     x.consts = a.consts;
     Ext zn, zh;
-    av_selectors(zeta, L.log_n, L.dom.g_n_inv, x.first, x.last, x.trans, zn, zh);
+    ood_selectors(zeta, L.log_n, L.dom.g_n_inv, x.first, x.last, x.trans, zn, zh);
     const Ext folded = air_eval_core(a.code, L.n_instr, x, LdsSlots{av_slots + threadIdx.x}, alpha);
-    a.ood[i] = av_quotient_matches(L.dom, L.n_chunks, zn, zh, folded, op + 8 * (size_t)L.width) ? 0u : 1u;
+    a.ood[i] = bb::eq(folded, bb::mul(ood_quotient(L.dom, L.n_chunks, zn, op + 8 * (size_t)L.width), zh)) ? 0u : 1u;
 }
 
 // the interpreter alone at n caller points (p3hip_air_eval_ext_dev)
@@ -445,18 +378,18 @@ int air_verify(const Air& a, int hash, uint32_t log_n, const FriParams& fp, cons
     const Ext alpha = ch.sample_ext();
     ch.observe_digest(roots + 8);
     const Ext zeta = ch.sample_ext();
-    AirDomain dom;
-    air_domain(log_n, lqd, &dom);
+    OodDomain dom;
+    ood_domain(log_n, lqd, &dom);
     ExtOperands x;
     x.local = opened.data();
     x.next = opened.data() + 4 * (size_t)w;
     x.pis = pis;
     x.consts = a.consts.data();
     Ext zn, zh;
-    av_selectors(zeta, log_n, dom.g_n_inv, x.first, x.last, x.trans, zn, zh);
+    ood_selectors(zeta, log_n, dom.g_n_inv, x.first, x.last, x.trans, zn, zh);
     std::vector<Ext> slots(a.n_slots, bb::ext_zero());
     const Ext folded = air_eval_core(a.code.data(), (uint32_t)(a.code.size() / 4), x, HostSlots{slots.data()}, alpha);
-    if (!av_quotient_matches(dom, C, zn, zh, folded, opened.data() + 8 * (size_t)w)) return reject(CODE_OOD, "OodEvaluationMismatch");
+    if (!bb::eq(folded, bb::mul(ood_quotient(dom, C, zn, opened.data() + 8 * (size_t)w), zh))) return reject(CODE_OOD, "OodEvaluationMismatch");
     AirPcsShape s(a, log_n);
     uint32_t points[4 * (2 + AIR_MAX_CHUNKS)];
     const Ext zeta_next = bb::scale(zeta, dom.g_n);
@@ -516,7 +449,7 @@ int AirVerifierDev::init(const Air& a, int hash, uint32_t log_n, const FriParams
     L.proof_words = (uint32_t)words;
     L.total = 2 * w + 4 * C;
     L.root_off = 3; L.local_off = 20; L.next_off = 21 + 4 * w; L.chunk0_off = 23 + 8 * w;
-    air_domain(log_n, a.log_quotient_degree, &L.dom);
+    ood_domain(log_n, a.log_quotient_degree, &L.dom);
     im->n_slots = a.n_slots;
     const std::vector<uint32_t> shape = dictated_words(a, log_n, pl);
     L.n_shape = (uint32_t)(shape.size() / 2);
@@ -543,9 +476,8 @@ int AirVerifierDev::init(const Air& a, int hash, uint32_t log_n, const FriParams
 int AirVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_pis, size_t n, uint32_t* d_status,
                                uint32_t* d_rejected, hipStream_t stream) {
     const AvLayout& L = im->L;
-    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
     if (int rc = im->check_batch("air_verifier_verify_dev", n, !d_proofs || !d_status || (!d_pis && L.n_public), stride, proof_len())) return rc;
-    if (misaligned(d_proofs) || misaligned(d_lens) || misaligned(d_pis) || misaligned(d_status) || misaligned(d_rejected))
+    if (misaligned(d_proofs, 4) || misaligned(d_lens, 4) || misaligned(d_pis, 4) || misaligned(d_status, 4) || misaligned(d_rejected, 4))
         return fail(ERR_BAD_ARG, "air_verifier_verify_dev: d_proofs, d_lens, d_pis, d_status and d_rejected must be 4-byte aligned");
     DeviceScope ds(im->device);
     if (int rc = ds.enter()) return rc;

@@ -1,6 +1,6 @@
 // The per-lane Merkle opening walk of every device verifier: one lane hashes a leaf row and compresses up a path to the root, for both
-// hash configurations.  mmcs_verify.hip (verify_lane_*_kernel), verifier_dev.hip (vd_open_kernel) and pcs_verifier_dev.hip
-// (pv_open_kernel) supply where the words come from and decide what a mismatch means; the absorb, the reduce after each permutation,
+// hash configurations.  mmcs_verify.hip (verify_lane_*_kernel) and pcs_verifier_dev.hip (pv_open_kernel, which the fib_air and the AIR
+// batch verifiers run through their owned PCS verifier) supply where the words come from and decide what a mismatch means; the absorb, the reduce after each permutation,
 // the last-block digest form, the left / right select and the canonicity fold into `hi` are here and nowhere else.
 //
 //   SRC   the word source.  len(l): the words of the row hashed at level l (level 0 = the leaf row); word(l, e): word e of that row,

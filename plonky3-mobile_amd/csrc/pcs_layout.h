@@ -24,6 +24,10 @@ struct PcsShape {
     size_t n_slots = 0;
     const uint32_t* slots = nullptr;  // null: the caller has points, not slots (the host verifier), and fills PLayout::pair_slot itself
     const unsigned* log_heights = nullptr;  // mixed heights: one log height per matrix, round -> matrix; log_h is then ignored
+    // wire format 1's dialect (verifier.hip Dialect::COUNTS): its host verifier FOLLOWS the queries' count words to the final polynomial,
+    // so a mismatch among them is met before the proof of work.  The device verifier follows nothing; the flag only says where in the
+    // order such a word reports (PLayout::counts)
+    bool counts = false;
 };
 
 constexpr uint32_t PV_MAX_IN = (uint32_t)PCS_MAX_ROUNDS, PV_MAX_ALLMATS = (uint32_t)(PCS_MAX_ROUNDS * PCS_MAX_MATS);
@@ -40,6 +44,7 @@ struct PLayout {
     // mixed heights.  mixed: the matrices are not all of one height (which kernels run); class_mask: bit log_big_c of every class with a
     // point; per round its tree's depth and a bit per log_big_m among its matrices
     uint32_t mixed, class_mask, log_big_r[PV_MAX_IN], round_mask[PV_MAX_IN];
+    uint32_t counts;  // PcsShape::counts
     // input rounds; offsets are relative to a query's first word
     uint32_t nm[PV_MAX_IN], mat0[PV_MAX_IN], open_off[PV_MAX_IN], depth_off[PV_MAX_IN], leaf_len[PV_MAX_IN];
     // matrices, round -> matrix: width word at val_off - 1, salt length word at salt_off - 1; leaf_start: where the matrix begins in its leaf

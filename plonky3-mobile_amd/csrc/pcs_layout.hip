@@ -67,6 +67,7 @@ int pcs_layout(int hash, bool hiding, const FriParams& fp, const PcsShape& sh, P
     L.pow_bits = fp.proof_of_work_bits;
     L.n_in = (uint32_t)n_rounds;
     L.n_slots = sh.slots ? (uint32_t)sh.n_slots : 0;
+    L.counts = sh.counts ? 1 : 0;
     const uint32_t D = 8;
     size_t mi = 0, pi = 0, total = 0;
     uint32_t cnt[bb::TWO_ADICITY + 1] = {0};  // alpha powers consumed so far, per class

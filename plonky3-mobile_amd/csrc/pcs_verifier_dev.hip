@@ -1,6 +1,7 @@
 // Batch verifier of PCS proofs on the device: TwoAdicFriPcs::verify / HidingFriPcs::verify + p3_fri::verifier over caller matrices for
 // MANY members of one shape at once.  verifier.hip's pcs_verify_any (host, one proof) is the specification: every phase below restates
-// it and FriCheck, and the reject codes are the host's.  The structure is verifier_dev.hip's (the fib_air batch verifier).
+// it and FriCheck, and the reject codes are the host's.  verifier_dev.hip (fib_air proofs) and air_verifier_dev.hip (a caller-defined AIR's)
+// each own one of these for the FRI section behind their header.
 //
 // A SHAPE fixes the layout of every proof: the FRI parameters, the committed log height, per round the matrices' widths, per matrix
 // its opening points as SLOTS (a member supplies n_slots points; pair (matrix, point) -> slot).  Every offset is then a function of
@@ -13,7 +14,9 @@
 // of that copy are compared with their ranges before anything uses them (a Keccak fill level indexes the sponge's block in LDS);
 // the query indices are sample_bits(log_big), in range by construction, and select bits and exponents, never addresses.
 //
-//   pv_transcript_kernel  one wavefront per member.  First the checks, before any arithmetic: length, the three header count words,
+//   pv_transcript_kernel  one wavefront per member.  A member its owner decided (d_owner_key at KEY_HEADER) is skipped unread; any other
+//                         starts from its owner's key.  First the checks, before any arithmetic: length, the three header count words
+//                         (KEY_SHAPE: compared, never followed, so the member is walked on and an owner's 10 still precedes them),
 //                         canonicity of the proof's field words outside the queries (those of the queries are scanned by
 //                         pv_open_kernel, AFTER pv_query_kernel's arithmetic has consumed them: harmless, they never reach an
 //                         address, and key 0 wins), of the opened values, the points and (Poseidon2)
@@ -56,9 +59,11 @@
 //                              round's tallest matrices in input order; a shorter class's row is hashed and compressed in (right
 //                              operand) at the level whose size equals its height, before that level's sibling.
 // A roll-in or an injection adds no check of its own: order keys and codes are where they were.
-// The first failure in the HOST's order decides the code: every check does atomicMin on a per-member word (order key << 8 | code).
-// Anything the host answers with 5..9 or 12, or refuses for a member's VALUES, is VERIFY_MALFORMED here (key 0 unless it is a shape
-// word inside a query, which keeps its place in the order so that an earlier query's 13 / 14 / 15 still wins).
+// The first failure in the HOST's order decides the code: every check does atomicMin on a per-member word (order key << 8 | code), on
+// the one scale of verifier_dev_common.hip.h.  Anything the host answers with 5..9 or 12, or refuses for a member's VALUES, is
+// VERIFY_MALFORMED here: key 0, or KEY_SHAPE for a count word outside the queries, or for a shape word inside a query its place in the
+// order, so that an earlier query's 13 / 14 / 15 still wins -- unless the shape has `counts` (PcsShape: wire format 1 of fib_air), which
+// sends the words that format's host follows to KEY_SHAPE.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -81,13 +86,7 @@ namespace {
 using namespace vdev;
 
 constexpr uint32_t PV_WAVE_MIN_COLS = 256;
-constexpr uint32_t CODE_INPUT_OPENING = 13;
-// order keys (smaller = earlier in the host verifier's order) behind KEY_HEADER
-constexpr uint64_t KEY_POW = 1, KEY_QUERY0 = 2;
 static_assert(PV_MAX_PAIRS <= 128, "the transcript kernel keeps two pair powers per lane");
-// where the Keccak half of an exported challenger begins (transcript.hip.h DevState)
-constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;
-static_assert(offsetof(DevState, pis) == (size_t)CHALLENGER_STATE_WORDS * 4 && CHALLENGER_STATE_WORDS % 2 == 0, "state words");
 
 struct PState {
     Ext beta[PV_MAX_FRI];
@@ -110,12 +109,13 @@ struct PArgs {
     uint32_t* pa;             // n x n_pairs x 4: alpha^off
     uint32_t* pb;             // n x n_pairs x 4: alpha^off Y
     unsigned long long* key;  // n
+    const unsigned long long* owner;  // n: the key an owner's own checks left each member at, or null
 };
 
 static_assert(sizeof(PLayout) + sizeof(PArgs) <= 4096, "both are passed by value: the kernel-argument segment holds 4 KB");
 
-// the transcript kernel rejected the member before it produced anything the later kernels read
-__device__ __forceinline__ bool header_rejected(const PArgs& a, uint32_t i) { return (a.key[i] >> 8) == KEY_HEADER; }
+// the owner or the transcript kernel decided the member (verifier_dev_common.hip.h) before it produced anything the later kernels read
+__device__ __forceinline__ bool header_rejected(const PArgs& a, uint32_t i) { return decided(a.key[i]); }
 __device__ __forceinline__ Ext wave_sum(Ext v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1)
@@ -129,7 +129,8 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
     P3_LATENCY_BOUND_KERNEL();
     __shared__ KState ks;
     const uint32_t i = blockIdx.x, lane = threadIdx.x;
-    if (!length_ok(a, L, i)) {  // rejected without being read
+    const uint64_t own = a.owner ? a.owner[i] : KEY_NONE;  // the member's key starts from its owner's
+    if (decided(own) || !length_ok(a, L, i)) {  // rejected without being read
         if (lane == 0) a.key[i] = make_key(KEY_HEADER, VERIFY_MALFORMED);
         return;
     }
@@ -141,10 +142,11 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
     const uint32_t nw = 4 * L.total;
     DevChal ch;  // a copy of fixed size and no arithmetic: the counters are not followed before the check below
     ch.begin(L.hash, reinterpret_cast<DevState*>(const_cast<uint32_t*>(cs)), &ks, false);
+    bool counts = false;  // a count word outside the queries: compared, never followed, so the transcript goes on
     {   // every check that needs no challenge, the lanes side by side
         bool bad = false;
         uint32_t hi = 0;
-        if (lane == 0) bad = w[0] != L.n_fri || w[L.nq_off] != L.nq || w[L.fpl_off] != L.fpl;
+        if (lane == 0) counts = w[0] != L.n_fri || w[L.nq_off] != L.nq || w[L.fpl_off] != L.fpl;
         if (L.hash == HASH_POSEIDON2) {
             for (uint32_t j = 1 + lane; j < 1 + 8 * L.n_fri; j += 64) hi = max(hi, w[j]);
             if (lane < 8 * L.n_in) hi = max(hi, roots[lane]);
@@ -169,7 +171,8 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
             return;
         }
     }
-    uint64_t key = KEY_NONE;
+    uint64_t key = own;
+    if (__builtin_amdgcn_ballot_w64(counts)) key = kmin(key, make_key(KEY_SHAPE, VERIFY_MALFORMED));
     for (uint32_t base = 0; base < nw; base += 64) {  // 64 words per load, observed one by one
         const uint32_t v = base + lane < nw ? op[base + lane] : 0u;
         const uint32_t cnt = min(64u, nw - base);
@@ -204,14 +207,8 @@ __global__ void __launch_bounds__(64) pv_transcript_kernel(PArgs a, PLayout L) {
         }
     }
     const FriTail tail{1, L.n_fri, L.fpoly_off, L.fpl, L.witness_off, L.pow_bits, L.nq, L.log_big};  // the roots follow the round count
-    if (!fri_transcript_tail(ch, w, lane, tail, a.st[i].beta, a.idx + (size_t)i * L.nq)) key = make_key(KEY_POW, CODE_POW);
-    if (a.chal_out) {  // the other configuration's half of the state is zero, as challenger_export leaves it
-        uint32_t* out = a.chal_out + (size_t)i * CHALLENGER_STATE_WORDS;
-        const uint32_t lo = L.hash == HASH_POSEIDON2 ? SW_KC : 0u, hi = L.hash == HASH_POSEIDON2 ? CHALLENGER_STATE_WORDS : SW_KC;
-        for (uint32_t j = lo + lane; j < hi; j += 64) out[j] = 0u;
-        ch.ds = reinterpret_cast<DevState*>(out);
-        ch.end();
-    }
+    if (!fri_transcript_tail(ch, w, lane, tail, a.st[i].beta, a.idx + (size_t)i * L.nq)) key = kmin(key, make_key(KEY_POW, CODE_POW));
+    if (a.chal_out) export_challenger(ch, L.hash, a.chal_out + (size_t)i * CHALLENGER_STATE_WORDS, lane);
     if (lane == 0) a.key[i] = key;
 }
 
@@ -349,20 +346,23 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
     const uint32_t* qw = w + L.q_base + (size_t)q * L.q_len;
     const uint32_t index = a.idx[pq];
     const uint64_t qkey = KEY_QUERY0 + (uint64_t)q * STEPS_PER_QUERY;
-    bool shape = false;  // a word of the query the shape dictates (the host's 12), met in query order
+    // a word of the query the shape dictates (the host's 12), met in query order; unless the shape has `counts`: then the words wire
+    // format 1's host FOLLOWS to the final polynomial (skip_queries_by_counts: the opening count, widths, depths, the round count;
+    // its 7 / 8, before the proof of work) report at KEY_SHAPE
+    bool shape = false, followed = false;
     LaneOpening o{};
     o.qw = qw;
     uint32_t hi = 0, code;
     if (slot < L.n_in) {
         const uint32_t m0 = L.mat0[slot], nm = L.nm[slot];
-        if (slot == 0 && qw[0] != L.n_in) shape = true;
+        if (slot == 0 && qw[0] != L.n_in) followed = true;
         if (qw[L.open_off[slot]] != nm) shape = true;
         for (uint32_t m = m0; m < m0 + nm; m++) {
-            if (qw[L.val_off[m] - 1] != L.width[m]) shape = true;
+            if (qw[L.val_off[m] - 1] != L.width[m]) followed = true;
             if (L.salt && qw[L.salt_off[m] - 1] != L.salt) shape = true;
         }
         o.depth = MIXED ? L.log_big_r[slot] : L.log_big;  // the round's own tree: the layout's word, compared with the proof's
-        if (qw[L.depth_off[slot]] != o.depth) shape = true;
+        if (qw[L.depth_off[slot]] != o.depth) followed = true;
         o.path = qw + L.depth_off[slot] + 1;
         o.m0 = m0; o.nm = nm;
         o.leaf_len = L.leaf_len[slot];
@@ -373,7 +373,7 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
     } else {
         const uint32_t r = slot - L.n_in;
         const uint32_t* p = qw + L.fri_off[r];
-        if (r == 0 && qw[L.nr_off] != L.n_fri) shape = true;
+        if (r == 0 && qw[L.nr_off] != L.n_fri) followed = true;
         for (int c = 0; c < 4; c++) hi = max(hi, p[c]);  // the sibling: a field element of the proof
         o.evs = a.evs + (pq * L.n_fri + r) * 8;
         o.n_ev = 8;
@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
         if (L.salt && p[4] != L.salt) shape = true;
         const uint32_t* dp = p + 4 + (L.salt ? 1 + L.salt : 0u);
         o.depth = L.log_big - 1 - r;
-        if (dp[0] != o.depth) shape = true;
+        if (dp[0] != o.depth) followed = true;
         o.path = dp + 1;
         o.leaf_len = 8 + L.salt;
         o.index = index >> (r + 1);
@@ -392,7 +392,8 @@ __global__ void __launch_bounds__(256) pv_open_kernel(PArgs a, PLayout L) {
     // walks into one kernel, which took the Poseidon2 form from 118 to 134 VGPRs when it was tried, below four waves per SIMD)
     OpeningWords<MIXED> src{L, o};
     const bool mismatch = lane_walk::walk<HASH, MIXED>(src, lane_walk::PathWords{o.path}, o.depth, o.index, o.root, hi);
-    if (shape) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
+    if (followed && L.counts) report(a, i, KEY_SHAPE, VERIFY_MALFORMED);
+    if (shape || (followed && !L.counts)) report(a, i, qkey + 2 * slot, VERIFY_MALFORMED);
     if (hi >= bb::P) report(a, i, KEY_HEADER, VERIFY_MALFORMED);
     if (mismatch) report(a, i, qkey + 2 * slot + 1, code);
 }
@@ -460,9 +461,8 @@ int PcsVerifierDev::init(int hash, bool hiding, const FriParams& fp, const PcsSh
 
 int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uint32_t* d_lens, const uint32_t* d_roots, const uint32_t* d_points,
                                const uint32_t* d_opened, const uint32_t* d_chal_in, size_t n, uint32_t* d_status, uint32_t* d_rejected,
-                               uint32_t* d_chal_out, hipStream_t stream) {
+                               uint32_t* d_chal_out, hipStream_t stream, const unsigned long long* d_owner_key) {
     const PLayout& L = im->L;
-    auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (int rc = im->check_batch("pcs_verifier_verify_dev", n, !d_proofs || !d_roots || !d_points || !d_opened || !d_chal_in || !d_status, stride, proof_len())) return rc;
     if (misaligned(d_proofs, 4) || misaligned(d_lens, 4) || misaligned(d_roots, 4) || misaligned(d_points, 4) || misaligned(d_opened, 4) ||
         misaligned(d_status, 4) || misaligned(d_rejected, 4))
@@ -472,7 +472,7 @@ int PcsVerifierDev::verify_dev(const uint8_t* d_proofs, size_t stride, const uin
     if (int rc = ds.enter()) return rc;
     if (d_rejected) P3_HIP(hipMemsetAsync(d_rejected, 0, 4, stream));
     if (!n) return OK;
-    PArgs a{d_proofs, stride, d_lens, d_roots, d_points, d_opened, d_chal_in, d_chal_out, (uint32_t)n, im->st, im->idx, im->evs, im->alp, im->pa, im->pb, im->key};
+    PArgs a{d_proofs, stride, d_lens, d_roots, d_points, d_opened, d_chal_in, d_chal_out, (uint32_t)n, im->st, im->idx, im->evs, im->alp, im->pa, im->pb, im->key, d_owner_key};
     hipLaunchKernelGGL(pv_transcript_kernel, dim3((uint32_t)n), dim3(64), 0, stream, a, L);
     const uint64_t pq = (uint64_t)n * L.nq;
     const dim3 qgrid((uint32_t)(wave_form() ? (pq + 3) / 4 : (pq + 255) / 256));

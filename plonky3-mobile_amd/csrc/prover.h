@@ -85,6 +85,9 @@ class FibHidingProver {
     int prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, const uint32_t* pis, std::vector<uint8_t>* proof);
 };
 
+// the first word of every proof's header (fib_air, plain and hiding, and a caller-defined AIR's): "P3FB", little endian
+constexpr uint32_t PROOF_MAGIC = 0x42463350u;
+
 // verifier.hip: p3_uni_stark::verify for FibonacciAir on the host (0 = accept, else the failed check's code)
 int verify_fib_air(const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
                    const FriParams& fp, std::string* why, int hash = 0);

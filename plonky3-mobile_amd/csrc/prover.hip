@@ -1251,7 +1251,7 @@ int FibProver::run(uint64_t a, uint64_t b, int slot, int phase, std::vector<uint
     std::vector<uint8_t>& pf = *proof;
     pf.clear();
     pf.reserve(64 + (size_t)nq * s.slot_words * 4 + 4096);
-    put_u32(pf, 0x42463350u); put_u32(pf, 1); put_u32(pf, log_n);
+    put_u32(pf, PROOF_MAGIC); put_u32(pf, 1); put_u32(pf, log_n);
     put_words(pf, hp + L.root_t, 8); put_words(pf, hp + L.root_q, 8);
     const uint32_t* op = hp + L.opened;
     put_u32(pf, 2); put_words(pf, op, 8);

@@ -756,7 +756,7 @@ int FibHidingProver::prove_any(uint64_t a, uint64_t b, const uint32_t* d_trace, 
     std::vector<uint8_t>& pf = *proof;
     pf.clear();
     pf.reserve(64 + (size_t)nq * (s.slot_words + 64) * 4 + 4096);
-    put_u32(pf, 0x42463350u); put_u32(pf, 2); put_u32(pf, log_n);
+    put_u32(pf, PROOF_MAGIC); put_u32(pf, 2); put_u32(pf, log_n);
     put_words(pf, hp + L.root_t, 8); put_words(pf, hp + L.root_q, 8); put_words(pf, hp + s.root_r_off, 8);
     const uint32_t* op = hp + L.opened;
     put_u32(pf, HRW); put_words(pf, op, 4 * HRW); op += 4 * HRW;

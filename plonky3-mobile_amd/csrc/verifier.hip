@@ -12,7 +12,9 @@
 #include "bb31.hip.h"
 #include "challenger.h"
 #include "common.h"
+#include "fib_format.h"
 #include "mmcs.h"
+#include "ood.hip.h"
 #include "pcs_layout.h"
 #include "poseidon2.hip.h"
 #include "prover.h"
@@ -158,18 +160,8 @@ struct FriCheck {
     }
 };
 
-// What the three callers of pcs_walk answer differently for the same bytes.  Nobody chose these differences; the recordings under
-// tests/golden pin them (fib_verify_codes.json, verifier_noncanonical_codes.json, pcs_verify_codes.json), so they are kept, in one place.
-struct Dialect {
-    const char* round_name[PCS_MAX_ROUNDS];  // the message that names an input round, in proof order
-    uint32_t named;                          // bit c: code c (of 9, 12, 13 at an input opening) carries round_name, not the general message
-    bool stop_on_flag;  // a reader flagged (truncated, or a word >= P) right after an input opening rejects with 9 before the path is hashed
-    enum { LAYOUT_CHECKED, LAYOUT, COUNTS } final_at;  // the final polynomial lies where the layout says, a shorter proof being a 9
-                                                       // (CHECKED) or final_poly's own 7; or where skip_queries_by_counts ends
-};
+// (Dialect: fib_format.h) what pcs_verify_any's members answer
 constexpr Dialect DIALECT_PCS{{}, 0, true, Dialect::LAYOUT_CHECKED};
-constexpr Dialect DIALECT_FIB1{{"trace opening", "quotient opening"}, 1u << 13, false, Dialect::COUNTS};
-constexpr Dialect DIALECT_FIB2{{"randomization opening", "trace opening", "quotient opening"}, 1u << 9 | 1u << 12 | 1u << 13, true, Dialect::LAYOUT};
 
 // Wire format 1 finds its final polynomial by FOLLOWING the queries' count words (widths, path lengths, round counts), as its first
 // verifier did, not from the shape: a tampered count moves the final polynomial and the proof is a 7 (or 8) there, before the query walk
@@ -281,68 +273,9 @@ int verify_check_parameters(int hash, bool hiding, uint32_t log_n, const FriPara
 // ---- the fib_air verifiers: p3_uni_stark::verify for FibonacciAir over TwoAdicFriPcs (wire format 1, prover.hip) and, with SC::Pcs::ZK,
 // over HidingFriPcs + MerkleTreeHidingMmcs as the reference configures them (wire format 2, prover_hiding.hip.inc;
 // native/src/fib_air.rs:40-72; [UPSTREAM-RECALL] in structure, parity unpinned).  A fib_air proof is a PCS proof of a fixed shape behind a
-// header: magic, version, log_n, the roots, the opened values.  What the two formats do not share is this table; verify_fib does the rest.
+// header: magic, version, log_n, the roots, the opened values.  What the two formats do not share is a table (fib_format.h); verify_fib does
+// the rest.
 namespace {
-constexpr uint32_t FIB_MAX_ROUNDS = 3, FIB_MAX_MATS = 6, FIB_MAX_OPENED = 36, FIB_MAX_CHUNKS = 4;
-struct FibFormat {
-    uint32_t version;
-    bool hiding;        // the salted MMCS, the trace committed at twice its height: the transcript opens with log_n + 1, then log_n
-    uint32_t n_rounds;  // the header's roots: trace, quotient[, randomization], observed in that order: the first, the public values,
-                        // alpha, then the others, zeta
-    // the commitment rounds in PROOF order as a PcsShape: each round's root among the header's, its matrices, their widths, each
-    // matrix's points and each (matrix, point) pair's slot (0: zeta, 1: zeta g)
-    uint32_t root_of[FIB_MAX_ROUNDS];
-    size_t mats[FIB_MAX_ROUNDS], widths[FIB_MAX_MATS], points[FIB_MAX_MATS];
-    uint32_t slots[FIB_MAX_MATS + 1];
-    // the header's opened values, in the proof's (and the transcript's) order: n > 0 is the count word n and n extension elements behind
-    // it, n < 0 the bare count word -n; 0 ends
-    int grammar[9];
-    uint32_t t_loc, t_nxt, chunks, log_chunks;  // among the opened values: the trace at zeta and at zeta g, the 2^log_chunks quotient chunks
-    Dialect dialect;
-};
-// format 1: trace (2 columns) at zeta and zeta g, the quotient (one chunk, 4 columns: an extension element's coordinates) at zeta
-constexpr FibFormat FIB_PLAIN{1, false, 2, {0, 1}, {1, 1}, {2, 4}, {2, 1}, {0, 1, 0}, {2, 2, -1, 4}, 0, 2, 4, 0, DIALECT_FIB1};
-// format 2, 4 random codewords: the randomization round (4 + 4 columns) first, the trace with its 4 random columns, 4 blinded chunks
-constexpr FibFormat FIB_HIDING{2, true, 3, {2, 0, 1}, {1, 1, 4}, {8, 6, 4, 4, 4, 4}, {1, 2, 1, 1, 1, 1}, {0, 0, 1, 0, 0, 0, 0},
-                               {8, 6, 6, -4, 4, 4, 4, 4}, 8, 14, 20, 2, DIALECT_FIB2};
-constexpr uint32_t opened_of(const FibFormat& f) { uint32_t n = 0; for (int g : f.grammar) if (g > 0) n += (uint32_t)g; return n; }
-static_assert(opened_of(FIB_PLAIN) == 8 && opened_of(FIB_HIDING) == FIB_MAX_OPENED && (1u << FIB_HIDING.log_chunks) <= FIB_MAX_CHUNKS &&
-              FIB_MAX_ROUNDS <= PCS_MAX_ROUNDS, "what a grammar reads fits verify_fib's arrays");
-
-// The FibonacciAir constraints at zeta (fib_air.rs:232-264), folded with alpha, against the quotient recomposed from its chunks:
-// sum_c zps_c(zeta) chunk_c(zeta) (the blinding of format 2 cancels in the sum).  Chunk cosets D_c = s_c <g_n> with s_c^n = GENERATOR^n w^c,
-// w of order n_chunks; zps_c(zeta) = prod_{j != c} (zeta^n - s_j^n) / (s_c^n - s_j^n): with one chunk the product is empty.
-bool fib_constraints_hold(const Ext* t_loc, const Ext* t_nxt, const Ext* chunks, uint32_t log_chunks, const uint32_t pis[3], Ext alpha, Ext zeta,
-                          uint32_t log_n) {
-    const uint64_t n = 1ull << log_n;
-    const uint32_t n_chunks = 1u << log_chunks;
-    const Ext zn = bb::pow(zeta, n), zh = bb::sub(zn, bb::ext_one());
-    const Ext ginv = bb::ext_from_base(bb::inv(bb::two_adic_generator(log_n)));
-    const Ext first = bb::mul(zh, bb::inv(bb::sub(zeta, bb::ext_one())));
-    const Ext last = bb::mul(zh, bb::inv(bb::sub(zeta, ginv)));
-    const Ext trans = bb::sub(zeta, ginv);
-    const Ext c[5] = {bb::mul(first, bb::sub(t_loc[0], bb::ext_from_base(pis[0]))), bb::mul(first, bb::sub(t_loc[1], bb::ext_from_base(pis[1]))),
-                      bb::mul(trans, bb::sub(t_loc[1], t_nxt[0])), bb::mul(trans, bb::sub(bb::add(t_loc[0], t_loc[1]), t_nxt[1])),
-                      bb::mul(last, bb::sub(t_loc[1], bb::ext_from_base(pis[2])))};
-    Ext folded = bb::ext_zero();
-    for (auto& ck : c) folded = bb::add(bb::mul(folded, alpha), ck);
-    uint32_t sn[FIB_MAX_CHUNKS];
-    { uint32_t gn = bb::pow(bb::to_monty(bb::GEN), n), w = bb::two_adic_generator(log_chunks), p = bb::ONE;
-      for (uint32_t k = 0; k < n_chunks; k++) { sn[k] = bb::mul(gn, p); p = bb::mul(p, w); } }
-    Ext quot = bb::ext_zero();
-    for (uint32_t ci = 0; ci < n_chunks; ci++) {
-        uint32_t kc = bb::ONE;
-        Ext zp = bb::ext_one();
-        for (uint32_t j = 0; j < n_chunks; j++)
-            if (j != ci) { kc = bb::mul(kc, bb::sub(sn[ci], sn[j])); zp = bb::mul(zp, bb::sub(zn, bb::ext_from_base(sn[j]))); }
-        zp = bb::scale(zp, bb::inv(kc));
-        Ext v = bb::ext_zero();  // the chunk's 4 columns are an extension element's coordinates
-        for (int e = 0; e < 4; e++) { Ext be = bb::ext_zero(); be.c[e] = bb::ONE; v = bb::add(v, bb::mul(be, chunks[ci * 4 + e])); }
-        quot = bb::add(quot, bb::mul(zp, v));
-    }
-    return bb::eq(bb::mul(folded, bb::inv(zh)), quot);
-}
-
 // 0 = accept; otherwise a positive code naming the failed check (1-4 the header, 10 the constraints, the others pcs_walk's and FriCheck's).
 int verify_fib(const FibFormat& f, const uint8_t* proof, size_t len, uint64_t a_pub, uint64_t b_pub, uint64_t x_pub, uint32_t log_n,
                const FriParams& fp, std::string* why, int hash) {
@@ -350,9 +283,9 @@ int verify_fib(const FibFormat& f, const uint8_t* proof, size_t len, uint64_t a_
     // pcs_layout's gates are verify_check_parameters' over again and refuse nothing it admits (before the first byte is read, so that
     // any bytes show it: test_no_pcs_refusal_leaks_out_of_a_fib_verifier)
     PLayout L;
-    if (int rc = pcs_layout(hash, f.hiding, fp, PcsShape{log_n, f.n_rounds, f.mats, f.widths, f.points, 2, f.slots, nullptr}, &L, nullptr, why)) return rc;
+    if (int rc = pcs_layout(hash, f.hiding, fp, fib_pcs_shape(f, log_n), &L, nullptr, why)) return rc;
     Reader rd{proof, len};
-    if (rd.u32() != 0x42463350u || rd.u32() != f.version) return reject(why, 1, "bad header");
+    if (rd.u32() != PROOF_MAGIC || rd.u32() != f.version) return reject(why, 1, "bad header");
     if (rd.u32() != log_n) return reject(why, 2, "degree_bits mismatch");
     uint32_t hdr_roots[FIB_MAX_ROUNDS][8], roots[FIB_MAX_ROUNDS * 8];
     for (uint32_t r = 0; r < f.n_rounds; r++) rd.digests(hash, hdr_roots[r], 1);
@@ -370,8 +303,15 @@ int verify_fib(const FibFormat& f, const uint8_t* proof, size_t len, uint64_t a_
     const Ext alpha = ch.sample_ext();
     for (uint32_t r = 1; r < f.n_rounds; r++) ch.observe_digest(hdr_roots[r]);
     const Ext zeta = ch.sample_ext();
-    if (!fib_constraints_hold(opened + f.t_loc, opened + f.t_nxt, opened + f.chunks, f.log_chunks, pis, alpha, zeta, log_n))
-        return reject(why, 10, "OodEvaluationMismatch");
+    {   // the FibonacciAir constraints at zeta, folded with alpha, against the quotient recomposed from its chunks (ood.hip.h)
+        OodDomain dom;
+        ood_domain(log_n, f.log_chunks, &dom);
+        Ext first, last, trans, zn, zh;
+        ood_selectors(zeta, log_n, dom.g_n_inv, first, last, trans, zn, zh);
+        const Ext folded = fib_constraints_folded(opened[f.t_loc].c, opened[f.t_nxt].c, pis, first, last, trans, alpha);
+        if (!bb::eq(bb::mul(folded, bb::inv(zh)), ood_quotient(dom, 1u << f.log_chunks, zn, opened[f.chunks].c)))
+            return reject(why, CODE_OOD, "OodEvaluationMismatch");
+    }
     // The PCS half, entered below pcs_verify_any's gates on the points: zeta comes from the proof's own bytes, and where it lies is no
     // argument of this call.
     const Ext zs[2] = {zeta, bb::scale(zeta, bb::two_adic_generator(log_n))};

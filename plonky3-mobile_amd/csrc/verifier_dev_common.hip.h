@@ -1,10 +1,15 @@
-// What the two device batch verifiers (verifier_dev.hip: fib_air proofs; pcs_verifier_dev.hip: PCS proofs) share besides the opening
-// walk (lane_walk.hip.h): the order key every check reports through, the readers of proof words, FriCheck's fold step and final
-// polynomial, and the FRI tail of the transcript.  Each verifier keeps its own args and layout structs (VArgs / VLayout, PArgs /
-// PLayout): the helpers that read them are templates over the fields they name (key, lens, proofs, stride; proof_words).
+// What the device batch verifiers share besides the opening walk (lane_walk.hip.h): pcs_verifier_dev.hip (PCS proofs) and its two owners,
+// verifier_dev.hip (fib_air proofs) and air_verifier_dev.hip (a caller-defined AIR's), each a front kernel over the header that hands
+// the FRI section to an owned PcsVerifierDev.  Here: the ONE scale of order keys every check reports through and the reject codes, the
+// readers of proof words, the export of a challenger, FriCheck's fold step and final polynomial, and the FRI tail of the transcript.
+// Each verifier keeps its own args and layout structs: the helpers that read them are templates over the fields they name (key, lens,
+// proofs, stride; proof_words).
 #pragma once
+#include <cstddef>
+
 #include "bb31.hip.h"
 #include "lane_walk.hip.h"
+#include "prover.h"
 #include "transcript.hip.h"
 
 namespace p3 {
@@ -13,11 +18,24 @@ namespace vdev {
 using bb::Ext;
 
 // The first failure in the HOST's order decides the code: every check does atomicMin on a per-proof word (order key << 8 | code).
-constexpr uint64_t KEY_HEADER = 0, KEY_NONE = ~0ull;
+// The scale, smaller = earlier:
+//   KEY_HEADER  a wrong length, a dictated word of an owner's header, ANY word that is no canonical field element (wherever it lies:
+//               the host's readers flag it where they meet it, the device answers MALFORMED whatever else is wrong), a member's values
+//   KEY_OWNER   the check an owner makes between its header and the FRI section: the constraints at zeta (CODE_OOD, ood.hip.h)
+//   KEY_SHAPE   the count words of the FRI section outside the queries (rounds, queries, final polynomial length) and, for a shape
+//               with PLayout::counts, the count words inside the queries that wire format 1's host follows to the final polynomial
+//   KEY_POW     the proof of work
+//   KEY_QUERY0  the queries, STEPS_PER_QUERY keys each: opening s of query q reports its count words at 2 s and its path at 2 s + 1
+// A member whose key is at KEY_HEADER is DECIDED: every key-0 report is MALFORMED and nothing precedes it, so the later kernels skip it
+// (an owner hands such a member on unread).  A member at any later key is walked to the end, whatever it holds so far: a word that is
+// no field element, found by the opening kernel, still precedes an owner's 10, a count word's 16 and the proof of work's 11.
+constexpr uint64_t KEY_HEADER = 0, KEY_OWNER = 1, KEY_SHAPE = 2, KEY_POW = 3, KEY_QUERY0 = 4, KEY_NONE = ~0ull;
 constexpr uint32_t STEPS_PER_QUERY = 64;  // 2 (openings + FRI rounds) + 1 <= 2 (4 + 27) + 1
-constexpr uint32_t CODE_POW = 11, CODE_FRI_OPENING = 14, CODE_FINAL_POLY = 15;
+constexpr uint32_t CODE_POW = 11, CODE_INPUT_OPENING = 13, CODE_FRI_OPENING = 14, CODE_FINAL_POLY = 15;
 
 __device__ __forceinline__ uint64_t make_key(uint64_t order, uint32_t code) { return (order << 8) | code; }
+__device__ __forceinline__ uint64_t kmin(uint64_t a, uint64_t b) { return a < b ? a : b; }
+__device__ __forceinline__ bool decided(uint64_t key) { return (key >> 8) == KEY_HEADER; }
 template <typename A>
 __device__ __forceinline__ void report(const A& a, uint32_t i, uint64_t order, uint32_t code) {
     atomicMin(a.key + i, (unsigned long long)make_key(order, code));
@@ -33,13 +51,24 @@ __device__ __forceinline__ Ext ldx(const uint32_t* w, size_t off) { return Ext{{
 __device__ __forceinline__ void stx(uint32_t* w, size_t off, const Ext& e) { for (int c = 0; c < 4; c++) w[off + c] = e.c[c]; }
 __device__ __forceinline__ uint32_t rev_bits_dev(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32u - bits) : 0u; }
 
-// order key -> status, count of rejected proofs: the body of vd_finish_kernel / pv_finish_kernel
+// order key -> status, count of rejected proofs: the body of pv_finish_kernel
 __device__ __forceinline__ void finish(const unsigned long long* key, uint32_t n, uint32_t* status, uint32_t* d_rejected) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = i < n;
     const uint32_t st = act && key[i] != KEY_NONE ? (uint32_t)(key[i] & 0xffu) : 0u;
     if (act) status[i] = st;
     count_rejected(st != 0u, d_rejected);
+}
+
+// A challenger's state written where the next verifier imports it (one wavefront; the state ends there).  The other configuration's
+// half is zero, as challenger_export leaves it.
+constexpr uint32_t SW_KC = offsetof(DevState, kc) / 4;  // where the Keccak half begins (transcript.hip.h DevState)
+static_assert(offsetof(DevState, pis) == (size_t)CHALLENGER_STATE_WORDS * 4 && CHALLENGER_STATE_WORDS % 2 == 0, "state words");
+__device__ __forceinline__ void export_challenger(DevChal& ch, int hash, uint32_t* out, uint32_t lane) {
+    const uint32_t lo = hash == HASH_POSEIDON2 ? SW_KC : 0u, hi = hash == HASH_POSEIDON2 ? CHALLENGER_STATE_WORDS : SW_KC;
+    for (uint32_t j = lo + lane; j < hi; j += 64) out[j] = 0u;
+    ch.ds = reinterpret_cast<DevState*>(out);
+    ch.end();
 }
 
 // One step of FriCheck::query's walk, from 2^(lfh + 1) to 2^lfh elements: the pair (ev0, ev1) this query's leaf of the round must

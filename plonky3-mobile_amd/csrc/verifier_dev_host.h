@@ -1,8 +1,10 @@
-// Host side of the two device batch verifiers (verifier_dev.hip: fib_air proofs; pcs_verifier_dev.hip: PCS proofs), what their Impls share:
-// the object's device and its buffers, freed together; the host entry's staging (a non-blocking stream, d_proofs, d_lens, d_status and
-// the verifier's own extras), made by the first call that needs it; a chunk's upload, with the rule that a proof of the wrong length
-// is rejected unread; the status download; the argument checks of verify_dev.  Device code is in verifier_dev_common.hip.h.
+// Host side of the device batch verifiers (pcs_verifier_dev.hip: PCS proofs; verifier_dev.hip: fib_air proofs; air_verifier_dev.hip: a
+// caller-defined AIR's), what their Impls share: the object's device and its buffers, freed together; the host entry's staging (a
+// non-blocking stream, d_proofs, d_lens, d_status and the verifier's own extras), made by the first call that needs it; a chunk's upload,
+// with the rule that a proof of the wrong length is rejected unread; the status download; the argument checks of verify_dev and the
+// alignment test they use.  Device code is in verifier_dev_common.hip.h.
 #pragma once
+#include <cstdint>
 #include <initializer_list>
 #include <vector>
 
@@ -10,6 +12,8 @@
 #include "verifier_dev.h"
 
 namespace p3 {
+
+inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 struct VerifierDevHost {
     int device = -1;  // none until init has a context

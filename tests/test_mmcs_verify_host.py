@@ -282,16 +282,16 @@ def test_cpp_mirror_verify_batch_runs(p3, oracle, tmp_path):
 
 def test_verify_kernels_use_no_scratch():
     """The device forms keep every state in registers: compiled with the resource report, each kernel of mmcs_verify.hip, the
-    bulk gather of mmcs.hip and every instantiation of the batch verifiers' opening kernels (the same per-lane walk, lane_walk.hip.h)
+    bulk gather of mmcs.hip and every instantiation of the batch verifiers' opening kernel (the same per-lane walk, lane_walk.hip.h)
     show 0 bytes of scratch per lane."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     csrc = os.path.join(ROOT, "plonky3-mobile_amd", "csrc")
-    instances = {"vd_open_kernel": 2, "pv_open_kernel": 4}  # per hash; per hash and (one height / mixed heights)
+    instances = {"pv_open_kernel": 4}  # per hash and (one height / mixed heights)
     for src, kernels in (("mmcs_verify.hip", ("verify_lane_p2_kernel", "verify_lane_keccak_kernel", "verify_coop_p2_kernel", "verify_coop_keccak_kernel")),
                          ("mmcs.hip", ("open_gather_many_kernel",)),
-                         ("verifier_dev.hip", ("vd_open_kernel",)), ("pcs_verifier_dev.hip", ("pv_open_kernel",))):
+                         ("pcs_verifier_dev.hip", ("pv_open_kernel",))):
         r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c",
                             os.path.join(csrc, src), "-o", os.devnull], capture_output=True, text=True, cwd=csrc)
         assert r.returncode == 0, r.stderr[-2000:]

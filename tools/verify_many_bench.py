@@ -4,7 +4,7 @@ proof-of-work bits) and at the reference's configuration at that size (Keccak + 
   host    p3hip_verify_fib_air_hash / _hiding, proofs/s on one thread and on 16 threads (the calls release the interpreter lock);
   device  FibAirVerifier at n = 1, 8, 64, 512: HIP events around the launches of the device entry (proofs resident), and end to end
           through the host entry, the upload included;
-  split   the device entry's kernels at n = 64 under rocprofv3 --kernel-trace --stats (a child process), when rocprofv3 is on the PATH.
+  split   the device entry's kernels (the front kernel and the owned PCS verifier's) at n = 64 under rocprofv3 --kernel-trace --stats (a child process), when rocprofv3 is on the PATH.
 Writes profiles/verify_many_bench.txt.      python3 tools/verify_many_bench.py [--out FILE] [--quick]"""
 import argparse
 import ctypes as C
@@ -25,6 +25,7 @@ from __graft_entry__ import load_package  # noqa: E402
 P = 0x78000001
 CONFIGS = {"cfg2": ("poseidon2", False), "cfg2_keccak_hiding": ("keccak", True)}
 LOG_N, FRI = 20, (1, 0, 100, 16)
+KERNELS = ("fv_", "pv_")  # the device entry's kernels: the fib front kernel and the owned PCS verifier's four
 DISTINCT = 8  # distinct proofs; larger batches repeat them (the verifier's work does not depend on which proof it is)
 
 
@@ -137,7 +138,7 @@ def kernel_split(name, n):
         files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
         if r.returncode != 0 or not files:
             return ["  (the traced child failed: rc %d)" % r.returncode]
-        rows = [row for row in csv.DictReader(open(files[0])) if "vd_" in row["Name"]]
+        rows = [row for row in csv.DictReader(open(files[0])) if any(k in row["Name"] for k in KERNELS)]
     out = []
     for row in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
         kname = row["Name"].replace("void ", "").replace("p3::(anonymous namespace)::", "").split("(")[0]
