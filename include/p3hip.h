@@ -136,6 +136,28 @@ int p3hip_coset_lde_from_coeffs_bb31_dev(const uint32_t *d_coeffs, uint32_t *d_o
  * *n_passes = kernel launches, stages_per_pass[i] = radix-2 stages pass i performs (their sum is log2 height; at most `cap` entries
  * are written).  Host-only: no GPU is touched. */
 int p3hip_dft_plan_bb31(size_t height, size_t width, uint32_t *stages_per_pass, size_t cap, size_t *n_passes);
+/* The LAUNCH LIST of p3hip_mmcs_commit* for a commitment under a hash (P3HIP_HASH_*) and a profile (P3HIP_PROFILE_*): steps[0] is
+ * the kernel that hashes the tallest matrices into the leaf layer (layer = levels = 0), every further step one launch that reads
+ * digest layer `layer` (0 = leaves) and writes the `levels` layers above it; makes_root: the last of them is the root.  The choice
+ * depends on addresses only through their alignment: mats (or an entry of it) and layers are never dereferenced, NULL = aligned;
+ * strides (words between two rows) NULL = dense.  At most `cap` steps are written, *n_steps is their number (<=
+ * P3HIP_MMCS_MAX_STEPS).  A shape the commit refuses is refused here with the same message.  Host-only: no GPU is touched. */
+enum p3hip_mmcs_kernel {
+    P3HIP_MK_LEAF_COOP, P3HIP_MK_LEAF_HASH_Q4, P3HIP_MK_LEAF_HASH_F64_WIDE, P3HIP_MK_LEAF_HASH_F64, P3HIP_MK_LEAF_HASH_F64_ROWSET,
+    P3HIP_MK_LEAF_HASH, P3HIP_MK_TREE_LEVELS_COOP, P3HIP_MK_COMPRESS_LAYER_Q4, P3HIP_MK_COMPRESS_LAYER_F64, P3HIP_MK_COMPRESS_LAYER,
+    P3HIP_MK_KECCAK_LEAF_WIDE, P3HIP_MK_KECCAK_LEAF_SALTED_4_1, P3HIP_MK_KECCAK_LEAF_SALTED_6_1, P3HIP_MK_KECCAK_LEAF_SALTED_8_1,
+    P3HIP_MK_KECCAK_LEAF_SALTED_4_4, P3HIP_MK_KECCAK_LEAF, P3HIP_MK_KECCAK_TREE_LEVELS_COOP, P3HIP_MK_KECCAK_TREE_LEVELS,
+    P3HIP_MK_KECCAK_COMPRESS, P3HIP_MK_COUNT
+};
+typedef struct p3hip_mmcs_step {
+    int kernel; /* enum p3hip_mmcs_kernel */
+    uint32_t layer, levels, makes_root;
+} p3hip_mmcs_step;
+#define P3HIP_MMCS_MAX_STEPS 64 /* the leaf step and one per layer above the leaves, whatever power of two a size_t height is */
+int p3hip_mmcs_commit_plan(int hash, int profile, const uint32_t *const *mats, const size_t *heights, const size_t *widths,
+                           const size_t *strides, size_t n_mats, const uint32_t *layers, p3hip_mmcs_step *steps, size_t cap,
+                           size_t *n_steps);
+const char *p3hip_mmcs_kernel_name(int kernel); /* "leaf_coop" .. "keccak_leaf_salted<4,4>" .. "keccak_compress"; NULL if unknown */
 /* write_bit_reversed_rows_u32 (backend_vulkan.rs:1005-1026) on device; out of place only (any overlap of the ranges is refused) */
 int p3hip_bit_reverse_rows_dev(const uint32_t *d_in, uint32_t *d_out, size_t height, size_t width, void *stream);
 

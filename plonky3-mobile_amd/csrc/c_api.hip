@@ -279,6 +279,26 @@ int p3hip_dft_plan_bb31(size_t height, size_t width, uint32_t* stages_per_pass, 
     });
 }
 
+int p3hip_mmcs_commit_plan(int hash, int profile, const uint32_t* const* mats, const size_t* heights, const size_t* widths, const size_t* strides,
+                           size_t n_mats, const uint32_t* layers, p3hip_mmcs_step* steps, size_t cap, size_t* n_steps) {
+    return guarded([&]() -> int {
+        if (!n_steps || (cap && !steps)) return fail(ERR_BAD_ARG, "mmcs_commit_plan: null argument");
+        *n_steps = 0;
+        if (hash != HASH_POSEIDON2 && hash != HASH_KECCAK) return fail(ERR_BAD_ARG, "mmcs_commit: unknown hash configuration");
+        if (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY) return fail(ERR_BAD_ARG, "mmcs_commit_plan: unknown profile");
+        if (int rc = mmcs_check_shape(heights, widths, n_mats)) return rc;
+        for (size_t i = 0; strides && i < n_mats; i++)
+            if (strides[i] < widths[i] || strides[i] > 0xffffffffull) return fail(ERR_BAD_ARG, "mmcs_commit: row stride below the width");
+        MmcsPlan plan;
+        if (int rc = mmcs_plan(hash, profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY, mats, heights, widths, strides,
+                               n_mats, layers, &plan)) return rc;
+        *n_steps = plan.n;
+        for (size_t i = 0; i < plan.n && i < cap; i++) steps[i] = plan.step[i];
+        return OK;
+    });
+}
+const char* p3hip_mmcs_kernel_name(int kernel) { return mmcs_kernel_name(kernel); }
+
 int p3hip_bit_reverse_rows_dev(const uint32_t* in, uint32_t* out, size_t h, size_t w, void* stream) {
     return guarded([&]() -> int {
         if (h == 0 || w == 0) return OK;

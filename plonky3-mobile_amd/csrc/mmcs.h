@@ -2,6 +2,7 @@
 #pragma once
 #include <memory>
 #include <cstring>
+#include "../../include/p3hip.h"  // p3hip_mmcs_kernel, p3hip_mmcs_step: the plan is exported as it is
 #include "common.h"
 
 namespace p3 {
@@ -33,6 +34,18 @@ int mmcs_commit(hipStream_t stream, const uint32_t* const* d_mats, const size_t*
 // The shape checks of mmcs_commit alone (host only: nothing is launched, allocated or drawn): power-of-two heights, at most 64 matrices,
 // at most 16 of one height.  The hiding commit asks before it draws a salt, so that a refused shape leaves its rng where it was.
 int mmcs_check_shape(const size_t* heights, const size_t* widths, size_t n_mats);
+// The launch list of mmcs_commit for one commitment: step[0] hashes the tallest class into layer 0 (levels = 0), every further step
+// is one launch that reads digest layer `layer` and writes the `levels` layers above it.  ALL of the launch policy is here (which
+// kernel by hash, profile, class shape, layer length, row stride and address alignment); mmcs_commit only executes the list.
+// Pure host code, no allocation: d_mats (or any entry of it), strides and layers may be null (= dense, aligned) and are never
+// dereferenced.  The caller has run mmcs_check_shape.
+struct MmcsPlan {
+    p3hip_mmcs_step step[P3HIP_MMCS_MAX_STEPS];
+    uint32_t n = 0;
+};
+int mmcs_plan(int kind, int profile, const uint32_t* const* d_mats, const size_t* heights, const size_t* widths, const size_t* strides,
+              size_t n_mats, const uint32_t* layers, MmcsPlan* plan);
+const char* mmcs_kernel_name(int kernel);  // "leaf_coop" .. "keccak_compress"; null for an unknown enumerator
 inline size_t mmcs_layer_words(uint64_t max_height) { return (size_t)(2 * max_height - 1) * 8; }
 int mmcs_root(hipStream_t stream, const Tree& t, uint32_t root_out[8]);
 int mmcs_open(hipStream_t stream, const Tree& t, uint64_t index, uint32_t* rows_out, uint32_t* path_out);

@@ -573,37 +573,25 @@ __global__ void __launch_bounds__(256) keccak_leaf_salted_kernel(SaltedRows<NP> 
     kk::permute_digest(st);
     store_digest64(digests + r * 8, st);
 }
-// (matrix, salt) x NP with equal matrix widths and 16-byte-aligned rows?  Fills `a` and returns the width, else 0.
-template <int NP>
-static uint32_t salted_rows_of(const RowSet& rs, SaltedRows<NP>* a) {
-    if (rs.count != 2u * NP) return 0;
+// (matrix, salt) x np with equal matrix widths and 16-byte-aligned rows?  The width, else 0.  (The plan's predicate.)
+static uint32_t salted_width(const RowSet& rs, uint32_t np) {
+    if (rs.count != 2u * np) return 0;
     const uint32_t w = rs.width[0];
     if (w != 4 && w != 6 && w != 8) return 0;
-    for (int p = 0; p < NP; p++) {
+    for (uint32_t p = 0; p < np; p++) {
         if (rs.width[2 * p] != w || rs.width[2 * p + 1] != 4 || rs.stride[2 * p] != rs.stride[0] || rs.stride[2 * p + 1] != 4) return 0;
         if (rs.stride[0] & (w == 6 ? 1u : 3u)) return 0;
         if ((reinterpret_cast<uintptr_t>(rs.ptr[2 * p]) & (w == 6 ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(rs.ptr[2 * p + 1]) & 15u)) return 0;
-        a->mat[p] = rs.ptr[2 * p]; a->salt[p] = rs.ptr[2 * p + 1];
     }
-    a->stride = rs.stride[0];
     return w;
 }
-// returns true when a salted-leaf kernel was launched for the tallest class
-static bool launch_keccak_leaf_salted(hipStream_t stream, const RowSet& rs, uint64_t n_rows, uint32_t* digests) {
-    const dim3 grid((uint32_t)((n_rows + 255) / 256)), block(256);
-    SaltedRows<1> a1;
-    SaltedRows<4> a4;
-    if (const uint32_t w = salted_rows_of<1>(rs, &a1)) {
-        if (w == 4) hipLaunchKernelGGL((keccak_leaf_salted_kernel<4, 1>), grid, block, 0, stream, a1, n_rows, digests);
-        else if (w == 6) hipLaunchKernelGGL((keccak_leaf_salted_kernel<6, 1>), grid, block, 0, stream, a1, n_rows, digests);
-        else hipLaunchKernelGGL((keccak_leaf_salted_kernel<8, 1>), grid, block, 0, stream, a1, n_rows, digests);
-        return true;
-    }
-    if (salted_rows_of<4>(rs, &a4) == 4) {
-        hipLaunchKernelGGL((keccak_leaf_salted_kernel<4, 4>), grid, block, 0, stream, a4, n_rows, digests);
-        return true;
-    }
-    return false;
+// the launch's half: a class the predicate accepted, as the kernel's argument
+template <int W, int NP>
+static void launch_keccak_leaf_salted(hipStream_t stream, const RowSet& rs, uint64_t n_rows, uint32_t* digests) {
+    SaltedRows<NP> a;
+    for (int p = 0; p < NP; p++) { a.mat[p] = rs.ptr[2 * p]; a.salt[p] = rs.ptr[2 * p + 1]; }
+    a.stride = rs.stride[0];
+    hipLaunchKernelGGL((keccak_leaf_salted_kernel<W, NP>), dim3((uint32_t)((n_rows + 255) / 256)), dim3(256), 0, stream, a, n_rows, digests);
 }
 
 // WIDE rows under the Keccak sponge (as leaf_hash_f64_wide_kernel): the workgroup's 256 rows staged through LDS one rate block
@@ -789,6 +777,166 @@ int keccak_f_states_variant(hipStream_t stream, uint64_t* d_states, uint64_t n, 
 }
 int keccak_f_states(hipStream_t stream, uint64_t* d_states, uint64_t n) { return keccak_f_states_variant(stream, d_states, n, 0); }
 
+// ---- mmcs_commit: the plan (which kernel reads which layer: pure host code, mmcs.h) and the launcher that executes one step of it ----
+// the matrices of height h, concatenated row-wise in the caller's order.  d_mats / strides may be null (mmcs.h)
+static RowSet class_rows(const uint32_t* const* d_mats, const size_t* heights, const size_t* widths, const size_t* strides, size_t n_mats, uint64_t h) {
+    RowSet rs{};
+    for (size_t m = 0; m < n_mats; m++)
+        if (heights[m] == h) {
+            rs.ptr[rs.count] = d_mats ? d_mats[m] : nullptr;
+            rs.width[rs.count] = (uint32_t)widths[m];
+            rs.stride[rs.count] = (uint32_t)(strides ? strides[m] : widths[m]);
+            rs.total += (uint32_t)widths[m];
+            rs.count++;
+        }
+    return rs;
+}
+// log2 of the digests one workgroup of a multi-level kernel takes (0: the kernel does one level, one state per lane or quad)
+static uint32_t chunk_log_of(int kernel) {
+    // 16 lanes per Poseidon2 state: 2^5 digests per workgroup = four waves, five levels per launch
+    constexpr uint32_t COOP_CHUNK_LOG = 5;
+    // one Keccak state per wave: 2^4 digests per workgroup
+    constexpr uint32_t KCOOP_CHUNK_LOG = 4;
+    // one-state-per-lane levels kernel: digests per workgroup.  A level costs one permutation's issue time (~9 us) per
+    // wave a SIMD holds, so ONE wave per workgroup (128 digests) spreads a layer of <= 2^15 digests over the whole chip;
+    // 2048 (sixteen waves on one CU) was 25 us per level
+    constexpr uint64_t KLANE_CHUNK = 1ull << 7;
+    return kernel == P3HIP_MK_TREE_LEVELS_COOP ? COOP_CHUNK_LOG : kernel == P3HIP_MK_KECCAK_TREE_LEVELS_COOP ? KCOOP_CHUNK_LOG
+           : kernel == P3HIP_MK_KECCAK_TREE_LEVELS ? log2u(KLANE_CHUNK) : 0u;
+}
+const char* mmcs_kernel_name(int kernel) {
+    static const char* const names[P3HIP_MK_COUNT] = {
+        "leaf_coop", "leaf_hash_q4", "leaf_hash_f64_wide", "leaf_hash_f64", "leaf_hash_f64_rowset", "leaf_hash", "tree_levels_coop",
+        "compress_layer_q4", "compress_layer_f64", "compress_layer", "keccak_leaf_wide", "keccak_leaf_salted<4,1>", "keccak_leaf_salted<6,1>",
+        "keccak_leaf_salted<8,1>", "keccak_leaf_salted<4,4>", "keccak_leaf", "keccak_tree_levels_coop", "keccak_tree_levels", "keccak_compress"};
+    return kernel >= 0 && kernel < P3HIP_MK_COUNT ? names[kernel] : nullptr;
+}
+
+int mmcs_plan(int kind, int profile, const uint32_t* const* d_mats, const size_t* heights, const size_t* widths, const size_t* strides,
+              size_t n_mats, const uint32_t* layers, MmcsPlan* plan) {
+    // ---- small-layer policy, by PROFILE (common.h; round 5: was a set of process-global environment switches) ----
+    // Layers with fewer than 2^12 permutations cannot fill the chip with one state per lane: they run the 16-lanes-per-state
+    // kernels (latency ~3x lower: ~3 us a level against ~8); the last digests finish inside one workgroup.  (Below 2^15 instead
+    // of 2^12: a lone 2^20 proof 3.3 against 3.6 ms, but the 16-lane form costs ~3.4x the VALU work and four provers lose 5 %;
+    // the quad form below took that range over.)
+    constexpr uint64_t COOP_MAX = 1ull << 12;
+    // LATENCY profile: one Poseidon2 state per DPP quad (poseidon2_q4.hip.h) for layers of 2^12 .. 2^15 permutations: 4-7 us a
+    // launch instead of ~12 at 1.6x the lane-instructions: a lone 2^20 proof 3.53 -> 3.33-3.38 ms.  THROUGHPUT profile: off — four
+    // concurrent provers LOSE 3.8 % with it (587 -> 565 proofs/s): the extra lane-instructions run at raised priority against the
+    // other provers' hash layers (profiles/r04_latency_ab.txt).  At 2^16 permutations the quad form loses even alone.
+    const uint64_t Q4_MAX = profile == PROFILE_LATENCY ? (1ull << 15) : 0;
+    // Cooperative Keccak levels (one state per wave, ~13x the lane-instructions of the per-lane form): layers of <= 2^10 digests
+    // under the THROUGHPUT profile (four provers: 2^12: 624.6 proofs/s, 2^11: 633, 2^10: 647, 2^9: 636), <= 2^12 under the LATENCY
+    // profile (a lone proof: -0.2 ms)
+    const uint64_t KCOOP_IN = profile == PROFILE_LATENCY ? (1ull << 12) : (1ull << 10);
+    uint64_t maxh = 0;
+    for (size_t i = 0; i < n_mats; i++) maxh = std::max<uint64_t>(maxh, heights[i]);
+    const uint32_t n_layers = log2u(maxh) + 1;  // <= P3HIP_MMCS_MAX_STEPS: at most one step each
+    auto injected = [&](uint32_t l) {  // a matrix is as tall as layer l is long
+        for (size_t m = 0; m < n_mats; m++)
+            if (heights[m] == maxh >> l) return true;
+        return false;
+    };
+    plan->n = 0;
+    auto step = [&](int kernel, uint32_t layer, uint32_t levels) {
+        plan->step[plan->n++] = p3hip_mmcs_step{kernel, layer, levels, levels && layer + levels + 1 == n_layers ? 1u : 0u};
+    };
+    const RowSet rs = class_rows(d_mats, heights, widths, strides, n_mats, maxh);
+    const bool dense1 = rs.count == 1 && rs.stride[0] == rs.width[0];  // the single-matrix kernels take (pointer, width)
+    if (kind == HASH_KECCAK) {
+        // one state per lane for the large layers, the lane-cooperative form (shuffles inside a half-wave) for the small ones
+        if (dense1 && rs.width[0] >= 68) step(P3HIP_MK_KECCAK_LEAF_WIDE, 0, 0);
+        else if (const uint32_t w = salted_width(rs, 1))
+            step(w == 4 ? P3HIP_MK_KECCAK_LEAF_SALTED_4_1 : w == 6 ? P3HIP_MK_KECCAK_LEAF_SALTED_6_1 : P3HIP_MK_KECCAK_LEAF_SALTED_8_1, 0, 0);
+        else step(salted_width(rs, 4) == 4 ? P3HIP_MK_KECCAK_LEAF_SALTED_4_4 : P3HIP_MK_KECCAK_LEAF, 0, 0);
+        for (uint32_t l = 1; l < n_layers;) {
+            if (maxh >> l >= COOP_MAX || injected(l)) { step(P3HIP_MK_KECCAK_COMPRESS, l - 1, 1); l++; continue; }
+            // as many injection-free levels as one launch may take.  Layers of <= KCOOP_IN digests (2^10 / 2^12 by profile) go through
+            // the lane-cooperative kernel; above that one state per lane, stopping where the cooperative kernel takes over
+            const uint64_t n_in = maxh >> (l - 1);
+            const bool coop = n_in <= KCOOP_IN;
+            const int kernel = coop ? P3HIP_MK_KECCAK_TREE_LEVELS_COOP : P3HIP_MK_KECCAK_TREE_LEVELS;
+            uint32_t levels = 0;
+            while (levels < (coop ? chunk_log_of(kernel) : 11u) && l + levels < n_layers && !injected(l + levels)) levels++;
+            if (!coop) while (levels > 1 && (n_in >> levels) < KCOOP_IN) levels--;
+            while ((1ull << levels) > std::min<uint64_t>(n_in, 1ull << chunk_log_of(kernel))) levels--;  // a workgroup's chunk
+            step(kernel, l - 1, levels);
+            l += levels;
+        }
+        return OK;
+    }
+    if (dense1 && maxh < COOP_MAX && maxh * 16 <= 0x7fffffffull) step(P3HIP_MK_LEAF_COOP, 0, 0);
+    else if (dense1 && maxh <= Q4_MAX && rs.width[0] <= 64 && (reinterpret_cast<uintptr_t>(layers) & 15u) == 0) step(P3HIP_MK_LEAF_HASH_Q4, 0, 0);
+    else if (dense1 && rs.width[0] >= 64) step(P3HIP_MK_LEAF_HASH_F64_WIDE, 0, 0);
+    else if (dense1) step(P3HIP_MK_LEAF_HASH_F64, 0, 0);
+    else if (maxh >= COOP_MAX || rs.count == 1) step(P3HIP_MK_LEAF_HASH_F64_ROWSET, 0, 0);
+    else step(P3HIP_MK_LEAF_HASH, 0, 0);
+    for (uint32_t l = 1; l < n_layers;) {
+        const uint64_t len = maxh >> l;
+        if (injected(l)) { step(P3HIP_MK_COMPRESS_LAYER, l - 1, 1); l++; continue; }
+        if (len >= COOP_MAX) { step(len <= Q4_MAX ? P3HIP_MK_COMPRESS_LAYER_Q4 : P3HIP_MK_COMPRESS_LAYER_F64, l - 1, 1); l++; continue; }
+        // as many injection-free levels as one launch may take (stop before the next injected layer)
+        uint32_t levels = 0;
+        while (levels < chunk_log_of(P3HIP_MK_TREE_LEVELS_COOP) && l + levels < n_layers && !injected(l + levels)) levels++;
+        while ((1ull << levels) > std::min<uint64_t>(2 * len, 1ull << chunk_log_of(P3HIP_MK_TREE_LEVELS_COOP))) levels--;
+        step(P3HIP_MK_TREE_LEVELS_COOP, l - 1, levels);
+        l += levels;
+    }
+    return OK;
+}
+
+// One step of a plan.  `layer`: the storage of digest layer step.layer, n its length in digests.  The leaf step WRITES it from the
+// rows of `rs`; every other step reads it and writes the next layer(s) right behind it (layers are stored back to back), injecting
+// the rows of `rs` when it has any.  root_copy: see tree_levels_coop_kernel.
+static int launch_step(hipStream_t stream, const p3hip_mmcs_step& s, const RowSet& rs, uint32_t* layer, uint64_t n, uint32_t* root_copy) {
+    constexpr uint32_t Q4_PRIO = 1;
+    const uint64_t n_out = n / 2;
+    uint32_t* next = layer + n * 8;
+    const dim3 b256(256), rows((uint32_t)((n + 255) / 256)), lanes((uint32_t)((n_out + 255) / 256));  // one row / one output digest per lane
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(n, 1ull << chunk_log_of(s.kernel)), levels = s.levels;
+    const dim3 chunks((uint32_t)(n / chunk));
+    const uint32_t inject = rs.count > 0 ? 1u : 0u;
+    switch (s.kernel) {
+        case P3HIP_MK_LEAF_COOP:
+            hipLaunchKernelGGL(leaf_coop_kernel, dim3((uint32_t)((n * 16 + 255) / 256)), b256, 0, stream, rs.ptr[0], rs.width[0], (uint32_t)n, layer);
+            break;
+        case P3HIP_MK_LEAF_HASH_Q4:
+            hipLaunchKernelGGL(leaf_hash_q4_kernel, dim3((uint32_t)((n * 4 + 255) / 256)), b256, 0, stream, rs.ptr[0], rs.width[0], n, layer, Q4_PRIO);
+            break;
+        case P3HIP_MK_LEAF_HASH_F64_WIDE: hipLaunchKernelGGL(leaf_hash_f64_wide_kernel, rows, b256, 0, stream, rs.ptr[0], rs.width[0], n, layer); break;
+        case P3HIP_MK_LEAF_HASH_F64: hipLaunchKernelGGL(leaf_hash_f64_kernel, rows, b256, 0, stream, rs.ptr[0], rs.width[0], n, layer); break;
+        case P3HIP_MK_LEAF_HASH_F64_ROWSET: hipLaunchKernelGGL(leaf_hash_f64_rowset_kernel, rows, b256, 0, stream, rs, n, layer); break;
+        case P3HIP_MK_LEAF_HASH: hipLaunchKernelGGL(leaf_hash_kernel, rows, b256, 0, stream, rs, n, layer); break;
+        case P3HIP_MK_TREE_LEVELS_COOP:
+            hipLaunchKernelGGL(tree_levels_coop_kernel, chunks, dim3(std::max<uint32_t>(64, chunk * 8)), 0, stream, layer, (uint32_t)n, chunk, levels,
+                               s.makes_root ? root_copy : nullptr);
+            break;
+        case P3HIP_MK_COMPRESS_LAYER_Q4:
+            hipLaunchKernelGGL(compress_layer_q4_kernel, dim3((uint32_t)((n_out * 4 + 255) / 256)), b256, 0, stream, layer, next, n_out, Q4_PRIO);
+            break;
+        case P3HIP_MK_COMPRESS_LAYER_F64: hipLaunchKernelGGL(compress_layer_f64_kernel, lanes, b256, 0, stream, layer, next, n_out); break;
+        case P3HIP_MK_COMPRESS_LAYER: hipLaunchKernelGGL(compress_layer_kernel, lanes, b256, 0, stream, layer, next, n_out, rs, inject); break;
+        case P3HIP_MK_KECCAK_LEAF_WIDE: hipLaunchKernelGGL(keccak_leaf_wide_kernel, rows, b256, 0, stream, rs.ptr[0], rs.width[0], n, layer); break;
+        case P3HIP_MK_KECCAK_LEAF_SALTED_4_1: launch_keccak_leaf_salted<4, 1>(stream, rs, n, layer); break;
+        case P3HIP_MK_KECCAK_LEAF_SALTED_6_1: launch_keccak_leaf_salted<6, 1>(stream, rs, n, layer); break;
+        case P3HIP_MK_KECCAK_LEAF_SALTED_8_1: launch_keccak_leaf_salted<8, 1>(stream, rs, n, layer); break;
+        case P3HIP_MK_KECCAK_LEAF_SALTED_4_4: launch_keccak_leaf_salted<4, 4>(stream, rs, n, layer); break;
+        case P3HIP_MK_KECCAK_LEAF: hipLaunchKernelGGL(keccak_leaf_kernel, rows, b256, 0, stream, rs, n, layer); break;
+        case P3HIP_MK_KECCAK_TREE_LEVELS_COOP:
+            hipLaunchKernelGGL(keccak_tree_levels_coop_kernel, chunks, dim3(std::max<uint32_t>(64, chunk * 32)), 0, stream, layer, (uint32_t)n, chunk,
+                               levels, root_copy);
+            break;
+        case P3HIP_MK_KECCAK_TREE_LEVELS:
+            hipLaunchKernelGGL(keccak_tree_levels_kernel, chunks, dim3(std::max<uint32_t>(64, chunk / 2)), (size_t)chunk * 32, stream, layer,
+                               (uint32_t)n, chunk, levels, root_copy);
+            break;
+        case P3HIP_MK_KECCAK_COMPRESS: hipLaunchKernelGGL(keccak_compress_kernel, lanes, b256, 0, stream, layer, next, n_out, rs, inject); break;
+        default: return fail(ERR_INTERNAL, "mmcs_commit: unknown kernel in the plan");
+    }
+    P3_HIP(hipGetLastError());
+    return OK;
+}
+
 // Test entry: ONE compression layer through the PRODUCTION kernel of a named form, launched with the geometry mmcs_commit gives it.
 // d_in: 2 n_out digests, d_out: n_out digests.  The layers are staged back to back in a 16-byte-aligned buffer of the entry's own (the
 // multi-level kernels write the next layer right behind the current one), so the caller's pointers need no alignment.  Synchronises.
@@ -816,33 +964,14 @@ int compress_layer_variant(hipStream_t stream, int kind, int variant, const uint
     uint32_t* buf = nullptr;
     P3_HIP(hipMalloc(reinterpret_cast<void**>(&buf), (size_t)(n_in + n_out) * 32));
     struct Free { uint32_t* p; ~Free() { (void)hipFree(p); } } guard{buf};
-    uint32_t* next = buf + n_in * 8;
     P3_HIP(hipMemcpyAsync(buf, d_in, (size_t)n_in * 32, hipMemcpyDeviceToDevice, stream));
-    const dim3 lane_grid((uint32_t)((n_out + 255) / 256)), b256(256);
-    const RowSet none{};
-    if (kind == HASH_POSEIDON2) {
-        if (variant == 0) hipLaunchKernelGGL(compress_layer_kernel, lane_grid, b256, 0, stream, buf, next, n_out, none, 0u);
-        else if (variant == 1) hipLaunchKernelGGL(compress_layer_f64_kernel, lane_grid, b256, 0, stream, buf, next, n_out);
-        else if (variant == 2) hipLaunchKernelGGL(compress_layer_q4_kernel, dim3((uint32_t)((n_out * 4 + 255) / 256)), b256, 0, stream, buf, next, n_out, 1u);
-        else {
-            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 32);
-            hipLaunchKernelGGL(tree_levels_coop_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk * 8)), 0, stream, buf,
-                               (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
-        }
-    } else {
-        if (variant == 0) hipLaunchKernelGGL(keccak_compress_kernel, lane_grid, b256, 0, stream, buf, next, n_out, none, 0u);
-        else if (variant == 1) {
-            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 128);
-            hipLaunchKernelGGL(keccak_tree_levels_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk / 2)), (size_t)chunk * 32,
-                               stream, buf, (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
-        } else {
-            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 16);
-            hipLaunchKernelGGL(keccak_tree_levels_coop_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk * 32)), 0, stream, buf,
-                               (uint32_t)n_in, chunk, 1u, (uint32_t*)nullptr);
-        }
-    }
-    P3_HIP(hipGetLastError());
-    P3_HIP(hipMemcpyAsync(d_out, next, (size_t)n_out * 32, hipMemcpyDeviceToDevice, stream));
+    static const int forms[2][4] = {
+        {P3HIP_MK_COMPRESS_LAYER, P3HIP_MK_COMPRESS_LAYER_F64, P3HIP_MK_COMPRESS_LAYER_Q4, P3HIP_MK_TREE_LEVELS_COOP},
+        {P3HIP_MK_KECCAK_COMPRESS, P3HIP_MK_KECCAK_TREE_LEVELS, P3HIP_MK_KECCAK_TREE_LEVELS_COOP, P3HIP_MK_COUNT}};
+    // one level, nothing injected, no root copy: the step mmcs_commit's plan would hold for this kernel on a layer of n_in digests
+    const p3hip_mmcs_step one{forms[kind == HASH_KECCAK][variant], 0, 1, 0};
+    if (int rc = launch_step(stream, one, RowSet{}, buf, n_in, nullptr)) return rc;
+    P3_HIP(hipMemcpyAsync(d_out, buf + n_in * 8, (size_t)n_out * 32, hipMemcpyDeviceToDevice, stream));
     P3_HIP(hipStreamSynchronize(stream));
     return OK;
 }
@@ -899,26 +1028,6 @@ __global__ void __launch_bounds__(64) open_gather_many_kernel(OpenArgs a, const 
     }
 }
 
-static RowSet make_rowset(const Tree& t, uint64_t h) {
-    RowSet rs{};
-    for (size_t m = 0; m < t.mats.size(); m++)
-        if (t.heights[m] == h) {
-            rs.ptr[rs.count] = t.mats[m];
-            rs.width[rs.count] = (uint32_t)t.widths[m];
-            rs.stride[rs.count] = (uint32_t)t.strides[m];
-            rs.total += (uint32_t)t.widths[m];
-            rs.count++;
-        }
-    return rs;
-}
-
-
-static bool has_height(const Tree& t, uint64_t h) {
-    for (size_t m = 0; m < t.mats.size(); m++)
-        if (t.heights[m] == h) return true;
-    return false;
-}
-
 Tree::~Tree() {
     if (layers && owns_layers) (void)hipFree(layers);
     if (staging) (void)hipFree(staging);
@@ -970,124 +1079,15 @@ int mmcs_commit(hipStream_t stream, const uint32_t* const* d_mats, const size_t*
         off += len * 8;
         if (len == 1) break;
     }
-    // ---- small-layer policy, by PROFILE (common.h; round 5: was a set of process-global environment switches) ----
-    // Layers with fewer than 2^12 permutations cannot fill the chip with one state per lane: they run the 16-lanes-per-state
-    // kernels (latency ~3x lower: ~3 us a level against ~8), 2^5 digests per workgroup = four waves, five levels per launch; the
-    // last digests finish inside one workgroup.  (Below 2^15 instead of 2^12: a lone 2^20 proof 3.3 against 3.6 ms, but the
-    // 16-lane form costs ~3.4x the VALU work and four provers lose 5 %; the quad form below took that range over.)
-    constexpr uint64_t COOP_MAX = 1ull << 12;
-    constexpr uint32_t COOP_CHUNK_LOG = 5;
-    // LATENCY profile: one Poseidon2 state per DPP quad (poseidon2_q4.hip.h) for layers of 2^12 .. 2^15 permutations: 4-7 us a
-    // launch instead of ~12 at 1.6x the lane-instructions: a lone 2^20 proof 3.53 -> 3.33-3.38 ms.  THROUGHPUT profile: off — four
-    // concurrent provers LOSE 3.8 % with it (587 -> 565 proofs/s): the extra lane-instructions run at raised priority against the
-    // other provers' hash layers (profiles/r04_latency_ab.txt).  At 2^16 permutations the quad form loses even alone.
-    const uint64_t Q4_MAX = profile == PROFILE_LATENCY ? (1ull << 15) : 0;
-    constexpr uint32_t Q4_PRIO = 1;
-    // Cooperative Keccak levels (one state per wave, ~13x the lane-instructions of the per-lane form): layers of <= 2^10 digests
-    // under the THROUGHPUT profile (four provers: 2^12: 624.6 proofs/s, 2^11: 633, 2^10: 647, 2^9: 636), <= 2^12 under the LATENCY
-    // profile (a lone proof: -0.2 ms); 2^4 digests per workgroup
-    const uint64_t KCOOP_IN = profile == PROFILE_LATENCY ? (1ull << 12) : (1ull << 10);
-    constexpr uint32_t KCOOP_CHUNK_LOG = 4;
-    // one-state-per-lane levels kernel: digests per workgroup.  A level costs one permutation's issue time (~9 us) per
-    // wave a SIMD holds, so ONE wave per workgroup (128 digests) spreads a layer of <= 2^15 digests over the whole chip;
-    // 2048 (sixteen waves on one CU) was 25 us per level
-    constexpr uint64_t KLANE_CHUNK = 1ull << 7;
-    if (kind == HASH_KECCAK) {
-        // one state per lane for the large layers, the lane-cooperative form (shuffles inside a half-wave) for the small ones
-        RowSet rs0 = make_rowset(*t, maxh);
-        if (rs0.count == 1 && rs0.width[0] >= 68 && rs0.stride[0] == rs0.width[0])
-            hipLaunchKernelGGL(keccak_leaf_wide_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs0.ptr[0], rs0.width[0], maxh,
-                               t->layers);
-        else if (!launch_keccak_leaf_salted(stream, rs0, maxh, t->layers))
-            hipLaunchKernelGGL(keccak_leaf_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs0, maxh, t->layers);
-        P3_HIP(hipGetLastError());
-        for (size_t l = 1; l < t->layer_len.size(); l++) {
-            uint64_t len = t->layer_len[l];
-            RowSet rs = make_rowset(*t, len);
-            if (len < COOP_MAX && !rs.count) {
-                // as many injection-free levels as one launch may take.  Layers of <= KCOOP_IN digests (2^10 / 2^12 by profile) go through
-                // the lane-cooperative kernel, 2^KCOOP_CHUNK_LOG digests per workgroup; above that one state per lane, chunks of KLANE_CHUNK
-                // digests per workgroup, stopping where the cooperative kernel takes over
-                const uint64_t n_in = t->layer_len[l - 1];
-                const bool coop = n_in <= KCOOP_IN;
-                uint32_t levels = 0;
-                while (levels < (coop ? KCOOP_CHUNK_LOG : 11u) && l + levels < t->layer_len.size() && !has_height(*t, t->layer_len[l + levels])) levels++;
-                if (!coop) while (levels > 1 && (n_in >> levels) < KCOOP_IN) levels--;
-                const uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, coop ? 1ull << KCOOP_CHUNK_LOG : KLANE_CHUNK);  // per workgroup
-                while ((1u << levels) > chunk) levels--;
-                if (coop)
-                    hipLaunchKernelGGL(keccak_tree_levels_coop_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk * 32)), 0,
-                                       stream, t->layers + t->layer_off[l - 1], (uint32_t)n_in, chunk, levels, root_copy);
-                else
-                    hipLaunchKernelGGL(keccak_tree_levels_kernel, dim3((uint32_t)(n_in / chunk)), dim3(std::max<uint32_t>(64, chunk / 2)),
-                                       (size_t)chunk * 32, stream, t->layers + t->layer_off[l - 1], (uint32_t)n_in, chunk, levels, root_copy);
-                P3_HIP(hipGetLastError());
-                if (t->layer_len[l + levels - 1] == 1) t->root_copied = root_copy != nullptr;
-                l += levels - 1;  // the loop's l++ completes the step
-                continue;
-            }
-            hipLaunchKernelGGL(keccak_compress_kernel, dim3((uint32_t)((len + 255) / 256)), dim3(256), 0, stream,
-                               t->layers + t->layer_off[l - 1], t->layers + t->layer_off[l], len, rs, rs.count > 0 ? 1u : 0u);
-            P3_HIP(hipGetLastError());
-        }
-        *out = t.release();
-        return OK;
-    }
-    {
-        RowSet rs = make_rowset(*t, maxh);
-        const bool dense1 = rs.count == 1 && rs.stride[0] == rs.width[0];  // the single-matrix kernels take (pointer, width)
-        if (dense1 && maxh < COOP_MAX && maxh * 16 <= 0x7fffffffull) {
-            hipLaunchKernelGGL(leaf_coop_kernel, dim3((uint32_t)((maxh * 16 + 255) / 256)), dim3(256), 0, stream, rs.ptr[0],
-                               rs.width[0], (uint32_t)maxh, t->layers);
-        } else if (dense1 && maxh <= Q4_MAX && rs.width[0] <= 64 && (reinterpret_cast<uintptr_t>(t->layers) & 15u) == 0) {
-            hipLaunchKernelGGL(leaf_hash_q4_kernel, dim3((uint32_t)((maxh * 4 + 255) / 256)), dim3(256), 0, stream, rs.ptr[0], rs.width[0], maxh,
-                               t->layers, Q4_PRIO);
-        } else if (dense1 && rs.width[0] >= 64) {
-            hipLaunchKernelGGL(leaf_hash_f64_wide_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs.ptr[0],
-                               rs.width[0], maxh, t->layers);
-        } else if (dense1) {
-            hipLaunchKernelGGL(leaf_hash_f64_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs.ptr[0],
-                               rs.width[0], maxh, t->layers);
-        } else if ((maxh >= COOP_MAX || (rs.count == 1 && !dense1))) {
-            hipLaunchKernelGGL(leaf_hash_f64_rowset_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs, maxh, t->layers);
-        } else {
-            hipLaunchKernelGGL(leaf_hash_kernel, dim3((uint32_t)((maxh + 255) / 256)), dim3(256), 0, stream, rs, maxh, t->layers);
-        }
-        P3_HIP(hipGetLastError());
-    }
-    for (size_t l = 1; l < t->layer_len.size();) {
-        uint64_t len = t->layer_len[l];
-        RowSet rs = make_rowset(*t, len);
-        bool inject = rs.count > 0;
-        if (!inject && len < COOP_MAX) {
-            // as many injection-free levels as one launch may take (<= 7, stop before the next injected layer)
-            uint32_t levels = 0;
-            while (levels < COOP_CHUNK_LOG && l + levels < t->layer_len.size() && !has_height(*t, t->layer_len[l + levels])) levels++;
-            uint64_t n_in = t->layer_len[l - 1];
-            uint32_t chunk = (uint32_t)std::min<uint64_t>(n_in, 1ull << COOP_CHUNK_LOG);
-            while ((1u << levels) > chunk) levels--;
-            uint32_t blocks = (uint32_t)(n_in / chunk);
-            uint32_t threads = std::max<uint32_t>(64, chunk * 8);
-            bool makes_root = t->layer_len[l + levels - 1] == 1;
-            hipLaunchKernelGGL(tree_levels_coop_kernel, dim3(blocks), dim3(threads), 0, stream, t->layers + t->layer_off[l - 1],
-                               (uint32_t)n_in, chunk, levels, makes_root ? root_copy : nullptr);
-            P3_HIP(hipGetLastError());
-            if (makes_root) t->root_copied = root_copy != nullptr;
-            l += levels;
-            continue;
-        }
-        if (!inject && len <= Q4_MAX) {
-            hipLaunchKernelGGL(compress_layer_q4_kernel, dim3((uint32_t)((len * 4 + 255) / 256)), dim3(256), 0, stream,
-                               t->layers + t->layer_off[l - 1], t->layers + t->layer_off[l], len, Q4_PRIO);
-        } else if (!inject) {
-            hipLaunchKernelGGL(compress_layer_f64_kernel, dim3((uint32_t)((len + 255) / 256)), dim3(256), 0, stream,
-                               t->layers + t->layer_off[l - 1], t->layers + t->layer_off[l], len);
-        } else {
-            hipLaunchKernelGGL(compress_layer_kernel, dim3((uint32_t)((len + 255) / 256)), dim3(256), 0, stream,
-                               t->layers + t->layer_off[l - 1], t->layers + t->layer_off[l], len, rs, inject ? 1u : 0u);
-        }
-        P3_HIP(hipGetLastError());
-        l++;
+    MmcsPlan plan;
+    if (int rc = mmcs_plan(kind, profile, t->mats.data(), heights, widths, t->strides.data(), n_mats, t->layers, &plan)) return rc;
+    for (uint32_t i = 0; i < plan.n; i++) {
+        const p3hip_mmcs_step& s = plan.step[i];
+        // the rows a step hashes: the tallest class into the leaf layer, else the class as tall as the layer it writes (none when it
+        // writes several)
+        const RowSet rs = class_rows(t->mats.data(), heights, widths, t->strides.data(), n_mats, t->layer_len[i ? s.layer + 1 : 0]);
+        if (int rc = launch_step(stream, s, rs, t->layers + t->layer_off[s.layer], t->layer_len[s.layer], root_copy)) return rc;
+        if (s.makes_root && chunk_log_of(s.kernel)) t->root_copied = root_copy != nullptr;  // the multi-level kernels copy the root out
     }
     *out = t.release();
     return OK;

@@ -56,6 +56,28 @@ def launch_plan(height, width):
     return tuple(int(buf[i]) for i in range(min(n.value, 8)))
 
 
+class _MmcsStep(C.Structure):  # include/p3hip.h p3hip_mmcs_step
+    _fields_ = [("kernel", C.c_int), ("layer", C.c_uint32), ("levels", C.c_uint32), ("makes_root", C.c_uint32)]
+
+
+def mmcs_commit_plan(hash_name, profile, dims, strides=None, mats=None, layers=0):
+    """(leaf kernel, [(kernel, levels) per launch above the leaves]) of a commitment to matrices of dims = [(height, width), ..] in
+    the caller's order, from the library (p3hip_mmcs_commit_plan, host-only).  strides: words between rows per matrix (None = dense);
+    mats / layers: addresses, looked at for their alignment only (None / 0 = aligned)."""
+    from . import _lib
+    from .fib_air import _hash_kind, profile_kind
+    n = len(dims)
+    hh, ww = (C.c_size_t * n)(*[h for h, _ in dims]), (C.c_size_t * n)(*[w for _, w in dims])
+    ss = (C.c_size_t * n)(*strides) if strides is not None else None
+    mm = (C.c_void_p * n)(*mats) if mats is not None else None
+    steps, count = (_MmcsStep * 64)(), C.c_size_t(0)
+    L = _lib.lib()
+    _lib.check(L.p3hip_mmcs_commit_plan(_hash_kind(hash_name), profile_kind(profile), mm, hh, ww, ss, n, C.c_void_p(layers),
+                                        steps, 64, C.byref(count)))
+    names = [(L.p3hip_mmcs_kernel_name(s.kernel).decode(), int(s.levels)) for s in steps[:count.value]]
+    return names[0][0], names[1:]
+
+
 @dataclass
 class ComputePlan:
     params: FftStageParams

@@ -1,4 +1,5 @@
-"""The driver logic of mmcs_commit — which rows are hashed into which digest — as data and as two small restatements.  No GPU here.
+"""The driver logic of mmcs_commit — which rows are hashed into which digest — as an independent driver, a grid of commitments and the
+names the grid must reach.  No GPU here.
 
   driver_layers   an independent per-digest tree driver over the oracle's primitives only (hash_row / compress or their Keccak
                   forms): tests/pyref.py::merkle_layers with the hash as a parameter.  It keeps oracle.Tree, the reference of the
@@ -6,7 +7,8 @@
   the grid        the commitments tests/test_gpu_mmcs_classes.py runs, shared with the host test: one injected matrix at every
                   level (A), two and all injections (B), class compositions on both sides of the cooperative threshold (C), 64
                   matrices (D), hiding commitments, and the caps.
-  plan            which kernels mmcs_commit launches for a shape, so that the host test can ASSERT what the grid reaches.
+  kernels_of ..   every kernel mmcs_commit can launch, by hash and profile: what the host test asks the grid to reach.  Which of
+                  them a shape DOES reach is the library's own answer (plan.mmcs_commit_plan), never restated here.
 
 A shape is a list of (height, width) in the CALLER's order; a class is the matrices of one height in that order."""
 import zlib
@@ -162,10 +164,6 @@ def tallest(dims):
 
 
 # ---------------------------------------------------------------- which kernels a shape reaches
-COOP_MAX = 1 << 12
-COOP_CHUNK_LOG, KCOOP_CHUNK_LOG = 5, 4
-KLANE_CHUNK = 1 << 7
-KLANE_MAX_LEVELS = 11
 MAX_CLASS_MATS, MAX_MATS = 16, 64
 
 POSEIDON2_KERNELS = {"leaf_coop", "leaf_hash_q4", "leaf_hash_f64_wide", "leaf_hash_f64", "leaf_hash_f64_rowset", "leaf_hash",
@@ -183,89 +181,8 @@ def kernels_of(kind, profile):
     return names - (THROUGHPUT_ONLY if profile == "latency" else LATENCY_ONLY)
 
 
-def _salted_leaf(ws):
-    """launch_keccak_leaf_salted / salted_rows_of<1>, <4>: (matrix, salt) x 1 with a matrix of 4, 6 or 8 words, or x 4 with matrices of 4"""
-    if len(ws) == 2 and ws[0] in (4, 6, 8) and ws[1] == SALT_ELEMS:
-        return "keccak_leaf_salted<%d,1>" % ws[0]
-    if len(ws) == 8 and all(w == 4 for w in ws):
-        return "keccak_leaf_salted<4,4>"
-    return None
-
-
-def plan(kind, profile, dims):
-    """(leaf kernel, [(kernel, levels) per launch above the leaves]) for one commitment.
-
-    This RESTATES the branch conditions of mmcs_commit in plonky3-mobile_amd/csrc/mmcs.hip — COOP_MAX 2^12, Q4_MAX 2^15 / 0 and
-    KCOOP_IN 2^12 / 2^10 by profile (latency / throughput), chunk logs 5 and 4, KLANE_CHUNK 128, the width bounds 64 and 68, the
-    salted shapes — and changes with it.  It computes no digest and is no reference of any: it exists so that the host test can assert
-    which kernels and which `levels` the grid reaches.  The branches that depend on a pointer's alignment or on a row stride (the quad
-    leaf kernel's 16-byte layer storage, the salted kernels' 16-byte rows, a column group of a wider matrix) are out of its scope:
-    dense matrices in aligned allocations are assumed, and tests/test_gpu_buffer_contract.py owns the other side of each."""
-    assert kind in HASHES and profile in PROFILES
-    maxh = tallest(dims)
-    lens = [maxh >> i for i in range(maxh.bit_length())]
-    heights = {h for h, _ in dims}
-    leaf_ws = [w for h, w in dims if h == maxh]
-    launches = []
-    if kind == "keccak":
-        kcoop_in = 1 << 12 if profile == "latency" else 1 << 10
-        if len(leaf_ws) == 1 and leaf_ws[0] >= 68:
-            leaf = "keccak_leaf_wide"
-        else:
-            leaf = _salted_leaf(leaf_ws) or "keccak_leaf"
-        l = 1
-        while l < len(lens):
-            if lens[l] < COOP_MAX and lens[l] not in heights:
-                n_in = lens[l - 1]
-                coop = n_in <= kcoop_in
-                levels = 0
-                while levels < (KCOOP_CHUNK_LOG if coop else KLANE_MAX_LEVELS) and l + levels < len(lens) and lens[l + levels] not in heights:
-                    levels += 1
-                while not coop and levels > 1 and (n_in >> levels) < kcoop_in:
-                    levels -= 1
-                chunk = min(n_in, 1 << KCOOP_CHUNK_LOG if coop else KLANE_CHUNK)
-                while (1 << levels) > chunk:
-                    levels -= 1
-                launches.append(("keccak_tree_levels_coop" if coop else "keccak_tree_levels", levels))
-                l += levels
-            else:
-                launches.append(("keccak_compress", 1))
-                l += 1
-        return leaf, launches
-    q4_max = 1 << 15 if profile == "latency" else 0
-    dense1 = len(leaf_ws) == 1
-    if dense1 and maxh < COOP_MAX:
-        leaf = "leaf_coop"
-    elif dense1 and maxh <= q4_max and leaf_ws[0] <= 64:
-        leaf = "leaf_hash_q4"
-    elif dense1 and leaf_ws[0] >= 64:
-        leaf = "leaf_hash_f64_wide"
-    elif dense1:
-        leaf = "leaf_hash_f64"
-    elif maxh >= COOP_MAX:
-        leaf = "leaf_hash_f64_rowset"
-    else:
-        leaf = "leaf_hash"
-    l = 1
-    while l < len(lens):
-        inject = lens[l] in heights
-        if not inject and lens[l] < COOP_MAX:
-            levels = 0
-            while levels < COOP_CHUNK_LOG and l + levels < len(lens) and lens[l + levels] not in heights:
-                levels += 1
-            chunk = min(lens[l - 1], 1 << COOP_CHUNK_LOG)
-            while (1 << levels) > chunk:
-                levels -= 1
-            launches.append(("tree_levels_coop", levels))
-            l += levels
-            continue
-        launches.append(("compress_layer" if inject else "compress_layer_q4" if lens[l] <= q4_max else "compress_layer_f64", 1))
-        l += 1
-    return leaf, launches
-
-
 def launch_neighbours(dims, launches):
-    """per launch of plan(): (kernel, levels, its input layer is an injected one, the layer after its last one is an injected one).
+    """per launch above the leaves (plan.mmcs_commit_plan's list): (kernel, levels, its input layer is an injected one, the layer after its last one is an injected one).
     The leaf layer is no injected layer."""
     maxh = tallest(dims)
     lens = [maxh >> i for i in range(maxh.bit_length())]
