@@ -936,6 +936,41 @@ int p3hip_air_verifier_verify(p3hip_air_verifier_t *v, size_t n, const uint8_t *
                               uint32_t *status_out);
 void p3hip_air_verifier_destroy(p3hip_air_verifier_t *v);
 
+/* ---- p3_uni_stark::prove for an `air` of the caller's in ONE device-resident launch chain.  The proof is the one
+ * p3hip_air_verify takes, byte for byte what plonky3-mobile_amd/air.py prove_air returns over a non-hiding TwoAdicFriPcs; the contract
+ * follows p3hip_fib_prover_* and p3hip_air_verifier_create.
+ * create copies the program (the air may be destroyed at once), remembers the calling thread's current device — every later call with
+ * another one current is refused — and allocates everything a proof needs: the trace LDE, the C = 2^log_quotient_degree chunk matrices
+ * and their LDEs, the two trees' digest layers, the open's scratch, the FRI arena, the proof staging buffer and its pinned landing
+ * buffer.  A failed allocation is reported with the arena's size.  profile / hash: P3HIP_PROFILE_*, 0 Poseidon2 / 1 Keccak; stream:
+ * the caller's (own_stream = 0; NULL is the null stream) or one the prover creates and owns.
+ * LIMITS, each refused by name before anything is allocated:  1 <= log_n <= 27 - log_quotient_degree;  log_blowup >= 1 and >=
+ * log_quotient_degree (the committed LDE must cover the quotient domain);  log_n + log_blowup <= 26;  log_final_poly_len < log_n;
+ * 2 width + 4 C <= 8192 batched columns;  proof_of_work_bits <= 30;  and whatever p3hip_air_proof_len refuses for the shape.  The
+ * hiding PCS and preprocessed columns are not covered.
+ * prove_dev: d_trace = 2^log_n x width Montgomery words of device memory on the prover's device, natural row order, ANY 4-byte
+ * alignment, READ IN PLACE: never written, never copied; the caller leaves it unchanged until the proof is returned.  pis: n_public
+ * Montgomery words of HOST memory (may be NULL when n_public == 0); one >= P is P3HIP_ERR_BAD_ARG.  The prover does not judge the trace:
+ * a broken one yields a proof the verifiers reject with code 10.  flags: P3HIP_PROVE_CHECK_TRACE runs p3hip_air_check_trace_dev on the
+ * prover's stream first and refuses a broken trace with "constraints had nonzero value on row R (constraint K)", R and K the ones that
+ * entry names; this costs one more synchronisation.  *proof_out stays valid until the prover's next proof or its destruction.
+ * Between the first launch and the copy-back there is no allocation and no host synchronisation: the transcript runs on the device.
+ * One synchronisation per proof, plus one per continued search range when the first proof-of-work range held no witness.
+ * prove: the same for a trace in host memory, uploaded into a slot the first such call allocates.
+ * enqueue_dev / finish: the same in two halves.  enqueue_dev returns once the launches and the copy-back are queued on the prover's
+ * stream; finish synchronises and serialises.  ONE proof in flight: a second enqueue, or a prove, before finish is refused, as is
+ * finish without enqueue.  Calls of one prover come from one thread at a time; two provers on two streams overlap freely. */
+typedef struct p3hip_air_prover p3hip_air_prover_t;
+int p3hip_air_prover_create(const p3hip_air_t *air, int profile, int hash, unsigned log_n, const p3hip_fri_params_t *params, void *stream,
+                            int own_stream, p3hip_air_prover_t **out);
+int p3hip_air_prover_prove_dev(p3hip_air_prover_t *prover, const uint32_t *d_trace, const uint32_t *pis, unsigned flags,
+                               const uint8_t **proof_out, size_t *proof_len);
+int p3hip_air_prover_prove(p3hip_air_prover_t *prover, const uint32_t *host_trace, const uint32_t *pis, unsigned flags,
+                           const uint8_t **proof_out, size_t *proof_len);
+int p3hip_air_prover_enqueue_dev(p3hip_air_prover_t *prover, const uint32_t *d_trace, const uint32_t *pis);
+int p3hip_air_prover_finish(p3hip_air_prover_t *prover, const uint8_t **proof_out, size_t *proof_len);
+void p3hip_air_prover_destroy(p3hip_air_prover_t *prover);
+
 /* The CPU column of the benchmark is the caller's: the reference times Plonky3's Radix2DitParallel (fib_air.rs:101,137-141),
  * which libp3hip does not contain (no CPU path in the product).  Returns 0 on success; Montgomery words, natural row order. */
 typedef int (*p3hip_cpu_dft_fn)(void *user, const uint32_t *in, uint32_t *out, size_t height, size_t width);

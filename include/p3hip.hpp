@@ -617,6 +617,57 @@ class AirVerifier {
     size_t n_public_ = 0, proof_len_ = 0;
 };
 
+// p3_uni_stark::prove for a caller-defined AIR in one device-resident launch chain (p3hip.h p3hip_air_prover_*): the arena of one (air,
+// log_n, fp, hash, profile); a proof allocates nothing and synchronises once.  The Air may be destroyed once the prover exists.
+class AirProver {
+  public:
+    AirProver(const Air& air, unsigned log_n, FriParameters fp = FriParameters(), int hash = P3HIP_HASH_POSEIDON2,
+              int profile = P3HIP_PROFILE_LATENCY, void* stream = nullptr, bool own_stream = true)
+        : log_n_(log_n), width_(air.info().width), n_public_(air.info().n_public) {
+        p3hip_fri_params_t c{fp.log_blowup, fp.log_final_poly_len, fp.num_queries, fp.proof_of_work_bits};
+        check(p3hip_air_prover_create(air.handle(), profile, hash, log_n, &c, stream, own_stream ? 1 : 0, &h_));
+    }
+    AirProver(const AirProver&) = delete;
+    AirProver& operator=(const AirProver&) = delete;
+    ~AirProver() { p3hip_air_prover_destroy(h_); }
+    // d_trace: 2^log_n x width Montgomery words of device memory, read in place; check: P3HIP_PROVE_CHECK_TRACE first
+    std::vector<uint8_t> prove_dev(const uint32_t* d_trace, const std::vector<uint32_t>& pis, bool check_constraints = false) {
+        need_pis(pis);
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_air_prover_prove_dev(h_, d_trace, pis.data(), check_constraints ? P3HIP_PROVE_CHECK_TRACE : 0u, &p, &n));
+        return std::vector<uint8_t>(p, p + n);
+    }
+    // the same for a trace in host memory (row-major, 2^log_n x width words), uploaded
+    std::vector<uint8_t> prove(const std::vector<uint32_t>& trace, const std::vector<uint32_t>& pis, bool check_constraints = false) {
+        need_pis(pis);
+        if (trace.size() != ((size_t)width_ << log_n_)) throw Error(P3HIP_ERR_BAD_ARG, "AirProver: a trace of 2^log_n x width words");
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_air_prover_prove(h_, trace.data(), pis.data(), check_constraints ? P3HIP_PROVE_CHECK_TRACE : 0u, &p, &n));
+        return std::vector<uint8_t>(p, p + n);
+    }
+    // the two halves: one proof in flight; the trace stays unchanged until finish returns
+    void enqueue_dev(const uint32_t* d_trace, const std::vector<uint32_t>& pis) {
+        need_pis(pis);
+        check(p3hip_air_prover_enqueue_dev(h_, d_trace, pis.data()));
+    }
+    std::vector<uint8_t> finish() {
+        const uint8_t* p = nullptr;
+        size_t n = 0;
+        check(p3hip_air_prover_finish(h_, &p, &n));
+        return std::vector<uint8_t>(p, p + n);
+    }
+
+  private:
+    void need_pis(const std::vector<uint32_t>& pis) const {
+        if (pis.size() != n_public_) throw Error(P3HIP_ERR_BAD_ARG, "AirProver: n_public public values");
+    }
+    p3hip_air_prover_t* h_ = nullptr;
+    unsigned log_n_ = 0;
+    size_t width_ = 0, n_public_ = 0;
+};
+
 // run_fib_air_zk (fib_air.rs:27-75) on the hip backend (non-hiding; either hash configuration): "fib_air ok (n=8, x=21)"
 inline std::string run_fib_air(unsigned log_n = 3, uint64_t a = 0, uint64_t b = 1, FriParameters fp = FriParameters(),
                                int hash = P3HIP_HASH_POSEIDON2) {

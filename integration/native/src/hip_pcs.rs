@@ -275,6 +275,27 @@ extern "C" {
     ) -> i32;
     fn p3hip_air_verifier_destroy(v: *mut p3hip_air_verifier_t);
 }
+// The prover of the same proofs as one device-resident launch chain (include/p3hip.h p3hip_air_prover_*): declarations only.
+#[repr(C)]
+pub struct p3hip_air_prover_t {
+    _private: [u8; 0],
+}
+#[allow(dead_code)]
+extern "C" {
+    fn p3hip_air_prover_create(
+        air: *const p3hip_air_t, profile: i32, hash: i32, log_n: u32, params: *const p3hip_fri_params_t, stream: *mut c_void, own_stream: i32,
+        out: *mut *mut p3hip_air_prover_t,
+    ) -> i32;
+    fn p3hip_air_prover_prove_dev(
+        prover: *mut p3hip_air_prover_t, d_trace: *const u32, pis: *const u32, flags: u32, proof_out: *mut *const u8, proof_len: *mut usize,
+    ) -> i32;
+    fn p3hip_air_prover_prove(
+        prover: *mut p3hip_air_prover_t, host_trace: *const u32, pis: *const u32, flags: u32, proof_out: *mut *const u8, proof_len: *mut usize,
+    ) -> i32;
+    fn p3hip_air_prover_enqueue_dev(prover: *mut p3hip_air_prover_t, d_trace: *const u32, pis: *const u32) -> i32;
+    fn p3hip_air_prover_finish(prover: *mut p3hip_air_prover_t, proof_out: *mut *const u8, proof_len: *mut usize) -> i32;
+    fn p3hip_air_prover_destroy(prover: *mut p3hip_air_prover_t);
+}
 
 // BabyBear is a transparent u32 holding the Montgomery word (the same reinterpretation backend_hip.rs makes of `shift`), and
 // BinomialExtensionField<Val, 4> is its four coefficients in order [UPSTREAM-RECALL]

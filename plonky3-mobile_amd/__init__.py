@@ -13,11 +13,11 @@ from .mmcs import (BAD_INDEX, FORM_AUTO, FORM_COOP, FORM_LANE, NOT_CANONICAL, RO
                    MerkleTreeMmcs, keccak_f, poseidon2_permute)
 from .pcs import Challenger, HidingFriPcs, PcsProverData, PcsRejected, PcsVerifier, TwoAdicFriPcs, pcs_proof_len
 from . import pcs
-from .air import Air, AirBuilder, AirRejected, AirVerifier, air_proof_len, fibonacci_air, prove_air, verify_air
+from .air import Air, AirBuilder, AirProver, AirRejected, AirVerifier, air_proof_len, fibonacci_air, prove_air, verify_air
 from . import air
 from . import plan
 
 __all__ = ["BackendKind", "GpuDft", "MerkleTree", "MerkleTreeMmcs", "MerkleTreeHidingMmcs", "P3HipError", "bit_reverse_rows", "coset_lde_from_coeffs", "build",
            "dev_u32", "generate_trace_rows", "FibAirProver", "FibAirBatchProver", "FibAirVerifier", "VERIFY_MALFORMED", "proof_len", "DeviceRng", "FriParameters", "BENCHMARK_CASES", "benchmark_input", "percentile_ms", "run_dft_benchmark", "run_dft_benchmark_report", "run_fib_air", "run_fib_air_zk_report", "verify_fib_air", "check_fib_trace", "PROVE_CHECK_TRACE", "fib_public_x", "get_backend_kind", "get_thread_profile", "set_thread_profile", "host_u32", "is_available", "last_timing_line", "keccak_f", "poseidon2_permute", "set_backend_kind",
            "set_backend_kind_from_str", "take_last_error", "GENERATOR_MONTY", "MONTY_ONE", "P", "ROOT_MISMATCH", "WRONG_HEIGHT", "NOT_CANONICAL",
-           "BAD_INDEX", "FORM_AUTO", "FORM_LANE", "FORM_COOP", "Challenger", "PcsProverData", "PcsRejected", "TwoAdicFriPcs", "HidingFriPcs", "PcsVerifier", "pcs_proof_len", "Air", "AirBuilder", "AirRejected", "fibonacci_air", "prove_air", "verify_air", "AirVerifier", "air_proof_len"]
+           "BAD_INDEX", "FORM_AUTO", "FORM_LANE", "FORM_COOP", "Challenger", "PcsProverData", "PcsRejected", "TwoAdicFriPcs", "HidingFriPcs", "PcsVerifier", "pcs_proof_len", "Air", "AirBuilder", "AirRejected", "fibonacci_air", "prove_air", "verify_air", "AirVerifier", "air_proof_len", "AirProver"]

@@ -185,6 +185,12 @@ _SIGS = {
                                                 C.c_void_p]),
     "p3hip_air_verifier_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_void_p, u32p]),
     "p3hip_air_verifier_destroy": (None, [C.c_void_p]),
+    "p3hip_air_prover_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "p3hip_air_prover_prove_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+    "p3hip_air_prover_prove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+    "p3hip_air_prover_enqueue_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3hip_air_prover_finish": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+    "p3hip_air_prover_destroy": (None, [C.c_void_p]),
     "p3hip_pcs_destroy": (None, [C.c_void_p]),
 }
 

@@ -1,14 +1,15 @@
 """Caller-defined AIRs (include/p3hip.h "caller-defined AIRs"): AirBuilder, shaped after p3_air::AirBuilder, records an AIR's
 constraints as an expression DAG and compiles it to the library's instruction list; Air owns the validated program and runs it —
 quotient_values and check_constraints on the device, the verifier's evaluation on the host; prove_air / verify_air are
-p3_uni_stark::prove / verify over a non-hiding TwoAdicFriPcs and a Challenger.  Field elements are Montgomery words unless said
+p3_uni_stark::prove / verify over a non-hiding TwoAdicFriPcs and a Challenger; AirProver is the same prover as one device-resident
+launch chain of the library's.  Field elements are Montgomery words unless said
 otherwise.  There is no CPU path for the device steps."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .fib_air import VERIFY_MALFORMED, FriParameters, _hash_kind
+from .fib_air import VERIFY_MALFORMED, FriParameters, _hash_kind, profile_kind
 from .gpu_dft import P, _is_torch, _stream_ptr, dev_u32
 from .pcs import Challenger, PcsRejected, _words
 
@@ -457,6 +458,102 @@ def prove_air(air, pcs, trace, pis=None):
     for c in range(len(chunks)):
         head += [u(4), o[8 * w + 16 * c:8 * w + 16 * (c + 1)]]
     return np.concatenate(head).astype(np.uint32).tobytes() + fri
+
+
+class AirProver:
+    """p3_uni_stark::prove for ONE (air, log_n, params, hash, profile) in one device-resident launch chain (include/p3hip.h
+    p3hip_air_prover_*): the arena is allocated here, a proof allocates nothing, keeps the transcript on the device and synchronises
+    once.  The bytes are prove_air's.  The air may be freed once the prover exists.  own_stream=False: the launches go to the torch
+    stream that is current NOW; True: to a stream the prover creates (two provers then overlap)."""
+
+    def __init__(self, air, log_n, params=None, hash="poseidon2", profile="latency", own_stream=False):
+        if not isinstance(air, Air) or not air._h:
+            raise TypeError("AirProver: air must be a live Air")
+        if not isinstance(log_n, (int, np.integer)) or isinstance(log_n, bool) or log_n < 1:
+            raise ValueError("AirProver: log_n must be an integer >= 1")
+        self.params = params or FriParameters()
+        kind, prof = _hash_kind(hash), profile_kind(profile)
+        self.log_n, self.hash, self.profile = int(log_n), hash, profile
+        self.width, self.n_public = air.width, air.n_public
+        self._h, self._own = C.c_void_p(), bool(own_stream)
+        stream = None if own_stream else _stream_ptr()
+        self._stream = None if own_stream else stream.value
+        _lib.check(_lib.lib().p3hip_air_prover_create(air._h, prof, kind, self.log_n, C.cast(self.params._c(), C.c_void_p), stream,
+                                                      1 if own_stream else 0, C.byref(self._h)))
+
+    def _args(self, trace, pis):
+        """-> (the trace as a contiguous numpy array or a device pointer, is it host memory, the public values); raises before any
+        library call"""
+        rows = 1 << self.log_n
+        what = "AirProver: a (%d, %d) trace of 32-bit Montgomery words" % (rows, self.width)
+        p = _words(pis if pis is not None else [], self.n_public)
+        if _is_torch(trace):
+            if tuple(trace.shape) != (rows, self.width) or trace.element_size() != 4 or trace.is_floating_point():
+                raise ValueError(what + ", got %s %s" % (tuple(trace.shape), trace.dtype))
+            if not trace.is_cuda or not trace.is_contiguous():
+                raise ValueError("AirProver: the trace must be a contiguous device tensor")
+            return trace, False, p
+        host = np.ascontiguousarray(trace, dtype=np.uint32)
+        if host.shape != (rows, self.width):
+            raise ValueError(what + ", got %s" % (host.shape,))
+        return host, True, p
+
+    def _behind_torch(self):
+        """the prover reads the tensor on ITS stream: what torch queued elsewhere to write it must be complete"""
+        import torch
+        cur = torch.cuda.current_stream()
+        if self._own or cur.cuda_stream != self._stream:
+            cur.synchronize()
+
+    def prove(self, trace, pis=None, check_constraints=False):
+        """trace: a (2^log_n, width) torch device tensor (read in place, left unchanged) or numpy array (uploaded); pis: n_public
+        Montgomery words.  check_constraints=True runs Air.check_trace's pass first (one more synchronisation) and raises P3HipError
+        naming the row and constraint; without it any trace is proven and the verifiers reject what does not hold."""
+        t, host, p = self._args(trace, pis)
+        if not self._h:
+            raise ValueError("AirProver: closed")
+        out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        pp = p.ctypes.data_as(C.c_void_p) if p.size else None
+        flags = 1 if check_constraints else 0  # P3HIP_PROVE_CHECK_TRACE
+        if host:
+            _lib.check(_lib.lib().p3hip_air_prover_prove(self._h, t.ctypes.data_as(C.c_void_p), pp, flags, C.byref(out), C.byref(n)))
+        else:
+            self._behind_torch()
+            _lib.check(_lib.lib().p3hip_air_prover_prove_dev(self._h, C.c_void_p(t.data_ptr()), pp, flags, C.byref(out), C.byref(n)))
+        return C.string_at(out, n.value)
+
+    def enqueue(self, trace, pis=None):
+        """Queues the proof of a DEVICE trace and returns at once; one proof in flight.  Keep `trace` alive and unchanged until finish()."""
+        t, host, p = self._args(trace, pis)
+        if host:
+            raise TypeError("AirProver.enqueue: a torch device tensor (prove() uploads numpy arrays)")
+        if not self._h:
+            raise ValueError("AirProver: closed")
+        self._behind_torch()
+        _lib.check(_lib.lib().p3hip_air_prover_enqueue_dev(self._h, C.c_void_p(t.data_ptr()), p.ctypes.data_as(C.c_void_p) if p.size else None))
+        self._keep = t
+
+    def finish(self):
+        """Waits for the enqueued proof and returns its bytes."""
+        if not self._h:
+            raise ValueError("AirProver: closed")
+        out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        try:
+            _lib.check(_lib.lib().p3hip_air_prover_finish(self._h, C.byref(out), C.byref(n)))
+        finally:
+            self._keep = None
+        return C.string_at(out, n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().p3hip_air_prover_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class AirRejected(_lib.P3HipError):

@@ -1,6 +1,7 @@
 // A caller-defined AIR as a small program (include/p3hip.h "caller-defined AIRs"): the validated program, its figures and the
 // device copies the two kernels of air.hip read.  Everything a kernel indexes with comes from here, checked once by air_create.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
@@ -36,6 +37,19 @@ struct Air {
 
 // makes the device copies of the program on the calling thread's current device (what the first device call of an Air does)
 int air_ensure_device(Air& a);
+
+// What an owner of a table of its own needs (AirProver, prover.hip): the table of a quotient over 2^log_n rows is
+// publics | K alpha powers, entry k = alpha^(K-1-k), at `ap` | Z_H, 1 / Z_H at `zh` | (8-byte aligned) chunk pointers, `words` in all
+// (at most Air::tab_words).  air_table_tail fills words [zh, words) into `tail`: they depend on log_n and the chunks alone.
+struct AirTable {
+    uint32_t ap, zh, words;
+};
+AirTable air_table(const Air& a, uint32_t log_n);
+void air_table_tail(const Air& a, uint32_t log_n, uint32_t* const* d_chunks, uint32_t* tail);
+// air_kernel<0> alone on table d_tab, which the caller has filled in stream order: no upload, no event, nothing checked
+int air_quotient_launch(Air& a, hipStream_t st, const uint32_t* d_tab, const uint32_t* d_lde, uint32_t log_n);
+// p3hip_air_check_trace_dev behind its argument checks
+int air_check_trace(Air& a, hipStream_t st, const uint32_t* d_trace, uint32_t log_n, const uint32_t* pis, long long* row_out, int* constraint_out);
 
 }  // namespace p3
 

@@ -276,11 +276,25 @@ int order_behind_last_call(Air& a, hipStream_t st) {
     return OK;
 }
 
-int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la) {
+// the kernel alone, on table `tab` (the object's own d_tab, or a table its owner keeps and has filled in stream order: AirProver)
+int launch_kernel(Air& a, int mode, hipStream_t st, const uint32_t* tab, const uint32_t* rows, AirLaunch& la) {
     Context* cx;
     int rc = get_context(&cx);
     if (rc) return rc;
     if (mode == 0 && (rc = cx->get_root_table(st, la.log_rows, false, &la.roots))) return rc;
+    const void* kernel = mode == 0 ? reinterpret_cast<const void*>(&air_kernel<0>) : reinterpret_cast<const void*>(&air_kernel<1>);
+    if ((rc = cx->ensure_dynamic_lds(kernel, P3HIP_AIR_MAX_SLOTS * AIR_BLOCK * 4))) return rc;
+    const uint32_t lds = a.n_slots * AIR_BLOCK * 4;
+    const dim3 grid((la.rows_n + AIR_BLOCK - 1) / AIR_BLOCK), block(AIR_BLOCK);
+    const uint4* code = reinterpret_cast<const uint4*>(a.d_code);
+    if (mode == 0) hipLaunchKernelGGL(air_kernel<0>, grid, block, lds, st, code, a.d_consts, tab, rows, la);
+    else hipLaunchKernelGGL(air_kernel<1>, grid, block, lds, st, code, a.d_consts, tab, rows, la);
+    P3_HIP(hipGetLastError());
+    return OK;
+}
+
+int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la) {
+    int rc;
     if ((rc = order_behind_last_call(a, st))) return rc;
     // the upload reads pinned staging of the object's; the event behind it says when the staging may be written again (a wait that
     // ends at once unless the previous call's upload has not run yet).  d_tab itself is reused in stream order.
@@ -290,23 +304,84 @@ int launch(Air& a, int mode, hipStream_t st, const uint32_t* rows, AirLaunch& la
     memcpy(a.h_pin, a.h_tab.data(), a.h_tab.size() * 4);
     P3_HIP(hipMemcpyAsync(a.d_tab, a.h_pin, a.h_tab.size() * 4, hipMemcpyHostToDevice, st));
     P3_HIP(hipEventRecord(done, st));
-    const void* kernel = mode == 0 ? reinterpret_cast<const void*>(&air_kernel<0>) : reinterpret_cast<const void*>(&air_kernel<1>);
-    if ((rc = cx->ensure_dynamic_lds(kernel, P3HIP_AIR_MAX_SLOTS * AIR_BLOCK * 4))) return rc;
-    const uint32_t lds = a.n_slots * AIR_BLOCK * 4;
-    const dim3 grid((la.rows_n + AIR_BLOCK - 1) / AIR_BLOCK), block(AIR_BLOCK);
-    const uint4* code = reinterpret_cast<const uint4*>(a.d_code);
-    if (mode == 0) hipLaunchKernelGGL(air_kernel<0>, grid, block, lds, st, code, a.d_consts, a.d_tab, rows, la);
-    else hipLaunchKernelGGL(air_kernel<1>, grid, block, lds, st, code, a.d_consts, a.d_tab, rows, la);
-    P3_HIP(hipGetLastError());
+    if ((rc = launch_kernel(a, mode, st, a.d_tab, rows, la))) return rc;
     P3_HIP(hipEventRecord((hipEvent_t)a.run_done, st));
     a.last_stream = (void*)st;
     a.ran = true;
     return OK;
 }
 
+// the quotient launch's figures and the table's offsets for 2^log_n rows (roots: set by launch_kernel)
+AirLaunch quotient_launch(const Air& a, uint32_t log_n) {
+    const uint32_t lqd = a.log_quotient_degree, C = 1u << lqd, log_qn = log_n + lqd;
+    AirLaunch la{};
+    la.n_instr = (uint32_t)(a.code.size() / 4);
+    la.width = a.width;
+    la.rows_n = 1u << log_qn;
+    la.log_rows = log_qn;
+    la.log_qd = lqd;
+    la.gen = bb::to_monty(bb::GEN);
+    la.ginv = bb::inv(bb::two_adic_generator(log_n));
+    la.ap_off = a.n_public;
+    la.zh_off = la.ap_off + 4 * a.n_constraints;
+    la.ptr_off = (la.zh_off + 2 * C + 3) & ~3u;
+    return la;
+}
+
 }  // namespace
 
 int air_ensure_device(Air& a) { return ensure_device(a); }
+
+AirTable air_table(const Air& a, uint32_t log_n) {
+    const AirLaunch la = quotient_launch(a, log_n);
+    return AirTable{la.ap_off, la.zh_off, la.ptr_off + 2u * (1u << a.log_quotient_degree)};
+}
+
+void air_table_tail(const Air& a, uint32_t log_n, uint32_t* const* d_chunks, uint32_t* tail) {
+    const AirLaunch la = quotient_launch(a, log_n);
+    const uint32_t C = 1u << a.log_quotient_degree;
+    memset(tail, 0, (la.ptr_off + 2 * C - la.zh_off) * 4);
+    const uint32_t gn = bb::pow(la.gen, 1u << log_n), wc = bb::two_adic_generator(a.log_quotient_degree);
+    uint32_t w = bb::ONE;
+    for (uint32_t c = 0; c < C; c++) {
+        const uint32_t zh = bb::sub(bb::mul(gn, w), bb::ONE);  // nonzero: GENERATOR^n w is no two-power root of unity
+        tail[c] = zh;
+        tail[C + c] = bb::inv(zh);
+        w = bb::mul(w, wc);
+    }
+    memcpy(tail + (la.ptr_off - la.zh_off), d_chunks, C * sizeof(uint32_t*));
+    static_assert(sizeof(uint32_t*) == 8, "chunk pointers take two words");
+}
+
+int air_quotient_launch(Air& a, hipStream_t st, const uint32_t* d_tab, const uint32_t* d_lde, uint32_t log_n) {
+    AirLaunch la = quotient_launch(a, log_n);
+    return launch_kernel(a, 0, st, d_tab, d_lde, la);
+}
+
+int air_check_trace(Air& a, hipStream_t st, const uint32_t* d_trace, uint32_t log_n, const uint32_t* pis, long long* row_out, int* constraint_out) {
+    int rc;
+    if ((rc = ensure_device(a))) return rc;
+    DeviceScope scope;
+    if ((rc = scope.enter(a.device))) return rc;
+    AirLaunch la{};
+    la.n_instr = (uint32_t)(a.code.size() / 4);
+    la.width = a.width;
+    la.rows_n = 1u << log_n;
+    la.log_rows = log_n;
+    la.found = a.d_found;
+    std::vector<uint32_t>& tab = a.h_tab;
+    tab.assign(a.n_public ? a.n_public : 1, 0);
+    if (a.n_public) memcpy(tab.data(), pis, a.n_public * 4);
+    if ((rc = order_behind_last_call(a, st))) return rc;
+    P3_HIP(hipMemsetAsync(a.d_found, 0xff, 8, st));
+    if ((rc = launch(a, 1, st, d_trace, la))) return rc;
+    unsigned long long found = 0;
+    P3_HIP(hipMemcpyAsync(&found, a.d_found, 8, hipMemcpyDeviceToHost, st));
+    P3_HIP(hipStreamSynchronize(st));
+    *row_out = found == ~0ull ? -1 : (long long)(found >> 32);
+    *constraint_out = found == ~0ull ? -1 : (int)(found & 0xffffffffu);
+    return OK;
+}
 
 Air::~Air() {
     if (d_code) (void)hipFree(d_code);  // waits for the device: an enqueued upload or kernel of this object has run when it returns
@@ -374,18 +449,7 @@ int p3hip_air_quotient_dev(p3hip_air_t* air, void* stream, const uint32_t* d_lde
         if ((rc = ensure_device(a))) return rc;
         DeviceScope scope;
         if ((rc = scope.enter(a.device))) return rc;
-        const uint32_t n = 1u << log_n, log_qn = log_n + lqd;
-        AirLaunch la{};
-        la.n_instr = (uint32_t)(a.code.size() / 4);
-        la.width = a.width;
-        la.rows_n = 1u << log_qn;
-        la.log_rows = log_qn;
-        la.log_qd = lqd;
-        la.gen = bb::to_monty(bb::GEN);
-        la.ginv = bb::inv(bb::two_adic_generator(log_n));
-        la.ap_off = a.n_public;
-        la.zh_off = la.ap_off + 4 * K;
-        la.ptr_off = (la.zh_off + 2 * C + 3) & ~3u;
+        AirLaunch la = quotient_launch(a, log_n);
         std::vector<uint32_t>& tab = a.h_tab;
         tab.assign(la.ptr_off + 2 * C, 0);
         if (a.n_public) memcpy(tab.data(), pis, a.n_public * 4);
@@ -395,16 +459,7 @@ int p3hip_air_quotient_dev(p3hip_air_t* air, void* stream, const uint32_t* d_lde
             memcpy(&tab[la.ap_off + 4 * k], p.c, 16);
             p = bb::mul(p, al);
         }
-        const uint32_t gn = bb::pow(la.gen, n), wc = bb::two_adic_generator(lqd);
-        uint32_t w = bb::ONE;
-        for (uint32_t c = 0; c < C; c++) {
-            const uint32_t zh = bb::sub(bb::mul(gn, w), bb::ONE);  // nonzero: GENERATOR^n w is no two-power root of unity
-            tab[la.zh_off + c] = zh;
-            tab[la.zh_off + C + c] = bb::inv(zh);
-            w = bb::mul(w, wc);
-        }
-        memcpy(&tab[la.ptr_off], d_chunks_out, C * sizeof(uint32_t*));
-        static_assert(sizeof(uint32_t*) == 8, "chunk pointers take two words");
+        air_table_tail(a, log_n, d_chunks_out, &tab[la.zh_off]);
         return launch(a, 0, (hipStream_t)stream, d_lde, la);
     });
 }
@@ -418,28 +473,7 @@ int p3hip_air_check_trace_dev(p3hip_air_t* air, void* stream, const uint32_t* d_
         if ((uintptr_t)d_trace & 3) return fail(ERR_BAD_ARG, "air_check_trace: the trace must be 4-byte aligned");
         int rc;
         if ((rc = check_words(pis, a.n_public, "air_check_trace: public value"))) return rc;
-        if ((rc = ensure_device(a))) return rc;
-        DeviceScope scope;
-        if ((rc = scope.enter(a.device))) return rc;
-        hipStream_t st = (hipStream_t)stream;
-        AirLaunch la{};
-        la.n_instr = (uint32_t)(a.code.size() / 4);
-        la.width = a.width;
-        la.rows_n = 1u << log_n;
-        la.log_rows = log_n;
-        la.found = a.d_found;
-        std::vector<uint32_t>& tab = a.h_tab;
-        tab.assign(a.n_public ? a.n_public : 1, 0);
-        if (a.n_public) memcpy(tab.data(), pis, a.n_public * 4);
-        if ((rc = order_behind_last_call(a, st))) return rc;
-        P3_HIP(hipMemsetAsync(a.d_found, 0xff, 8, st));
-        if ((rc = launch(a, 1, st, d_trace, la))) return rc;
-        unsigned long long found = 0;
-        P3_HIP(hipMemcpyAsync(&found, a.d_found, 8, hipMemcpyDeviceToHost, st));
-        P3_HIP(hipStreamSynchronize(st));
-        *row_out = found == ~0ull ? -1 : (long long)(found >> 32);
-        *constraint_out = found == ~0ull ? -1 : (int)(found & 0xffffffffu);
-        return OK;
+        return air_check_trace(a, (hipStream_t)stream, d_trace, log_n, pis, row_out, constraint_out);
     });
 }
 

@@ -1643,3 +1643,100 @@ int p3hip_air_verifier_verify(p3hip_air_verifier_t* v, size_t n, const uint8_t* 
 }
 void p3hip_air_verifier_destroy(p3hip_air_verifier_t* v) { delete v; }
 }  // extern "C"
+
+// ---- proofs of caller-defined AIRs made in one device-resident launch chain (air_prover.hip.inc) ----
+struct p3hip_air_prover {
+    AirProver p;
+    std::vector<uint8_t> last;
+};
+// the public values, the flags and the optional check_constraints pass in front of a proof
+static int air_prover_admit(p3hip_air_prover& h, const uint32_t* d_trace, const uint32_t* pis, unsigned flags, const char* who) {
+    if (flags & ~P3HIP_PROVE_CHECK_TRACE) return fail(ERR_BAD_ARG, std::string(who) + ": unknown flag bits");
+    if (!pis && h.p.n_public()) return fail(ERR_BAD_ARG, std::string(who) + ": null public values");
+    for (uint32_t k = 0; k < h.p.n_public(); k++)
+        if (pis[k] >= bb::P) return fail(ERR_BAD_ARG, std::string(who) + ": public value " + std::to_string(k) + " is not a canonical field element");
+    if (!(flags & P3HIP_PROVE_CHECK_TRACE)) return OK;
+    long long row = -1;
+    int k = -1;
+    if (int rc = h.p.check_trace(d_trace, pis, &row, &k)) return rc;
+    if (row >= 0) return fail(ERR_BAD_ARG, "constraints had nonzero value on row " + std::to_string(row) + " (constraint " + std::to_string(k) + ")");
+    return OK;
+}
+static int air_prover_device(const p3hip_air_prover& h) {
+    Context* cx;
+    if (int rc = get_context(&cx)) return rc;
+    if (cx->device != h.p.device())
+        return fail(ERR_BAD_ARG, "air prover: created on device " + std::to_string(h.p.device()) + ", current device is " + std::to_string(cx->device));
+    return OK;
+}
+extern "C" {
+int p3hip_air_prover_create(const p3hip_air_t* air, int profile, int hash, unsigned log_n, const p3hip_fri_params_t* params, void* stream,
+                            int own_stream, p3hip_air_prover_t** out) {
+    return guarded([&]() -> int {
+        if (!air || !params || !out) return fail(ERR_BAD_ARG, "air_prover_create: null argument");
+        if (profile != P3HIP_PROFILE_THROUGHPUT && profile != P3HIP_PROFILE_LATENCY) return fail(ERR_BAD_ARG, "air_prover_create: unknown profile");
+        const int prof = profile == P3HIP_PROFILE_THROUGHPUT ? PROFILE_THROUGHPUT : PROFILE_LATENCY;
+        Context* cx;
+        int rc = get_context(&cx);
+        if (rc) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        bool own = false;
+        if (own_stream) {
+            P3_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            own = true;
+        }
+        std::unique_ptr<p3hip_air_prover> h(new p3hip_air_prover());
+        FriParams fp{params->log_blowup, params->log_final_poly_len, params->num_queries, params->proof_of_work_bits};
+        if ((rc = h->p.init(air->a, prof, hash, log_n, fp, st, own))) return rc;  // on failure the destructor destroys the owned stream
+        *out = h.release();
+        return OK;
+    });
+}
+int p3hip_air_prover_enqueue_dev(p3hip_air_prover_t* prover, const uint32_t* d_trace, const uint32_t* pis) {
+    return guarded([&]() -> int {
+        if (!prover) return fail(ERR_BAD_ARG, "air_prover_enqueue_dev: null argument");
+        if (int rc = air_prover_device(*prover)) return rc;
+        if (int rc = air_prover_admit(*prover, d_trace, pis, 0, "air_prover_enqueue_dev")) return rc;
+        return prover->p.enqueue(d_trace, pis);
+    });
+}
+int p3hip_air_prover_finish(p3hip_air_prover_t* prover, const uint8_t** proof_out, size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!prover || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "air_prover_finish: null argument");
+        int rc = prover->p.finish(&prover->last);
+        if (rc) { prover->last.clear(); return rc; }  // a failed proof leaves nothing behind that could be mistaken for one
+        *proof_out = prover->last.data();
+        *proof_len = prover->last.size();
+        return OK;
+    });
+}
+int p3hip_air_prover_prove_dev(p3hip_air_prover_t* prover, const uint32_t* d_trace, const uint32_t* pis, unsigned flags, const uint8_t** proof_out,
+                               size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!prover || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "air_prover_prove_dev: null argument");
+        if (prover->p.pending()) return fail(ERR_BAD_ARG, "air prover: finish the enqueued proof before a synchronous prove");
+        if (int rc = air_prover_device(*prover)) return rc;
+        if (!d_trace) return fail(ERR_BAD_ARG, "air_prover_prove_dev: null trace");
+        if (int rc = air_prover_admit(*prover, d_trace, pis, flags, "air_prover_prove_dev")) return rc;
+        if (int rc = prover->p.enqueue(d_trace, pis)) return rc;
+        return p3hip_air_prover_finish(prover, proof_out, proof_len);
+    });
+}
+int p3hip_air_prover_prove(p3hip_air_prover_t* prover, const uint32_t* host_trace, const uint32_t* pis, unsigned flags, const uint8_t** proof_out,
+                           size_t* proof_len) {
+    return guarded([&]() -> int {
+        if (!prover || !host_trace || !proof_out || !proof_len) return fail(ERR_BAD_ARG, "air_prover_prove: null argument");
+        if (prover->p.pending()) return fail(ERR_BAD_ARG, "air prover: finish the enqueued proof before a synchronous prove");
+        if (int rc = air_prover_device(*prover)) return rc;
+        if (flags & ~P3HIP_PROVE_CHECK_TRACE) return fail(ERR_BAD_ARG, "air_prover_prove: unknown flag bits");
+        // into the arena's trace slot, on the prover's stream: ordered before everything of the proof that reads it
+        uint32_t* slot = prover->p.arena_trace();
+        if (!slot) return ERR_HIP;
+        P3_HIP(hipMemcpyAsync(slot, host_trace, ((size_t)4 << prover->p.log_n()) * prover->p.width(), hipMemcpyHostToDevice, prover->p.stream()));
+        if (int rc = air_prover_admit(*prover, slot, pis, flags, "air_prover_prove")) return rc;
+        if (int rc = prover->p.enqueue(slot, pis)) return rc;
+        return p3hip_air_prover_finish(prover, proof_out, proof_len);
+    });
+}
+void p3hip_air_prover_destroy(p3hip_air_prover_t* prover) { delete prover; }
+}  // extern "C"

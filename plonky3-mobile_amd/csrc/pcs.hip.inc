@@ -37,8 +37,9 @@ struct PcsDenArgs {
     uint32_t* d;   // [K][big] extension elements
     uint32_t* xd;  // [K][h]
     uint32_t big, log_big, h, gen;
+    const DenConsts* dk;  // DEV: the K points' constants in device memory, written earlier on the stream (AirProver); k is not read
 };
-template <int K>
+template <int K, bool DEV = false>
 __global__ void __launch_bounds__(256) pcs_inv_denoms_kernel(TwoLevelTable roots, PcsDenArgs a) {
     const uint32_t big = a.big;
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,7 +52,7 @@ __global__ void __launch_bounds__(256) pcs_inv_denoms_kernel(TwoLevelTable roots
         xs[k] = x;
 #pragma unroll
         for (int z = 0; z < K; z++) {
-            const DenConsts& c = a.k[z];
+            const DenConsts& c = DEV ? a.dk[z] : a.k[z];
             const uint32_t v = bb::sub(c.z0, x);
             const uint32_t dd0 = bb::add(bb::sqr(v), c.k0), dd1 = bb::sub(bb::mul(c.k1, v), c.c1);
             a0[K * k + z] = v; e0[K * k + z] = dd0; e1[K * k + z] = dd1;
@@ -74,7 +75,7 @@ __global__ void __launch_bounds__(256) pcs_inv_denoms_kernel(TwoLevelTable roots
         if (j >= big) break;
 #pragma unroll
         for (int z = 0; z < K; z++) {
-            const DenConsts& c = a.k[z];
+            const DenConsts& c = DEV ? a.dk[z] : a.k[z];
             const uint32_t i = K * k + z;
             const uint32_t f0 = bb::mul(e0[i], nrm[i]), f1 = bb::neg(bb::mul(e1[i], nrm[i]));  // 1/D = f0 + f1 Y
             Ext r;
@@ -170,6 +171,7 @@ struct PcsOpenArgs {
     uint32_t* alp;         // [total] extension elements: alpha^i
     Ext z[PCS_MAX_POINTS];
     uint32_t n_points, n_pairs, total, log_h, sn, denom;  // total: the length of the alpha table; log_h, sn, denom: the tallest height's
+    const Ext* dz;  // null, or the n_points points in device memory, written earlier on the stream (AirProver): z is not read
 };
 __device__ __forceinline__ Ext pcs_pick(const Ext* f, uint32_t k) { return k == 0 ? f[0] : k == 1 ? f[1] : k == 2 ? f[2] : f[3]; }
 // finish the opened values (interpolate_coset's factor (z^h - s^h) / (h s^h), h the pair's own height), put them into the staging
@@ -177,7 +179,7 @@ __device__ __forceinline__ Ext pcs_pick(const Ext* f, uint32_t k) { return k == 
 __device__ __forceinline__ void pcs_bary_factors(const PcsOpenArgs& a, uint32_t log_h, uint32_t sn, uint32_t denom, Ext* f) {
 #pragma unroll
     for (uint32_t k = 0; k < PCS_MAX_POINTS; k++) {
-        Ext z = a.z[k < a.n_points ? k : 0];
+        Ext z = a.dz ? a.dz[k < a.n_points ? k : 0] : a.z[k < a.n_points ? k : 0];
         for (uint32_t i = 0; i < log_h; i++) z = bb::sqr(z);
         f[k] = bb::scale(bb::sub(z, bb::ext_from_base(sn)), denom);
     }
@@ -395,6 +397,12 @@ bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big) {
     if (z[1] || z[2] || z[3]) return false;
     const uint32_t q = bb::mul(z[0], bb::inv(bb::to_monty(bb::GEN)));
     return bb::pow(q, 1ull << log_big) == bb::ONE;
+}
+
+// workgroups of pcs_bary_kernel along a matrix's rows: up to 4096 per matrix (at most 1024 blocks of rows), at least 8 wave steps each
+static uint32_t pcs_bary_blocks(uint32_t w, uint32_t log_h) {
+    const uint32_t tiles = (w + 63) / 64, rps = w < 64 ? 64 / w : 1, mh = 1u << log_h;
+    return std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(1024, 4096 / tiles), mh / std::min<uint32_t>(mh, 32 * rps)));
 }
 
 struct Pcs::Impl {
@@ -656,11 +664,9 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
     std::vector<size_t> part_off(mats.size());
     size_t part_words = 0;
     for (size_t m = 0; m < mats.size(); m++) {
-        const uint32_t w = mats[m].w, tiles = (w + 63) / 64, rps = w < 64 ? 64 / w : 1;
-        const uint32_t mh = 1u << mats[m].log_h;
-        nblk[m] = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(1024, 4096 / tiles), mh / std::min<uint32_t>(mh, 32 * rps)));
+        nblk[m] = pcs_bary_blocks(mats[m].w, mats[m].log_h);
         part_off[m] = part_words;
-        part_words += (size_t)nblk[m] * mats[m].np * w * 4;
+        part_words += (size_t)nblk[m] * mats[m].np * mats[m].w * 4;
     }
     if ((rc = s.d.reserve((size_t)n_points * big * 4))) return rc;
     if ((rc = s.xd.reserve((size_t)n_points * h * 4))) return rc;
@@ -800,3 +806,4 @@ int Pcs::open(const PcsData* const* rounds, size_t n_rounds, const size_t* point
 }  // namespace p3
 
 #include "pcs_hiding.hip.inc"
+#include "air_prover.hip.inc"

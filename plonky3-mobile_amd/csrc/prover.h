@@ -169,6 +169,36 @@ class Pcs {
     int hiding_finish(PcsData* data, uint32_t root_out[8]);
 };
 
+// p3_uni_stark::prove for a caller-defined AIR (air.h) over the non-hiding PCS, device-resident (air_prover.hip.inc; include/p3hip.h
+// p3hip_air_prover_*): one object owns the arena of one (AIR, log_n, FRI parameters, hash, profile); a proof is one launch chain on
+// the object's stream with the transcript on the device, one copy-back and one synchronisation.  The bytes are prove_air's.
+struct Air;
+class AirProver {
+  public:
+    AirProver();
+    ~AirProver();
+    AirProver(const AirProver&) = delete;
+    // copies the program; every gate is refused by name before anything is allocated
+    int init(const Air& air, int profile, int hash, uint32_t log_n, const FriParams& fp, hipStream_t stream, bool own_stream);
+    // d_trace: 2^log_n x width Montgomery words in device memory, read in place; pis: n_public host words, each < P.  One proof in
+    // flight: enqueue returns once the launches and the copy-back are queued, finish synchronises and serialises
+    int enqueue(const uint32_t* d_trace, const uint32_t* pis);
+    int finish(std::vector<uint8_t>* proof);
+    // check_constraints on the prover's stream (synchronises): *row < 0 when every constraint holds on every row
+    int check_trace(const uint32_t* d_trace, const uint32_t* pis, long long* row, int* constraint);
+    uint32_t* arena_trace();  // 2^log_n x width words: what a host trace is uploaded into (allocated by the first call)
+    bool pending() const;
+    hipStream_t stream() const;
+    uint32_t log_n() const;
+    uint32_t width() const;
+    uint32_t n_public() const;
+    int device() const;
+
+  private:
+    struct Impl;
+    Impl* im;
+};
+
 bool pcs_point_on_lde_coset(const uint32_t z[4], uint32_t log_big);
 // A challenger as the words a device transcript imports and exports (transcript.hip.h DevState up to `pis`): the duplex state,
 // buffers and counters, then the Keccak streaming sponge.  import refuses counters no challenger can hold (pending inputs >= 8,
